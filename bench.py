@@ -13,15 +13,19 @@ pairs/step = B² (in-batch) + B·N (explicit) per GPU; N GPUs run data-parallel
 replicas on their own batches with one RCCL all-reduce of the flat grad slab
 (weak scaling).
 
-Extras on the same line (rank 0): Flat-IP top-K QPS at config 3 (6,040 users x
-3,416 items, fp32, k=10) and a config-4 shard (65,536 queries x 125,000
-items, fp16, k=100), the HBM row-gather rate (config-5 table shard, bf16
-rows of 256), the config-5 in-batch scoring CE (8,192 x 8,192 x 256 bf16,
+A plain run sets up, warms up, times the K steps and prints the headline line.
+--dump-outputs DIR also writes what the last timed step returned to its
+caller (the loss triple) as DIR/loss.npy.
+
+With --full, extras on the same line (rank 0): Flat-IP top-K QPS at config 3
+(6,040 users x 3,416 items, fp32, k=10) and a config-4 shard (65,536 queries x
+125,000 items, fp16, k=100), the HBM row-gather rate (config-5 table shard,
+bf16 rows of 256), the config-5 in-batch scoring CE (8,192 x 8,192 x 256 bf16,
 forward and forward+backward on the 16-bit MFMA), the live roofline of the
 dominant kernel, and the CPU baseline (the oracle's torch-CPU restatement of
 the same step on this host's cores).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
        torchrun --nproc-per-node N bench.py --gpus N ...
 """
 import argparse
@@ -662,17 +666,44 @@ def c5_sharded_step(dev, dist, rank, world, reps=10):
     return out
 
 
+def dump_outputs(out_dir, loss):
+    """What the last timed step returned to its caller, as ``loss.npy``: the
+    float64 [3] loss buffer (mixed, explicit, in-batch) of FusedTrainStep.replay
+    / __call__. Inputs, initial weights and dropout seeds are fixed, so two
+    builds run the same steps; the losses of two runs of one build agree to
+    about 1e-5 relative (measured: 5e-6 after 25 steps, 5e-5 after 2,010).
+
+    The model state the step updates in place is left out on purpose: it does
+    not compare from run to run. The gradient sums use fp32 atomics (order
+    dependent in the last bits) and Adam scales every update to about lr
+    whatever the gradient's size, so elements whose true gradient is zero (the
+    biases ahead of a BatchNorm) walk by up to lr per step on rounding noise
+    alone: two runs of one build differ there by 1.4e-4 after 25 steps and by
+    0.05 (of values up to 0.1) after 2,010."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), loss.detach().cpu().numpy().astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--no-extras", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (its loss triple) as DIR/loss.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline of the dominant kernel, the top-K / gather / in-batch / "
+                         "feeder / C1 extras and the CPU baselines (default: the headline figure only)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the extras")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--cpu-budget", type=float, default=10.0)
     ap.add_argument("--eager", action="store_true",
                     help="time eager steps (default: hipGraph replays of the captured step, inputs copied in)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:  # a plain run measures the headline figure only
+        args.no_extras = args.no_cpu_baseline = True
     # hipGraph replay (default): one graph per step on one GPU; under data
     # parallelism two graphs (gradients; clip+Adam) with the RCCL all-reduce of
     # the flat grad slab launched between them (FusedTrainStep.capture)
@@ -697,13 +728,15 @@ def main():
 
     for i in range(args.warmup):
         run(i)
-    # calibration step (eager, untimed): which ABI call dominates the step?
+    # --full, calibration step (eager, untimed): which ABI call dominates the step?
     # (a GPU spin before each call keeps host submission gaps out of the events)
-    TIMER.enable(spacer_cycles=SPACER_CYCLES)
-    run(args.warmup)
-    cal = TIMER.summary()
-    TIMER.disable()
-    dominant = max(cal, key=lambda k: cal[k]["total_ms"])
+    cal = dominant = None
+    if args.full:
+        TIMER.enable(spacer_cycles=SPACER_CYCLES)
+        run(args.warmup)
+        cal = TIMER.summary()
+        TIMER.disable()
+        dominant = max(cal, key=lambda k: cal[k]["total_ms"])
 
     # timed region: eager steps, HIP events around every launch of the dominant
     # kernel on its launching stream (the roofline is measured live here).
@@ -729,7 +762,7 @@ def main():
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
-    if not args.graph:
+    if args.full and not args.graph:
         TIMER.enable([dominant])
     t0 = time.perf_counter()
     for i in range(args.steps):
@@ -739,20 +772,52 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    if args.graph:
-        TIMER.enable([dominant], spacer_cycles=SPACER_CYCLES)
-        for i in range(args.steps):
-            run(i)
-    live = TIMER.summary()
-    TIMER.disable()
+    final_loss = float(loss[0].item())
+    if args.dump_outputs and rank == 0:  # before the roofline pass below steps the model on
+        dump_outputs(args.dump_outputs, loss)
+    live = None
+    if args.full:
+        if args.graph:
+            TIMER.enable([dominant], spacer_cycles=SPACER_CYCLES)
+            for i in range(args.steps):
+                run(i)
+        live = TIMER.summary()
+        TIMER.disable()
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    final_loss = float(loss[0].item())
 
     pairs_per_step = 1024 * 1024 + 1024 * 16
     value = world * args.steps * pairs_per_step / elapsed
+    result = {
+        "metric": "user-item pairs scored/sec (train) + top-K queries/sec, emb_dim=128",
+        "value": value, "unit": "pairs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": 1000.0 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": value / BASELINE_MD_C2_PAIRS_PER_S, "vs_baseline_source": (
+            f"BASELINE.md §2: the reference's own CPU C2 step, {BASELINE_MD_C2_MS:g} ms = "
+            f"{BASELINE_MD_C2_PAIRS_PER_S / 1e6:.2f} M pairs/s (survey container, 8 ATen threads; a different "
+            f"machine from this run: vs_cpu_baseline_same_box, under --full, divides by cpu_baseline.value "
+            f"measured here)"),
+        "dtype": "f32",
+        "data": "synthetic ML-1M-shaped (6040 users x 3416 movies, seeded; ratings.dat unavailable)",
+        "config": {"workload": "C2: MovieLens-1M two-tower train step, emb 128, batch 1024, 16 negatives, "
+                               "hidden [256,128], dropout 0.2, tau 0.05, Adam+clip",
+                   "global_batch": 1024 * world, "emb_dim": 128, "num_negatives": 16,
+                   "parallelism": f"dp{world}", "final_loss": final_loss},
+    }
+    if args.full:
+        result["roofline"] = roofline(args, cal, live, dominant)
+    if rank == 0 and not args.full:
+        print(json.dumps(result), flush=True)
+    if args.full:
+        full_legs(args, result, dev, dist, rank, world, host, value)
+    if dist is not None:
+        dist.destroy_process_group()
+
+
+def roofline(args, cal, live, dominant):
+    """--full: the live roofline of the step's dominant kernel."""
     d = live[dominant]
     per_launch_flops = d["flops"] / max(1, d["count"])
     per_launch_bytes = d["bytes"] / max(1, d["count"])
@@ -782,24 +847,11 @@ def main():
                  "avg_launch_ms": d["avg_ms"], "step_share": cal[dominant]["total_ms"] /
                  max(1e-9, sum(v["total_ms"] for v in cal.values())),
                  "calibration_ms": {k: round(v["total_ms"], 4) for k, v in cal.items()}})
+    return roof
 
-    result = {
-        "metric": "user-item pairs scored/sec (train) + top-K queries/sec, emb_dim=128",
-        "value": value, "unit": "pairs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": 1000.0 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "vs_baseline_source": (
-            f"BASELINE.md §2: the reference's own CPU C2 step, {BASELINE_MD_C2_MS:g} ms = "
-            f"{BASELINE_MD_C2_PAIRS_PER_S / 1e6:.2f} M pairs/s (survey container, 8 ATen threads; a different "
-            f"machine from this run: vs_cpu_baseline_same_box divides by cpu_baseline.value measured here)"),
-        "dtype": "f32",
-        "data": "synthetic ML-1M-shaped (6040 users x 3416 movies, seeded; ratings.dat unavailable)",
-        "config": {"workload": "C2: MovieLens-1M two-tower train step, emb 128, batch 1024, 16 negatives, "
-                               "hidden [256,128], dropout 0.2, tau 0.05, Adam+clip",
-                   "global_batch": 1024 * world, "emb_dim": 128, "num_negatives": 16,
-                   "parallelism": f"dp{world}", "final_loss": final_loss},
-        "roofline": roof,
-    }
-    result["vs_baseline"] = value / BASELINE_MD_C2_PAIRS_PER_S
+
+def full_legs(args, result, dev, dist, rank, world, host, value):
+    """--full: the extras and the CPU baselines, added to ``result``; prints the line."""
     scaling = c5 = repl = None
     if not args.no_extras:  # collective: every rank
         try:
@@ -857,8 +909,6 @@ def main():
             scaling["vs_cpu"] = scaling["qps"] / cb["qps"]
     if rank == 0:
         print(json.dumps(result), flush=True)
-    if dist is not None:
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

@@ -10,5 +10,5 @@ timeout -k 10 500 python -u -m pytest ${FIRST:-tests/test_gpu_dist.py tests/test
 tail -3 $O/pytest_first.log
 timeout -k 10 700 python -u -m pytest tests -m gpu -x -q --timeout 250 --timeout-method thread > $O/pytest_gpu.log 2>&1 || { tail -60 $O/pytest_gpu.log; exit 1; }
 tail -3 $O/pytest_gpu.log
-timeout -k 10 300 python -u bench.py > $O/bench.json 2> $O/bench.err || { tail -30 $O/bench.err; exit 1; }
+timeout -k 10 300 python -u bench.py --full > $O/bench.json 2> $O/bench.err || { tail -30 $O/bench.err; exit 1; }
 cat $O/bench.json

@@ -71,8 +71,8 @@ for (name, fam), b in tot.items():
     launches = max(disp[(k, f)] for (k, f) in disp if k == name)
     per[name] += b / launches
 json.dump({"source": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE, separate passes: "
-                     "bench.py --steps 10 --warmup 3 --no-extras --no-cpu-baseline, tools/prof_topk.py 100 2 and "
-                     "tools/prof_gather.py 2",
+                     "bench.py --full --steps 10 --warmup 3 --no-extras --no-cpu-baseline, "
+                     "tools/prof_topk.py 100 2 and tools/prof_gather.py 2",
            "correction": "bytes = 2*FETCH_SIZE + WRITE_SIZE (gfx950 FETCH_SIZE halves wide 16-B/lane reads)",
            "kernel_sources_sha": {k: _bench_module()._kernel_sources_sha(k) for k in per},
            "bytes_per_launch": {k: round(v) for k, v in per.items()},
