@@ -97,11 +97,13 @@ __device__ __forceinline__ const Cand& entry(const Cand* buf, int n0, int idx) {
 // Shrink one query's buffer (halves of n0 and n1 entries, k <= n0+n1) to a
 // superset of its top k, re-dealt over the halves (entry j → half j&1, slot
 // j>>1). Returns the new total; thr = the new filter threshold (v >= thr).
-// CAP = the buffer's entry capacity (v2/v3: kCap; v4: its own).
-template <int CAP = kCap>
+// CAP = the buffer's entry capacity (v2/v3: kCap; v4: its own). KEEP = the most
+// entries the radix bucket may leave (more: the exact sort, which leaves k);
+// the caller's append budget starts from ceil(KEEP / 2) entries per half.
+template <int CAP = kCap, int KEEP = CAP - 64>
 __device__ __forceinline__ int compact_query_body(Cand* __restrict__ buf, int n0, int n1, int k, uint32_t* hist,
                                                   float& thr) {
-    constexpr int kE = CAP / 64, kHalf = CAP / 2, kCap = CAP;
+    constexpr int kE = CAP / 64, kHalf = CAP / 2;
     const int lane = threadIdx.x & 63;
     const int n = n0 + n1;
     float s[kE];
@@ -130,7 +132,8 @@ __device__ __forceinline__ int compact_query_body(Cand* __restrict__ buf, int n0
         keep[e] = sel[e] && key[e] >= T;
         total += __popcll(__ballot(keep[e]));
     }
-    if (total <= kCap - 64) {
+    static_assert(KEEP >= kMaxKv2 && KEEP <= CAP, "the bucket must be able to hold the k best");
+    if (total <= KEEP) {
         int base = 0;
 #pragma unroll
         for (int e = 0; e < kE; ++e) {
@@ -162,10 +165,10 @@ __device__ __forceinline__ int compact_query_body(Cand* __restrict__ buf, int n0
     return k;
 }
 // out of line (v2/v3 scans: keeps the compaction's registers out of the loop)
-template <int CAP = kCap>
+template <int CAP = kCap, int KEEP = CAP - 64>
 __device__ __noinline__ int compact_query(Cand* __restrict__ buf, int n0, int n1, int k, uint32_t* hist,
                                           float& thr) {
-    return compact_query_body<CAP>(buf, n0, n1, k, hist, thr);
+    return compact_query_body<CAP, KEEP>(buf, n0, n1, k, hist, thr);
 }
 
 // Sort one query's buffer (halves of n0 / n1 entries, n0+n1 <= 64*E) and
@@ -370,6 +373,11 @@ __global__ __launch_bounds__(512) void flatip_topk_v2_kernel(Args a, int splits,
     };
     // compact every buffer of this wave that may overflow on the next sub-tile
     auto maybe_compact = [&]() {
+        // checked after every sub-tile (<= 16 appends per half): a half that
+        // passes holds <= kHalf - 16, and a compaction leaves <= (kCap - 64 + 1) / 2
+        // (the first bound is the check's own constant; the assert ties the second to it)
+        static_assert((kCap - 64 + 1) / 2 <= kHalf - 16,
+                      "v2: a half overflows before the next compaction check");
         const uint64_t m = __ballot(cnt > kHalf - 16);
         uint32_t need = static_cast<uint32_t>(m) | static_cast<uint32_t>(m >> 32);
         if (!need) return;

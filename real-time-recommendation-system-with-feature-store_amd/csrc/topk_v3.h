@@ -163,8 +163,27 @@ __global__ __launch_bounds__(512) void flatip_topk_v3_kernel(Args a, int splits,
     uint32_t woff = woff0;
     // checked once per stage (or per pair of sub-tiles): room for the appends until the next check;
     // small k compacts early too — a half holding ~2k entries refreshes a stale threshold
+    // The append budget of a half. Appends run one sub-tile late (step()
+    // appends the sub-tile before), 16 per half and sub-tile at most. With the
+    // check at the top of a stage a half takes NSUB sub-tiles = kHead appends
+    // from one check to the next, and after the LAST check kHead plus the final
+    // select() of the held-back sub-tile: kHead + kTail (PAIRCMP: two sub-tiles
+    // between checks, two plus the final one after the last). A half enters
+    // such a stretch with at most kRoom3 entries, from either side of the check:
+    //  * it passed the check: <= lim_n <= kRoom3;
+    //  * it was compacted: <= (kKeep3 + 1) / 2, what the radix bucket may keep
+    //    (v2's own bound, kCap - 64, would leave 224 of a half's 256 entries:
+    //    scores that rise along the rows inside one 16-bit key bucket — every
+    //    compaction keeps everything, every new row passes — then run a half
+    //    over its end by up to 48 entries, into the other half and the next query).
     constexpr int kHead = RT_TOPK3_PAIRCMP ? 2 * 16 : C::NSUB * 16;  // appends between checks, at most
-    const int lim_n = kRefreshMul > 0 ? min(kHalf - kHead, kRefreshMul * k + 32) : kHalf - kHead;
+    constexpr int kTail = 16;                                        // the final select() after the last check
+    constexpr int kRoom3 = kHalf - kHead - kTail;
+    constexpr int kKeep3 = 2 * kRoom3;
+    static_assert(kRoom3 + kHead + kTail <= kHalf && (kKeep3 + 1) / 2 <= kRoom3,
+                  "v3: a half overflows before the next compaction check (or the end of the scan)");
+    static_assert(kKeep3 >= kMaxKv3, "v3: a compaction must be able to keep the k best");
+    const int lim_n = kRefreshMul > 0 ? min(kRoom3, kRefreshMul * k + 32) : kRoom3;
     const uint32_t woff_lim = woff0 + static_cast<uint32_t>(lim_n * sizeof(Cand));
 
     // ---- DMA plan: this wave's pieces w, w+8, ... of a stage ----
@@ -287,7 +306,7 @@ __global__ __launch_bounds__(512) void flatip_topk_v3_kernel(Args a, int splits,
             const int cnt = static_cast<int>((woff - woff0) / sizeof(Cand));
             const int n0 = __shfl(cnt, c, 64), n1 = __shfl(cnt, c + 32, 64);
             float nt;
-            const int nn = compact_query(cbase + static_cast<int64_t>(c) * kCap, n0, n1, k, whist, nt);
+            const int nn = compact_query<kCap, kKeep3>(cbase + static_cast<int64_t>(c) * kCap, n0, n1, k, whist, nt);
             if (col == c) {
                 woff = woff0 + static_cast<uint32_t>((half ? nn >> 1 : (nn + 1) >> 1) * sizeof(Cand));
                 thr = nt;
@@ -460,7 +479,7 @@ __global__ __launch_bounds__(512) void flatip_topk_v3_kernel(Args a, int splits,
         } else {
             Cand* b = cbase + static_cast<int64_t>(c) * kCap;
             float nt;
-            const int nn = compact_query(b, n0, n1, k, whist, nt);
+            const int nn = compact_query<kCap, kKeep3>(b, n0, n1, k, whist, nt);
             n0 = (nn + 1) >> 1;
             n1 = nn >> 1;
             if (n0 + n1 <= 128) emit_sorted<2>(b, n0, n1, k, orow, irow, a.id_offset);

@@ -392,9 +392,49 @@ __global__ __launch_bounds__(512) void flatip_topk_v4_scan(Args a, int splits, i
 #pragma unroll
         for (int j = 0; j < QS; ++j) thr[j] = qok[j] ? fmaxf(a.thr_in[qw + j * 32 + col], -FLT_MAX) : INFINITY;
     }
+    // ---- the append budget of a candidate region ----
+    // A region (shared layout: the query's kCap entries, both lane halves
+    // appending; per-half layout: one half's kHalf entries) takes at most kSub
+    // appends per 32-row sub-tile of its query set: 16 rows per lane half.
+    // maybe_compact() leaves a region at <= kRoom entries (a compaction keeps at
+    // most kLimit = kRoom), so the region must hold kRoom plus everything
+    // appended before the next check runs, or, after the last check, before the
+    // scan ends. In sub-tiles of one set (main_pass; set QS-1, or the only set
+    // at QS = 1, is stored one sub-tile late, the other sets at once):
+    //  * RING = 4, a check at the end of EVERY stage, the last one included:
+    //      start -> 1st check          NSUB      (late set: NSUB - 1)
+    //      check -> next check         NSUB      (late set: the held-back
+    //                                             sub-tile of the stage before
+    //                                             + NSUB - 1 of this one)
+    //      last check -> end of scan   0         (late set: 1, the trailing flush)
+    //  * RING = 3, a check before the last sub-tile of EVERY stage, the last
+    //    one included:
+    //      start -> 1st check          NSUB - 1  (late set: NSUB - 2)
+    //      check -> next check         NSUB      (late set: NSUB)
+    //      last check -> end of scan   1         (late set: 2, with the flush)
+    //    (a check only at the END of the last stage would not do here: the late
+    //    set would append NSUB + 1 sub-tiles since the check inside the stage
+    //    before.)
+    // A ragged last stage only skips sub-tiles. The maximum is kBetween = NSUB
+    // sub-tiles = kHead appends per lane half; before the check of the last
+    // stage existed the tail was NSUB + 1 (RING 4) or NSUB + 2 (RING 3)
+    // sub-tiles and a region at kRoom ran up to 64 entries into its neighbour.
+    // What the static_assert below binds is kRoom to kBetween as written here:
+    // it fires when kRoom (or NSUB, kCap, the layout) is changed without the
+    // other. It cannot see WHERE the checks sit: a moved or dropped check is
+    // covered only by this table and by count_model in tests/_ordered_corpora.py
+    // (tests/test_ordered_corpora_cpu.py), which mirror main_pass and must be
+    // changed with it.
+    constexpr int kSub = kShared ? 32 : 16;    // appends per region and sub-tile, at most
+    constexpr int kRegion = kShared ? kCap : kHalf;
+    constexpr int kTailSubs = C::RING == 4 ? 1 : 2;  // sub-tiles of the late set after the last check
+    constexpr int kBetween = C::NSUB > kTailSubs ? C::NSUB : kTailSubs;
     constexpr int kHead = C::NSUB * 16;  // appends per half between two compaction checks, at most
     // shared region: both halves append up to kHead each between checks
     constexpr int kRoom = kShared ? kCap - 2 * kHead : kHalf - kHead;
+    static_assert(kRoom + kBetween * kSub <= kRegion,
+                  "v4: a region at kRoom overflows before the next compaction check (or the end of the scan)");
+    static_assert(kRoom >= kMaxK, "v4: a compaction must be able to keep the k best");
     constexpr uint32_t kLimBytes = static_cast<uint32_t>(kRoom * sizeof(Cand));
     constexpr int kLimit = kRoom;  // a compaction keeps at most this many entries (in all)
 
@@ -774,8 +814,9 @@ __global__ __launch_bounds__(512) void flatip_topk_v4_scan(Args a, int splits, i
                     RT_PT(const uint64_t c2 = clock64(); pc_wait += c2 - c1;)
                     raw_barrier();
                     RT_PT(const uint64_t c3 = clock64(); pc_bar += c3 - c2;)
+                    // every stage, the last one too: see the append budget at kRoom
+                    maybe_compact();  // fragments of this sub-tile are live (in registers)
                     if (more) {
-                        maybe_compact();  // fragments of this sub-tile are live (in registers)
                         if (v + 2 < nst) fetch(stage_t0(v + 2, false), cur == 0 ? C::RING - 1 : cur - 1);
                         mk_next = issued;
                     }
@@ -831,7 +872,9 @@ __global__ __launch_bounds__(512) void flatip_topk_v4_scan(Args a, int splits, i
             }
             RT_PT(pc_main += clock64() - c0;)
             if constexpr (R4) {
-                if (more) maybe_compact();  // wave-local: one stage of appends between checks
+                // wave-local: one stage of appends between checks; after the last
+                // stage too, so that only the trailing flush follows the last check
+                maybe_compact();
                 if (more && (v & 1)) {
                     wait_vm_le(issued - mk_next);  // this wave's pieces of stages v+1, v+2
                     raw_barrier();
