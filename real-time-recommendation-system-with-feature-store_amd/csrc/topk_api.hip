@@ -1,13 +1,8 @@
 // C ABI for the Flat-IP top-K (rt_flatip_topk) and the candidate-list merge
 // (rt_topk_merge, used for split corpora and for the multi-GPU merge of
 // per-shard top-K lists after an RCCL all-gather).
-#include <array>
-#include <cmath>
-#include <map>
-#include <mutex>
-#include <tuple>
-
 #include "topk_impl.h"
+#include "topk_sample_plan.h"
 
 namespace rt {
 namespace topk {
@@ -222,100 +217,12 @@ static int g_v4_joint = 1;    // 1: over several splits, one corpus-wide thresho
 static int g_dense = 1;       // 1: fp32 small corpora take the GEMM + select pair (topk_dense.h)
 static int g_v4_presample = 1;  // 1: joint thresholds from one sample-only launch over every split
 
-// Smallest failure-safe rank: the least r in [1, r_max] with P(Bin(n, f) >= r)
-// <= 1e-6 (r > n: probability 0, safe), 0 when none. The binomial tail of
-// every r comes from one pass over the pmf (n <= kMaxK terms), summed from the
-// top — the planner below evaluates it for up to 63 strides per plan, on the
-// host path of every search call (a log-sum-exp tail per (stride, rank) pair
-// cost ~1.7 ms per call at the C4 shapes).
-inline int safe_rank(int n, double f, int r_max) {
-    static const auto lf = [] {  // log i!
-        std::array<double, kMaxK + 2> t{};
-        for (int i = 0; i <= kMaxK + 1; ++i) t[i] = std::lgamma(i + 1.0);
-        return t;
-    }();
-    if (n < 0 || n > kMaxK || !(f > 0.0)) return 0;
-    if (f >= 1.0) return n + 1 <= r_max ? n + 1 : 0;  // X = n: only r > n is safe
-    double tail[kMaxK + 2];
-    tail[n + 1] = 0.0;
-    const double lf_ = std::log(f), lg = std::log1p(-f);
-    for (int i = n; i >= 0; --i) tail[i] = tail[i + 1] + std::exp(lf[n] - lf[i] - lf[n - i] + i * lf_ + (n - i) * lg);
-    for (int r = 1; r <= r_max; ++r)
-        if (r > n || tail[r] <= 1e-6) return r;
-    return 0;
-}
-
-// the v4 sample: the sparsest stride whose smallest safe rank keeps the expected
-// candidates per query, rank/f, within RT_TOPK_V4_APPEND_CAP. "Safe": the
-// estimate overshoots the split's k-th score (a rescan) with probability <= 1e-6
-// — P(>= rank of the split's top k fall in the sample) for a 1/f sample; the
-// group-maximum estimate sits at or below the item rank, so this bounds it.
-// Cap 500 (round 6; 960 before): k = 100 at the C4 shard and the 1M corpus
-// takes stride 32 / rank 15 (~460 appends) instead of 64 / 11 (~670): the
-// twice denser sample costs less than the appends and finish input it saves,
-// 3-7 % at 125K and 2 % at 1M (profiles/r06_topk_stride_sweep.txt).
-#ifndef RT_TOPK_V4_APPEND_CAP
-#define RT_TOPK_V4_APPEND_CAP 500.0
-#endif
-#ifndef RT_TOPK_V4_MAX_STRIDE
-#define RT_TOPK_V4_MAX_STRIDE 64
-#endif
-// (stride, rank) of the v4 sample over `items_per_split` rows: the largest
-// stride whose failure-safe rank keeps the expected appends (rank * stride,
-// per query) within RT_TOPK_V4_APPEND_CAP
-inline void plan_v4_sample(int k, int64_t items_per_split, int& stride, int& rank) {
-    const int64_t nst = (items_per_split + v4::Cfg4<__half, 8>::NT - 1) / v4::Cfg4<__half, 8>::NT;
-    stride = 0;
-    rank = 0;
-    for (int st = RT_TOPK_V4_MAX_STRIDE; st >= 2; --st) {
-        const int64_t nsa = (nst + st - 1) / st;
-        if (nsa < 4) continue;  // fewer than 32 groups per query in the sample
-        const double f = static_cast<double>(nsa) / static_cast<double>(nst);
-        const int r = safe_rank(k, f, 2 * v4::kList);
-        if (r > 0 && r / f <= RT_TOPK_V4_APPEND_CAP) { stride = st; rank = r; return; }
-    }
-}
-
-// the same, for a sample taken split by split (every stride-th stage of each
-// split: the presampled plan, or shards of a corpus on several GPUs): the
-// sampled fraction is sum_s ceil(stages_s / stride) / stages
-inline void plan_v4_sample_split(int k, int64_t nx, int64_t items_per_split, int& stride, int& rank) {
-    constexpr int NT = v4::Cfg4<__half, 8>::NT;
-    const int64_t nst = (nx + NT - 1) / NT;
-    const int64_t sps = (items_per_split + NT - 1) / NT;  // stages per full split
-    const int64_t nfull = nst / sps, rem = nst - nfull * sps;
-    stride = 0;
-    rank = 0;
-    for (int st = RT_TOPK_V4_MAX_STRIDE; st >= 2; --st) {
-        const int64_t nsa = nfull * ((sps + st - 1) / st) + (rem + st - 1) / st;
-        if (nsa < 4) continue;
-        const double f = static_cast<double>(nsa) / static_cast<double>(nst);
-        const int r = safe_rank(k, f, 2 * v4::kList);
-        if (r > 0 && r / f <= RT_TOPK_V4_APPEND_CAP) { stride = st; rank = r; return; }
-    }
-}
-
-// (stride, rank) per (kind, k, rows, rows per split), computed once per shape
-inline void plan_v4_sample_cached(bool split_form, int k, int64_t nx, int64_t items_per_split, int& stride,
-                                  int& rank) {
-    static std::mutex mu;
-    static std::map<std::tuple<bool, int, int64_t, int64_t>, std::pair<int, int>> memo;
-    const auto key = std::make_tuple(split_form, k, nx, items_per_split);
-    {
-        std::lock_guard<std::mutex> g(mu);
-        const auto it = memo.find(key);
-        if (it != memo.end()) {
-            stride = it->second.first;
-            rank = it->second.second;
-            return;
-        }
-    }
-    if (split_form) plan_v4_sample_split(k, nx, items_per_split, stride, rank);
-    else plan_v4_sample(k, items_per_split, stride, rank);
-    std::lock_guard<std::mutex> g(mu);
-    if (memo.size() > 4096) memo.clear();
-    memo[key] = {stride, rank};
-}
+// the sample planner (topk_sample_plan.h) restates these; the kernels own them
+static_assert(splan::kStageRows == v4::Cfg4<__half, 4>::NT && splan::kStageRows == v4::Cfg4<__half, 8>::NT,
+              "sample plan: rows per v4 stage");
+static_assert(splan::kMaxK == kMaxK && v4::kMaxK <= kMaxK, "sample plan: the rank table covers every k");
+static_assert(splan::kSampleList == v4::kSampleList && v4::kSampleList == 2 * v4::kList,
+              "sample plan: group maxima per query");
 
 // v4 (sampled-threshold scan + finish) for 16-bit, d <= 128, 32 < k <= 128 over
 // a large corpus with enough queries to fill the chip at <= 8 item splits
@@ -347,18 +254,17 @@ inline bool plan_v4(int64_t nq, int64_t nx, int d, int dtype, int k, Plan& p) {
     // splits times that); one split: the per-split form
     p.v4_joint = (p.splits > 1 && g_v4_joint) ? 1 : 0;
     p.v4_presample = (p.v4_joint && g_v4_presample) ? 1 : 0;
-    if (p.v4_presample) plan_v4_sample_cached(true, k, nx, p.items_per_split, p.stride, p.rank);
-    else plan_v4_sample_cached(false, k, 0, p.v4_joint ? nx : p.items_per_split, p.stride, p.rank);
+    // the rows a sample walks as one run of stages: a split (presampled: every
+    // split of the corpus; per split: that one alone), or, joint without the
+    // presample, the whole corpus
+    const int64_t run = (p.v4_joint && !p.v4_presample) ? nx : p.items_per_split;
+    const splan::SamplePlan sp = splan::plan_sample_cached(k, p.v4_presample ? nx : run, run);
+    p.stride = sp.stride;
+    p.rank = sp.rank;
     if (p.v4_presample && (p.stride <= 0 || p.rank <= 0)) p.v4_presample = 0;  // no sample fits: round-4 form
     if (g_v4_stride > 0) p.stride = g_v4_stride;
     if (g_v4_rank >= 0) p.rank = g_v4_rank;
-    const int64_t q_pad = static_cast<int64_t>(p.q_tiles) * QT;
-    p.cand_bytes = static_cast<size_t>(p.splits) * q_pad * v4::kCap * sizeof(Cand);
-    p.meta_bytes = static_cast<size_t>(p.splits) * q_pad * 2 * sizeof(int);
-    p.fail_bytes = p.v4_joint ? static_cast<size_t>(q_pad) * sizeof(int) : 0;
-    p.lists_bytes = p.v4_presample ? static_cast<size_t>(p.splits) * q_pad * v4::kSampleList * sizeof(float) : 0;
-    p.thr_bytes = p.v4_presample ? static_cast<size_t>(q_pad) * sizeof(float) : 0;
-    p.part_bytes = 0;
+    p.cand_bytes = static_cast<size_t>(p.splits) * v4::q_pad(p) * v4::kCap * sizeof(Cand);
     return true;
 }
 
@@ -406,7 +312,52 @@ inline Plan make_plan(int64_t nq, int64_t nx, int d, int dtype, int k, const Sha
     return p;
 }
 
-inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }
+// The workspace of one call: the byte offset of every region, in this order,
+// and their sum. The one place that knows the layout — the size queries, the
+// size checks and the pointers of rt_flatip_topk and of the shard entry points
+// all come from it. A region starts 256-byte aligned, except that the regions
+// after `part` follow its unpadded end (a multiple of 4 bytes; the 4-byte k-th
+// keys are all that ever follows a non-empty `part`). The v4 regions hold one
+// row per padded query and exist as the plan's flags say.
+struct Layout {
+    size_t cand;      // candidate buffers (the dense plan: the score slab)
+    size_t part;      // per-split partial lists: [split][chunk][k] scores, then ids at part_ids
+    size_t part_ids;
+    size_t meta;      // v4: per-(split, query, half) entry counts
+    size_t kth;       // register lists over several splits: per-query shared k-th keys
+    size_t fail;      // v4 joint: per-query rescue flags
+    size_t lists;     // v4 presample: [split][q_pad][32] sampled group maxima
+    size_t thr;       // v4 presample: per-query thresholds
+    size_t total;
+};
+inline Layout layout_of(const Plan& p) {
+    const auto al = [](size_t x) { return (x + 255) / 256 * 256; };
+    const size_t q_pad = p.v4 ? v4::q_pad(p) : 0;
+    Layout l{};
+    l.part = l.cand + al(p.cand_bytes);
+    l.part_ids = l.part + p.part_bytes / (sizeof(float) + sizeof(int64_t)) * sizeof(float);
+    l.meta = l.part + p.part_bytes;
+    l.kth = l.meta + al(p.splits * q_pad * 2 * sizeof(int));
+    l.fail = l.kth + al(p.kth_bytes);
+    l.lists = l.fail + al(p.v4_joint ? q_pad * sizeof(int) : 0);
+    l.thr = l.lists + al(p.v4_presample ? p.splits * q_pad * v4::kSampleList * sizeof(float) : 0);
+    l.total = l.thr + al(p.v4_presample ? q_pad * sizeof(float) : 0);
+    return l;
+}
+constexpr size_t kWorkspaceSlack = 256;  // the size queries add it to Layout::total
+
+template <typename T>
+inline T* region(void* workspace, size_t offset) {
+    return reinterpret_cast<T*>(static_cast<char*>(workspace) + offset);
+}
+// the regions every chunk of a call shares (kth and part: see rt_flatip_topk)
+inline void bind_workspace(Args& a, void* workspace, const Layout& l) {
+    a.cand = region<Cand>(workspace, l.cand);
+    a.meta = region<int>(workspace, l.meta);
+    a.fail = region<int>(workspace, l.fail);
+    a.v4_lists = region<float>(workspace, l.lists);
+    a.v4_thr = region<float>(workspace, l.thr);
+}
 
 }  // namespace topk
 }  // namespace rt
@@ -417,8 +368,7 @@ extern "C" size_t rt_flatip_topk_workspace_bytes(int64_t nq, int64_t nx, int d, 
     if (nq <= 0 || k <= 0 || k > topk::kMaxK || d <= 0) return 256;
     if (dtype != RT_F32 && dtype != RT_F16 && dtype != RT_BF16) return 256;
     const topk::Plan p = topk::make_plan(nq, nx, d, dtype, k, topk::shape_for(dtype, d, k));
-    return topk::align256(p.cand_bytes) + p.part_bytes + topk::align256(p.meta_bytes) + topk::align256(p.kth_bytes) +
-           topk::align256(p.fail_bytes) + topk::align256(p.lists_bytes) + topk::align256(p.thr_bytes) + 256;
+    return topk::layout_of(p).total + topk::kWorkspaceSlack;
 }
 
 extern "C" int rt_flatip_topk(const void* queries, int64_t nq, const void* items, int64_t nx, int d,
@@ -435,18 +385,9 @@ extern "C" int rt_flatip_topk(const void* queries, int64_t nq, const void* items
     if ((reinterpret_cast<uintptr_t>(queries) | reinterpret_cast<uintptr_t>(items)) & 15) return RT_ERR_INVALID;
     if (exclude_bits && exclude_words < (nx + 31) / 32) return RT_ERR_INVALID;
     const topk::Plan p = topk::make_plan(nq, nx, d, dtype, k, topk::shape_for(dtype, d, k));
-    const size_t cand_al = topk::align256(p.cand_bytes);
-    if (!workspace ||
-        workspace_bytes < cand_al + p.part_bytes + topk::align256(p.meta_bytes) + topk::align256(p.kth_bytes) +
-                              topk::align256(p.fail_bytes) + topk::align256(p.lists_bytes) + topk::align256(p.thr_bytes))
-        return RT_ERR_WORKSPACE;
+    const topk::Layout lay = topk::layout_of(p);
+    if (!workspace || workspace_bytes < lay.total) return RT_ERR_WORKSPACE;
     hipStream_t st = as_stream(stream);
-    char* part = reinterpret_cast<char*>(workspace) + cand_al;
-    int* meta = reinterpret_cast<int*>(part + p.part_bytes);
-    uint32_t* kth = reinterpret_cast<uint32_t*>(part + p.part_bytes + topk::align256(p.meta_bytes));
-    int* fail = reinterpret_cast<int*>(part + p.part_bytes + topk::align256(p.meta_bytes) + topk::align256(p.kth_bytes));
-    float* v4_lists = reinterpret_cast<float*>(reinterpret_cast<char*>(fail) + topk::align256(p.fail_bytes));
-    float* v4_thr = reinterpret_cast<float*>(reinterpret_cast<char*>(v4_lists) + topk::align256(p.lists_bytes));
     const size_t esz = dtype == RT_F32 ? 4 : 2;
     for (int64_t q0 = 0; q0 < nq; q0 += p.chunk) {
         const int64_t nc = (nq - q0) < p.chunk ? (nq - q0) : p.chunk;
@@ -467,23 +408,19 @@ extern "C" int rt_flatip_topk(const void* queries, int64_t nq, const void* items
         a.k = k;
         a.excl = exclude_bits ? exclude_bits + q0 * exclude_words : nullptr;
         a.excl_words = exclude_words;
-        a.cand = reinterpret_cast<Cand*>(workspace);
         a.id_offset = id_offset;
-        a.meta = meta;
-        a.fail = fail;
-        a.v4_lists = v4_lists;
-        a.v4_thr = v4_thr;
+        topk::bind_workspace(a, workspace, lay);
         if (p.kth_bytes) {
-            a.kth_shared = kth;
-            const hipError_t e = hipMemsetAsync(kth, 0, static_cast<size_t>(nc) * sizeof(uint32_t), st);
+            a.kth_shared = topk::region<uint32_t>(workspace, lay.kth);
+            const hipError_t e = hipMemsetAsync(a.kth_shared, 0, static_cast<size_t>(nc) * sizeof(uint32_t), st);
             if (e != hipSuccess) {
                 set_last_error("hipMemsetAsync(topk kth)", e);
                 return RT_ERR_HIP;
             }
         }
         if (p.splits > 1 && !p.v4) {  // per-split lists [split][nc][k], merged below
-            a.out_s = reinterpret_cast<float*>(part);
-            a.out_i = reinterpret_cast<int64_t*>(part + static_cast<size_t>(p.splits) * p.chunk * k * sizeof(float));
+            a.out_s = topk::region<float>(workspace, lay.part);
+            a.out_i = topk::region<int64_t>(workspace, lay.part_ids);
         } else {
             a.out_s = os;
             a.out_i = oi;
@@ -512,6 +449,12 @@ struct ShardArgs {
     Args a;
     size_t need;
 };
+// The shard calls presample every split whatever make_plan chose for one GPU,
+// and flag nothing (a shard may hold < k of a query's top k): their workspace
+// is candidates, meta and sample lists. The threshold region that comes with
+// the presample is reserved and unused — the thresholds come from the caller
+// (rt_topk_sample_threshold over every shard's lists) — but stays part of the
+// reported size.
 inline int shard_setup(const void* queries, int64_t nq, const void* items, int64_t nx, int d, int dtype, int k,
                        void* workspace, size_t workspace_bytes, ShardArgs& s) {
     if (nq <= 0 || nx <= 0 || d <= 0 || k <= 0 || k > v4::kMaxK) return RT_ERR_INVALID;
@@ -522,11 +465,11 @@ inline int shard_setup(const void* queries, int64_t nq, const void* items, int64
     if (nx >= 0xFFFFFFFFll) return RT_ERR_UNSUPPORTED;
     s.p = make_plan(nq, nx, d, dtype, k, shape_for(dtype, d, k));
     if (!s.p.v4 || s.p.chunk < nq) return RT_ERR_UNSUPPORTED;  // one query chunk, the v4 plan
-    const int64_t q_pad = static_cast<int64_t>(s.p.q_tiles) * v4::Geo<v4::kQS>::QT;
-    const size_t lists = static_cast<size_t>(s.p.splits) * q_pad * v4::kSampleList * sizeof(float);
-    s.need = align256(s.p.cand_bytes) + align256(s.p.meta_bytes) + align256(lists) + align256(q_pad * sizeof(float));
+    s.p.v4_joint = 0;
+    s.p.v4_presample = 1;
+    const Layout lay = layout_of(s.p);
+    s.need = lay.total;
     if (!workspace || workspace_bytes < s.need) return RT_ERR_WORKSPACE;
-    char* w = reinterpret_cast<char*>(workspace);
     s.a = Args{};
     s.a.Q = queries;
     s.a.nq = nq;
@@ -534,13 +477,20 @@ inline int shard_setup(const void* queries, int64_t nq, const void* items, int64
     s.a.nx = nx;
     s.a.d = d;
     s.a.k = k;
-    s.a.cand = reinterpret_cast<Cand*>(w);
-    s.a.meta = reinterpret_cast<int*>(w + align256(s.p.cand_bytes));
-    s.a.v4_lists = reinterpret_cast<float*>(w + align256(s.p.cand_bytes) + align256(s.p.meta_bytes));
+    bind_workspace(s.a, workspace, lay);
     return RT_OK;
 }
-inline int v4_scan(int dtype, const Args& a, const Plan& p, int stride, int rank, int mode, hipStream_t st) {
-    return dtype == RT_F16 ? v4_scan_f16(a, p, stride, rank, mode, st) : v4_scan_bf16(a, p, stride, rank, mode, st);
+// one scan of the shard in `mode`, with the caller's sample in place of the plan's
+inline int shard_scan(int dtype, const Args& a, Plan p, int stride, int rank, int mode, hipStream_t st) {
+    p.stride = stride;
+    p.rank = rank;
+    return dtype == RT_F16 ? v4_scan_f16(a, p, mode, st) : v4_scan_bf16(a, p, mode, st);
+}
+// {sampled stages, stages} of a shard under plan p (the mode-3 scan of shard_scan)
+inline void shard_stage_counts(const Plan& p, int64_t nx, int stride, int64_t* counts) {
+    const splan::StageCounts c = splan::sampled_stages(nx, p.items_per_split, stride);
+    counts[0] = c.sampled;
+    counts[1] = c.total;
 }
 }  // namespace topk
 }  // namespace rt
@@ -549,22 +499,8 @@ extern "C" size_t rt_flatip_topk_shard_workspace_bytes(int64_t nq, int64_t nx, i
     topk::ShardArgs s{};
     const int rc = topk::shard_setup(reinterpret_cast<const void*>(16), nq, reinterpret_cast<const void*>(16), nx, d,
                                      dtype, k, reinterpret_cast<void*>(16), ~size_t(0), s);
-    return rc ? 0 : s.need + 256;
+    return rc ? 0 : s.need + topk::kWorkspaceSlack;
 }
-
-namespace rt {
-namespace topk {
-// {sampled stages, stages} of a shard under plan p: every split samples its
-// stages 0, stride, 2·stride, ... (the mode-3 scan of v4_scan)
-inline void shard_stage_counts(const Plan& p, int64_t nx, int stride, int64_t* counts) {
-    constexpr int NT = v4::Cfg4<__half, 8>::NT;
-    const int64_t nst = (nx + NT - 1) / NT, sps = (p.items_per_split + NT - 1) / NT;
-    const int64_t nfull = nst / sps, rem = nst - nfull * sps;
-    counts[0] = nfull * ((sps + stride - 1) / stride) + (rem + stride - 1) / stride;
-    counts[1] = nst;
-}
-}  // namespace topk
-}  // namespace rt
 
 extern "C" int rt_flatip_topk_shard_plan(int64_t nq, int64_t nx, int d, int dtype, int k, int stride,
                                          int64_t* stage_counts) {
@@ -588,18 +524,17 @@ extern "C" int rt_flatip_topk_shard_sample(const void* queries, int64_t nq, cons
     hipStream_t st = as_stream(stream);
     topk::Args b = s.a;
     b.lists_out = s.a.v4_lists;
-    const int64_t q_pad = static_cast<int64_t>(s.p.q_tiles) * topk::v4::Geo<topk::v4::kQS>::QT;
-    rc = topk::v4_scan(dtype, b, s.p, stride, 1, 3, st);
+    rc = topk::shard_scan(dtype, b, s.p, stride, 1, 3, st);
     if (rc) return rc;
-    return topk::v4::launch_threshold(s.a.v4_lists, s.p.splits, q_pad * topk::v4::kSampleList, nq, 1, nullptr, top32,
-                                      st);
+    return topk::v4::launch_threshold(s.a.v4_lists, s.p.splits, topk::v4::q_pad(s.p) * topk::v4::kSampleList, nq, 1,
+                                      nullptr, top32, st);
 }
 
 extern "C" int rt_topk_sample_rank(int k, int64_t sampled_stages, int64_t stages, int* rank) {
     if (k <= 0 || k > topk::v4::kMaxK || sampled_stages <= 0 || stages < sampled_stages || !rank) return RT_ERR_INVALID;
     const double f = static_cast<double>(sampled_stages) / static_cast<double>(stages);
     // 0: no failure-safe rank within the lists (the caller scans from -inf)
-    *rank = topk::safe_rank(k, f, topk::v4::kSampleList);
+    *rank = topk::splan::safe_rank(k, f, topk::v4::kSampleList);
     return RT_OK;
 }
 
@@ -624,10 +559,9 @@ extern "C" int rt_flatip_topk_shard_search(const void* queries, int64_t nq, cons
     b.out_s = out_scores;
     b.out_i = out_ids;
     b.id_offset = id_offset;
-    const int64_t q_pad = static_cast<int64_t>(s.p.q_tiles) * topk::v4::Geo<topk::v4::kQS>::QT;
-    rc = topk::v4_scan(dtype, b, s.p, 0, 0, 4, st);
+    rc = topk::shard_scan(dtype, b, s.p, 0, 0, 4, st);
     if (rc) return rc;
-    return topk::v4::launch_finish(b, s.p.splits, q_pad, 3, nullptr, st);  // no union check: a shard may hold < k
+    return topk::v4::launch_finish(b, s.p, 3, st);  // no union check: a shard may hold < k
 }
 
 extern "C" int rt_flatip_topk_tuning(int v4_mode, int v4_stride, int v4_rank) {

@@ -21,7 +21,7 @@
 //        maxima (both lane halves). The host picks (stride, rank) so that
 //        P(thr > the k-th score) = P(Bin(k, f) >= rank) is below 1e-6 for
 //        the sampled fraction f, with rank / f (the expected appends) at
-//        most RT_TOPK_V4_APPEND_CAP (topk_api.hip::plan_v4_sample).
+//        most RT_TOPK_V4_APPEND_CAP (topk_sample_plan.h::plan_sample).
 //      * main phase: every stage (the sample stages again), each score >= thr
 //        appended to the query's candidate buffer (per lane half: one
 //        SADDR 8-byte store at the lane's cursor). About rank / f appends
@@ -60,7 +60,7 @@ namespace v4 {
 
 constexpr int kWavesB = 8;
 constexpr int kCap = 1024;             // candidate entries per (split, query)
-constexpr int kHalf = kCap / 2;        // per owning lane half
+constexpr int kHalf = kCap / 2;        // the finish's (split, half) segments; the scan leaves half 1 empty
 constexpr int kMaxK = 128;
 constexpr int kList = 16;              // group maxima per lane and query set (sample phase)
 constexpr int kMaxSplits = 16;
@@ -71,14 +71,9 @@ constexpr int kFinishRegs = 16;        // candidates per lane the finish holds i
 #define RT_TOPK_V4_QS 2
 #endif
 constexpr int kQS = RT_TOPK_V4_QS;     // query sets of 32 per wave
-// one candidate region and cursor per query shared by its two lane halves
-// (the lanes (col, 0) and (col, 1) of a query interleave their appends), instead
-// of one region per (query, half): half the open buffer lines per block
-#ifdef RT_TOPK_V4_PER_HALF
-constexpr bool kShared = false;
-#else
-constexpr bool kShared = true;
-#endif
+// One candidate region (kCap entries) and cursor per query, shared by its two
+// lane halves: the lanes (col, 0) and (col, 1) of a query interleave their
+// appends. Half the open buffer lines per block of one region per (query, half).
 
 template <int QS>
 struct Geo {
@@ -97,11 +92,7 @@ struct Cfg4 {
     static constexpr int PIECES = SLOTS / 64;      // 1 KiB DMA pieces per stage
     static constexpr int MAXP = (PIECES + kWavesB - 1) / kWavesB;
     static constexpr int TILE_BYTES = SLOTS * 16;
-#ifdef RT_TOPK_V4_RING3  // A/B: a block barrier inside every stage at d = 128 too
-    static constexpr int RING = 3;
-#else
     static constexpr int RING = S == 8 ? 4 : 3;    // d = 128: a block barrier every other stage
-#endif
     static constexpr int HIST_BYTES = kWavesB * 1024;
     static constexpr int LDS_BYTES = RING * TILE_BYTES + HIST_BYTES + 16;
     static_assert(PIECES * 64 == SLOTS, "whole DMA pieces");
@@ -232,49 +223,42 @@ __device__ __forceinline__ void radix_prefix(Each&& each, int k, int limit, uint
     }
 }
 
-// In-scan compaction of one query's buffer (halves of n0 / n1 entries, k <=
-// n0 + n1), streamed from memory so that the scan keeps its registers: each
-// half keeps, in place and in order, its entries in the radix bucket holding
-// the k best (<= limit entries in all). thr = the new filter threshold:
+// In-scan compaction of one query's region (n entries, k <= n), streamed from
+// memory so that the scan keeps its registers: the region keeps, in place and
+// in order, its entries in the radix bucket holding the k best (<= limit
+// entries). thr = the new filter threshold:
 // the bucket's score floor (v >= thr), or, when the bucket had to be resolved
 // down into the ids (massive exact ties), strictly above the k-th score — items
 // arrive in increasing id order, so an equal later score loses.
-__device__ __forceinline__ void compact_stream(Cand* __restrict__ buf, int& n0, int& n1, int k, int limit,
-                                               uint32_t* hist, float& thr) {
+__device__ __forceinline__ void compact_stream(Cand* __restrict__ buf, int& n, int k, int limit, uint32_t* hist,
+                                               float& thr) {
     const int lane = threadIdx.x & 63;
     __threadfence_block();
-    const int a0 = n0, a1 = n1;
+    const int n_in = n;
     auto each = [&](auto&& fn) {
-        for (int i = lane; i < a0; i += 64) fn(ckey(buf[i]));
-        for (int i = lane; i < a1; i += 64) fn(ckey(buf[kHalf + i]));
+        for (int i = lane; i < n_in; i += 64) fn(ckey(buf[i]));
     };
     uint64_t prefix = 0;
-    int shift = 64, kept = a0 + a1;
+    int shift = 64, kept = n_in;
     radix_prefix(each, k, limit, hist, prefix, shift, kept);
     const uint64_t pmask = prefix_mask(shift);
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        Cand* p = buf + h * kHalf;
-        const int n = h ? a1 : a0;
-        int m = 0;
-        for (int i0 = 0; i0 < n; i0 += 64) {
-            const int i = i0 + lane;
-            Cand c{-INFINITY, kEmptyId};
-            bool take = false;
-            if (i < n) {
-                c = p[i];
-                take = (ckey(c) & pmask) >= prefix;
-            }
-            const uint64_t bm = __ballot(take);
-            const int pos = m + static_cast<int>(__builtin_amdgcn_mbcnt_hi(
-                                    static_cast<uint32_t>(bm >> 32),
-                                    __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(bm), 0u)));
-            if (take) p[pos] = c;  // pos <= i: every lane read its entry before any lane writes
-            m += __popcll(bm);
+    int m = 0;
+    for (int i0 = 0; i0 < n_in; i0 += 64) {
+        const int i = i0 + lane;
+        Cand c{-INFINITY, kEmptyId};
+        bool take = false;
+        if (i < n_in) {
+            c = buf[i];
+            take = (ckey(c) & pmask) >= prefix;
         }
-        if (h) n1 = m;
-        else n0 = m;
+        const uint64_t bm = __ballot(take);
+        const int pos = m + static_cast<int>(__builtin_amdgcn_mbcnt_hi(
+                                static_cast<uint32_t>(bm >> 32),
+                                __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(bm), 0u)));
+        if (take) buf[pos] = c;  // pos <= i: every lane read its entry before any lane writes
+        m += __popcll(bm);
     }
+    n = m;
     const float floor = v2::okey_inv(static_cast<uint32_t>(prefix >> 32));
     if (shift >= 32) thr = (static_cast<uint32_t>(prefix >> 32) <= 0x007FFFFFu) ? -FLT_MAX : floor;
     else thr = nextafterf(floor, INFINITY);
@@ -380,7 +364,7 @@ __global__ __launch_bounds__(512) void flatip_topk_v4_scan(Args a, int splits, i
     float thr[QS];
 #pragma unroll
     for (int j = 0; j < QS; ++j) {
-        woff0[j] = static_cast<uint32_t>(((j * 32 + col) * kCap + (kShared ? 0 : half * kHalf)) * sizeof(Cand));
+        woff0[j] = static_cast<uint32_t>((j * 32 + col) * kCap * sizeof(Cand));
         woff[j] = woff0[j];
         thr[j] = qok[j] ? -FLT_MAX : INFINITY;
     }
@@ -393,9 +377,8 @@ __global__ __launch_bounds__(512) void flatip_topk_v4_scan(Args a, int splits, i
         for (int j = 0; j < QS; ++j) thr[j] = qok[j] ? fmaxf(a.thr_in[qw + j * 32 + col], -FLT_MAX) : INFINITY;
     }
     // ---- the append budget of a candidate region ----
-    // A region (shared layout: the query's kCap entries, both lane halves
-    // appending; per-half layout: one half's kHalf entries) takes at most kSub
-    // appends per 32-row sub-tile of its query set: 16 rows per lane half.
+    // A region (the query's kCap entries, both lane halves appending) takes at
+    // most kSub appends per 32-row sub-tile of its query set: 16 rows per lane half.
     // maybe_compact() leaves a region at <= kRoom entries (a compaction keeps at
     // most kLimit = kRoom), so the region must hold kRoom plus everything
     // appended before the next check runs, or, after the last check, before the
@@ -420,19 +403,18 @@ __global__ __launch_bounds__(512) void flatip_topk_v4_scan(Args a, int splits, i
     // stage existed the tail was NSUB + 1 (RING 4) or NSUB + 2 (RING 3)
     // sub-tiles and a region at kRoom ran up to 64 entries into its neighbour.
     // What the static_assert below binds is kRoom to kBetween as written here:
-    // it fires when kRoom (or NSUB, kCap, the layout) is changed without the
+    // it fires when kRoom (or NSUB, RING, kCap) is changed without the
     // other. It cannot see WHERE the checks sit: a moved or dropped check is
     // covered only by this table and by count_model in tests/_ordered_corpora.py
     // (tests/test_ordered_corpora_cpu.py), which mirror main_pass and must be
     // changed with it.
-    constexpr int kSub = kShared ? 32 : 16;    // appends per region and sub-tile, at most
-    constexpr int kRegion = kShared ? kCap : kHalf;
+    constexpr int kSub = 32;  // appends per region and sub-tile, at most
     constexpr int kTailSubs = C::RING == 4 ? 1 : 2;  // sub-tiles of the late set after the last check
     constexpr int kBetween = C::NSUB > kTailSubs ? C::NSUB : kTailSubs;
     constexpr int kHead = C::NSUB * 16;  // appends per half between two compaction checks, at most
-    // shared region: both halves append up to kHead each between checks
-    constexpr int kRoom = kShared ? kCap - 2 * kHead : kHalf - kHead;
-    static_assert(kRoom + kBetween * kSub <= kRegion,
+    // both halves append up to kHead each between checks
+    constexpr int kRoom = kCap - 2 * kHead;
+    static_assert(kRoom + kBetween * kSub <= kCap,
                   "v4: a region at kRoom overflows before the next compaction check (or the end of the scan)");
     static_assert(kRoom >= kMaxK, "v4: a compaction must be able to keep the k best");
     constexpr uint32_t kLimBytes = static_cast<uint32_t>(kRoom * sizeof(Cand));
@@ -526,9 +508,6 @@ __global__ __launch_bounds__(512) void flatip_topk_v4_scan(Args a, int splits, i
         }
         return pm;
     };
-#ifdef RT_TOPK_V4_STREAMTEST
-    uint32_t scur = 0u;
-#endif
     auto store_loop = [&](int j, uint32_t pm, const f32x16& acc, int64_t sub0) {
         const uint32_t sub_lane = static_cast<uint32_t>(sub0) + static_cast<uint32_t>(4 * half);
         uint32_t wo = woff[j];
@@ -538,17 +517,8 @@ __global__ __launch_bounds__(512) void flatip_topk_v4_scan(Args a, int splits, i
             issued += 1;  // exactly one store instruction (dwordx2) for the wave
             // shared region: the half-1 lane writes behind its half-0 partner
             // when both store this round; both advance by the pair's stores
-            uint32_t other = 0u, slot = wo;
-            if constexpr (kShared) {
-                other = static_cast<uint32_t>((sb >> (lane ^ 32)) & 1ull);
-                slot = wo + (half ? other * static_cast<uint32_t>(sizeof(Cand)) : 0u);
-            }
-#ifdef RT_TOPK_V4_STREAMTEST  // timing probe only: wave-contiguous appends (the finish reads garbage)
-            slot = ((scur + __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(sb >> 32),
-                                                      __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(sb), 0u))) &
-                    (64u * kCap - 1u)) * static_cast<uint32_t>(sizeof(Cand));
-            scur += static_cast<uint32_t>(__popcll(sb));
-#endif
+            const uint32_t other = static_cast<uint32_t>((sb >> (lane ^ 32)) & 1ull);
+            const uint32_t slot = wo + (half ? other * static_cast<uint32_t>(sizeof(Cand)) : 0u);
             if (pm) {
                 // the lowest passing row as an isolated bit, tested against
                 // constant masks; the score is picked by explicit v_cndmask
@@ -571,10 +541,8 @@ __global__ __launch_bounds__(512) void flatip_topk_v4_scan(Args a, int splits, i
                 // a compiler-visible SADDR store (hipcc counts it and pads its hazards)
                 *reinterpret_cast<__attribute__((address_space(1))) uint64_t*>(wbytes + slot) =
                     (static_cast<uint64_t>(id) << 32) | __float_as_uint(s);
-                if constexpr (!kShared) wo += 8;
             }
-            if constexpr (kShared)
-                wo += static_cast<uint32_t>(sizeof(Cand)) * (((sb >> lane) & 1ull ? 1u : 0u) + other);
+            wo += static_cast<uint32_t>(sizeof(Cand)) * (((sb >> lane) & 1ull ? 1u : 0u) + other);
         }
         woff[j] = wo;
     };
@@ -601,11 +569,11 @@ __global__ __launch_bounds__(512) void flatip_topk_v4_scan(Args a, int splits, i
                 const int c = __builtin_ctz(need);
                 need &= need - 1;
                 const int cnt = static_cast<int>((woff[j] - woff0[j]) / sizeof(Cand));
-                int n0 = __shfl(cnt, c, 64), n1 = kShared ? 0 : __shfl(cnt, c + 32, 64);
+                int n0 = __shfl(cnt, c, 64);
                 float nt;
-                compact_stream(cbase + static_cast<int64_t>(j * 32 + c) * kCap, n0, n1, k, kLimit, whist, nt);
+                compact_stream(cbase + static_cast<int64_t>(j * 32 + c) * kCap, n0, k, kLimit, whist, nt);
                 if (col == c) {
-                    woff[j] = woff0[j] + static_cast<uint32_t>(((half && !kShared) ? n1 : n0) * sizeof(Cand));
+                    woff[j] = woff0[j] + static_cast<uint32_t>(n0 * sizeof(Cand));
                     thr[j] = fmaxf(thr[j], nt);
                 }
             }
@@ -906,8 +874,7 @@ __global__ __launch_bounds__(512) void flatip_topk_v4_scan(Args a, int splits, i
 #pragma unroll
         for (int j = 0; j < QS; ++j) {
             const int cnt = static_cast<int>((woff[j] - woff0[j]) / sizeof(Cand));
-            const int tot = kShared ? cnt : cnt + __shfl_xor(cnt, 32, 64);
-            const bool fail = qok[j] && tot < k;
+            const bool fail = qok[j] && cnt < k;
             any |= fail;
             if (fail) {
                 thr[j] = -FLT_MAX;  // start over for this query: empty buffer, v2 selection
@@ -925,8 +892,8 @@ __global__ __launch_bounds__(512) void flatip_topk_v4_scan(Args a, int splits, i
 #pragma unroll
     for (int j = 0; j < QS; ++j) {
         const int cnt = static_cast<int>((woff[j] - woff0[j]) / sizeof(Cand));
-        // shared region: the whole count in the half-0 segment, the half-1 segment empty
-        meta[((static_cast<int64_t>(split) * q_pad) + qw + j * 32 + col) * 2 + half] = (kShared && half) ? 0 : cnt;
+        // the whole count in the half-0 segment, the half-1 segment empty
+        meta[((static_cast<int64_t>(split) * q_pad) + qw + j * 32 + col) * 2 + half] = half ? 0 : cnt;
     }
 #ifdef RT_TOPK_PROBE_TIMING
     {  // [total, DMA wait, barrier, main sub-tiles, sample pass, compaction checks]
@@ -954,11 +921,8 @@ __device__ __noinline__ void finish_sort(const Cand* __restrict__ buf, int m, in
         s[j] = c.s;
         id[j] = c.i;
     }
-#ifndef RT_SORT2_GENERIC  // A/B: the loop form
     if constexpr (E == 2) wave_sort_regs2(s, id);
-    else
-#endif
-        wave_sort_regs<E>(s, id);
+    else wave_sort_regs<E>(s, id);
 #pragma unroll
     for (int j = 0; j < E; ++j) {
         const int r = lane * E + j;
@@ -1183,22 +1147,30 @@ inline int launch_threshold(const float* lists, int n_lists, int64_t list_stride
     return check_launch("flatip_topk_v4_threshold");
 }
 
-template <typename T, int S, int QS>
-int launch_scan(const Args& a, int q_tiles, int splits, int64_t items_per_split, int stride, int rank, int* meta,
-                int mode, int* fail, hipStream_t st) {
-    dim3 grid(static_cast<unsigned>(q_tiles * splits));
+// ---- host launchers ----
+// They read the grid (q_tiles, splits, items_per_split) and the sample
+// (stride, rank) from the Plan, and the workspace regions (meta, fail,
+// v4_lists, v4_thr) from Args. A caller that picks its own stride, rank or
+// mode (the shard entry points) sets them on a copy of the plan.
+
+// queries a v4 plan's grid covers: the row count of every per-query workspace region
+inline int64_t q_pad(const Plan& p) { return static_cast<int64_t>(p.q_tiles) * Geo<kQS>::QT; }
+
+template <typename T, int S>
+int launch_scan(const Args& a, const Plan& p, int mode, hipStream_t st) {
+    dim3 grid(static_cast<unsigned>(p.q_tiles * p.splits));
     if (a.excl)
-        hipLaunchKernelGGL((flatip_topk_v4_scan<T, S, QS, true>), grid, dim3(64 * kWavesB), 0, st, a, splits,
-                           items_per_split, stride, rank, meta, mode, fail);
+        hipLaunchKernelGGL((flatip_topk_v4_scan<T, S, kQS, true>), grid, dim3(64 * kWavesB), 0, st, a, p.splits,
+                           p.items_per_split, p.stride, p.rank, a.meta, mode, a.fail);
     else
-        hipLaunchKernelGGL((flatip_topk_v4_scan<T, S, QS, false>), grid, dim3(64 * kWavesB), 0, st, a, splits,
-                           items_per_split, stride, rank, meta, mode, fail);
+        hipLaunchKernelGGL((flatip_topk_v4_scan<T, S, kQS, false>), grid, dim3(64 * kWavesB), 0, st, a, p.splits,
+                           p.items_per_split, p.stride, p.rank, a.meta, mode, a.fail);
     return check_launch("flatip_topk_v4_scan");
 }
 
-inline int launch_finish(const Args& a, int splits, int64_t q_pad, int mode, int* fail, hipStream_t st) {
+inline int launch_finish(const Args& a, const Plan& p, int mode, hipStream_t st) {
     hipLaunchKernelGGL(flatip_topk_v4_finish<4>, dim3(static_cast<unsigned>((a.nq + 3) / 4)), dim3(256), 0, st,
-                       a.cand, a.meta, splits, q_pad, a.nq, a.k, a.out_s, a.out_i, a.id_offset, mode, fail);
+                       a.cand, a.meta, p.splits, q_pad(p), a.nq, a.k, a.out_s, a.out_i, a.id_offset, mode, a.fail);
     return check_launch("flatip_topk_v4_finish");
 }
 
@@ -1207,46 +1179,31 @@ inline int launch_finish(const Args& a, int splits, int64_t q_pad, int mode, int
 // the main scan against it (mode 4), the finish with the union check (mode
 // 1), then the rescue pair (mode 2) — every block samples its own split only
 // (the mode-1 scan has every block sample the whole corpus)
-template <typename T, int S, int QS>
-int launch_presampled(const Args& a, int q_tiles, int splits, int64_t items_per_split, int stride, int rank,
-                      float* lists, float* thr, int* fail, hipStream_t st) {
-    const int64_t q_pad = static_cast<int64_t>(q_tiles) * Geo<QS>::QT;
+template <typename T, int S>
+int launch_presampled(const Args& a, const Plan& p, hipStream_t st) {
     Args b = a;
-    b.lists_out = lists;
-    int rc = launch_scan<T, S, QS>(b, q_tiles, splits, items_per_split, stride, rank, a.meta, 3, nullptr, st);
+    b.lists_out = a.v4_lists;
+    int rc = launch_scan<T, S>(b, p, 3, st);
     if (rc) return rc;
-    if ((rc = launch_threshold(lists, splits, q_pad * kSampleList, a.nq, rank, thr, nullptr, st))) return rc;
-    b.lists_out = nullptr;
-    b.thr_in = thr;
-    if ((rc = launch_scan<T, S, QS>(b, q_tiles, splits, items_per_split, stride, rank, a.meta, 4, nullptr, st)))
+    if ((rc = launch_threshold(a.v4_lists, p.splits, q_pad(p) * kSampleList, a.nq, p.rank, a.v4_thr, nullptr, st)))
         return rc;
-    if ((rc = launch_finish(a, splits, q_pad, 1, fail, st))) return rc;
-    if ((rc = launch_scan<T, S, QS>(a, q_tiles, splits, items_per_split, stride, rank, a.meta, 2, fail, st))) return rc;
-    return launch_finish(a, splits, q_pad, 2, fail, st);
+    b.lists_out = nullptr;
+    b.thr_in = a.v4_thr;
+    if ((rc = launch_scan<T, S>(b, p, 4, st))) return rc;
+    if ((rc = launch_finish(a, p, 1, st))) return rc;
+    if ((rc = launch_scan<T, S>(a, p, 2, st))) return rc;
+    return launch_finish(a, p, 2, st);
 }
 
-template <typename T, int S, int QS>
-int launch_S(const Args& a, int q_tiles, int splits, int64_t items_per_split, int stride, int rank, int* meta,
-             int* fail, hipStream_t st) {
-    // joint threshold (several splits): scan + finish, then the rescue pair,
-    // whose blocks exit at once unless the finish flagged one of their queries
-    const int passes = fail ? 2 : 1;
-    const int64_t q_pad = static_cast<int64_t>(q_tiles) * Geo<QS>::QT;
-    for (int pass = 0; pass < passes; ++pass) {
-        const int mode = fail ? 1 + pass : 0;
-        dim3 grid(static_cast<unsigned>(q_tiles * splits));
-        if (a.excl)
-            hipLaunchKernelGGL((flatip_topk_v4_scan<T, S, QS, true>), grid, dim3(64 * kWavesB), 0, st, a, splits,
-                               items_per_split, stride, rank, meta, mode, fail);
-        else
-            hipLaunchKernelGGL((flatip_topk_v4_scan<T, S, QS, false>), grid, dim3(64 * kWavesB), 0, st, a, splits,
-                               items_per_split, stride, rank, meta, mode, fail);
-        int rc = check_launch("flatip_topk_v4_scan");
+// one split, or the per-split form (mode 0): scan + finish. Joint threshold
+// without the presample (mode 1): scan + finish, then the rescue pair (mode
+// 2), whose blocks exit at once unless the finish flagged one of their queries
+template <typename T, int S>
+int launch_S(const Args& a, const Plan& p, hipStream_t st) {
+    for (int mode = p.v4_joint ? 1 : 0; mode <= (p.v4_joint ? 2 : 0); ++mode) {
+        int rc = launch_scan<T, S>(a, p, mode, st);
         if (rc) return rc;
-        hipLaunchKernelGGL(flatip_topk_v4_finish<4>, dim3(static_cast<unsigned>((a.nq + 3) / 4)), dim3(256), 0, st,
-                           a.cand, meta, splits, q_pad, a.nq, a.k, a.out_s, a.out_i, a.id_offset, mode, fail);
-        rc = check_launch("flatip_topk_v4_finish");
-        if (rc) return rc;
+        if ((rc = launch_finish(a, p, mode, st))) return rc;
     }
     return 0;
 }
@@ -1254,3 +1211,4 @@ int launch_S(const Args& a, int q_tiles, int splits, int64_t items_per_split, in
 }  // namespace v4
 }  // namespace topk
 }  // namespace rt
+

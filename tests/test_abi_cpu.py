@@ -129,7 +129,7 @@ def test_sample_rank_matches_binomial_tail(native):
     """rt_topk_sample_rank (host-only) is the least rank r <= 32 with
     P(Bin(k, f) >= r) <= 1e-6 for f = sampled / stages (r > k: safe; 0 when
     none fits) — the failure bound of the v4 sampled threshold
-    (topk_api.hip::safe_rank), checked against scipy's binomial tail."""
+    (topk_sample_plan.h::safe_rank), checked against scipy's binomial tail."""
     from scipy.stats import binom
     L = native.lib()
     for k in (1, 10, 33, 64, 100, 128):
@@ -156,3 +156,52 @@ def test_shard_plan_is_cheap_on_the_host(native):
     for _ in range(200):
         L.rt_flatip_topk_shard_plan(*args)
     assert (time.perf_counter() - t0) / 200 < 1e-3  # loose: CPU-contended runners
+
+
+# (tuning, dtype, d, k, nx, nq): one shape or more per plan kind of make_plan
+_F32, _F16, _BF16 = 0, 1, 2
+_PLAN_KINDS = [
+    (0, _F32, 64, 10, 1000, 241), (0, _F32, 64, 10, 3456, 6040),          # dense GEMM + select
+    (8, _F32, 64, 10, 3456, 6040),                                        # register lists, several splits, k-th keys
+    (0, _F32, 128, 32, 100000, 1024),                                     # register lists, K = 32
+    (0, _F32, 256, 100, 50000, 1024), (0, _F32, 128, 100, 50000, 1024),   # v1, v2
+    (0, _F16, 96, 10, 125000, 8192), (0, _BF16, 128, 32, 65536, 1),       # v3
+    (0, _F16, 128, 100, 125000, 65536), (0, _BF16, 64, 100, 1000000, 8192),   # v4 presampled
+    (4, _F16, 128, 100, 125000, 65536), (4, _BF16, 64, 100, 1000000, 8192),   # v4 per split
+    (16, _F16, 128, 100, 125000, 65536), (16, _BF16, 64, 100, 1000000, 8192),  # v4 joint, no presample
+    (2, _F16, 128, 100, 1249, 241),                                       # v4 forced, one split
+    (0, _F16, 128, 100, 125000, 70000),                                   # two query chunks
+    (0, _F16, 256, 100, 65536, 8192), (0, _F32, 128, 512, 10000, 100),    # d = 256 16-bit; k = 512
+    (0, _F32, 64, 10, 0, 241), (0, _F16, 128, 100, 0, 8192),              # empty corpus
+]
+
+
+def test_size_query_and_size_check_are_one_computation(native):
+    """W = rt_flatip_topk_workspace_bytes is the layout's total + 256 bytes of
+    slack, so W - 257 is one byte short and rt_flatip_topk must refuse it — on
+    the host, before any GPU call (the pointers are dummies). The shard pair
+    likewise."""
+    L = native.lib()
+    p16 = ctypes.c_void_p(16)
+    try:
+        for tuning, dtype, d, k, nx, nq in _PLAN_KINDS:
+            assert L.rt_flatip_topk_tuning(tuning, 0, -1) == 0
+            W = L.rt_flatip_topk_workspace_bytes(nq, nx, d, dtype, k)
+            if W == 256:  # no workspace at all (register lists over an empty corpus): nothing can be short
+                continue
+            assert W > 257, (tuning, dtype, d, k, nx, nq, W)
+            rc = L.rt_flatip_topk(p16, nq, p16, nx, d, dtype, k, None, 0, 0, p16, p16, p16, W - 257, None)
+            assert rc == -3, (tuning, dtype, d, k, nx, nq, W, rc)
+        shard = 0
+        for tuning, dtype, d, k, nx, nq in _PLAN_KINDS:
+            assert L.rt_flatip_topk_tuning(tuning, 0, -1) == 0
+            W = L.rt_flatip_topk_shard_workspace_bytes(nq, nx, d, dtype, k)
+            if W == 0:  # no v4 plan in one query chunk: the shard calls do not apply
+                continue
+            assert W > 257
+            rc = L.rt_flatip_topk_shard_search(p16, nq, p16, nx, d, dtype, k, p16, 0, p16, p16, p16, W - 257, None)
+            assert rc == -3, (tuning, dtype, d, k, nx, nq, W, rc)
+            shard += 1
+        assert shard >= 7  # every v4 case above in one chunk
+    finally:
+        assert L.rt_flatip_topk_tuning(0, 0, -1) == 0

@@ -11,12 +11,11 @@ at the wrong moment. What these cases are aimed at:
     holds the count model that shows it on the mode-4 grid below);
   * csrc/topk_v3.h: scores ascending inside one 16-bit key bucket, where a
     compaction keeps everything it is allowed to (`bucket_ascending`).
-Variants of the v4 scan that exist only as compile-time macros
-(RT_TOPK_V4_RING3: the 3-stage ring at d = 128; RT_TOPK_V4_PER_HALF: a region
-per lane half; RT_TOPK_V4_QS) cannot be reached from rt_flatip_topk_tuning;
-their budget is covered by the static_assert next to kRoom. What the tuning
-can select — forced v4, per-split thresholds (+4), no presample (+16),
-stride / rank — is selected below."""
+The one compile-time variant of the v4 scan, RT_TOPK_V4_QS (query sets per
+wave), cannot be reached from rt_flatip_topk_tuning; its budget is covered by
+the static_assert next to kRoom. What the tuning can select — forced v4,
+per-split thresholds (+4), no presample (+16), stride / rank — is selected
+below."""
 import functools
 
 import numpy as np
