@@ -421,6 +421,22 @@ int rt_linear_bwd_dw_f32(const rt_linear_bwd_args* args, void* stream);
 int rt_linear_fwd_f32_multi(const rt_linear_fwd_args* args, int n_args, void* stream);
 int rt_linear_bwd_dz_f32_multi(const rt_linear_bwd_args* args, int n_args, void* stream);
 int rt_linear_bwd_dw_f32_multi(const rt_linear_bwd_args* args, int n_args, void* stream);
+/* The dW (+ dbias, + the fused dz of fuse_dz sets) of up to 6 argument sets —
+ * every Linear of a tower pair — in ONE launch, enqueued after the dz launches
+ * of all of them (dW of a layer needs only that layer's dz and staged input,
+ * and nothing needs dW). Sets are validated as by rt_linear_bwd_dw_f32_multi.
+ * fuse_dz is decided PER SET here: clear it on the sets of a pair whose dz
+ * launch ran (rt_linear_bwd_dz_fused == 0). A set with dw_part stores its row
+ * splits' tile sums ([splits][n][k], splits from rt_linear_bwd_dw_joint_splits)
+ * for rt_grad_sqnorm_fold; a set without adds them with fp32 atomics. fold_*
+ * with fold_in 1 is refused (no tower launch follows). A set the joint kernel
+ * has no instantiation for (a recomputing prologue, a 64x64-tile set with
+ * unaligned operands or a gather, a k <= 32 set whose dz is not fused) runs as
+ * a launch of its own after the joint one, same results. */
+int rt_linear_bwd_dw_f32_joint(const rt_linear_bwd_args* args, int n_args, void* stream);
+/* Row splits per argument set that rt_linear_bwd_dw_f32_joint(args, n_args)
+ * will use. Host-only, no GPU work. */
+int rt_linear_bwd_dw_joint_splits(const rt_linear_bwd_args* args, int n_args, int64_t* splits);
 
 /* ------------------------------------------------------------------------
  * Losses (fp32 scores, fp32 accumulation; bf16/f16 inputs widened on load).
@@ -480,9 +496,28 @@ int rt_similarity_f32(const float* u, const float* v, int64_t b, int d, float in
  *   from `step` / `lr`. The grads are CONSUMED: every element is zeroed after
  *   use, and zero_buf[0, zero_words) (fp64, may be NULL) is zeroed too — the
  *   next step's accumulators start at zero without memset launches.
+ * rt_grad_sqnorm_fold: rt_grad_sqnorm that first folds row-split partial sums
+ *   (rt_linear_bwd_args.dw_part of rt_linear_bwd_dw_f32_joint) into the tensors
+ *   the n_folds <= RT_GRAD_FOLD_MAX descriptors name (host array, copied at the
+ *   call): element e of such a tensor becomes
+ *     g[e] + (((p_0[e] + p_1[e]) + p_2[e]) + … + p_{splits-1}[e]),  p_s = part + s·words,
+ *   fp32, in ascending split order; it is written back to grads and that value
+ *   is squared into the tensor's sum. Tensors without a descriptor, and the
+ *   counters, behave exactly as in rt_grad_sqnorm.
  * ------------------------------------------------------------------------ */
+#define RT_GRAD_FOLD_MAX 8
+typedef struct {
+    const float* part;   /* [splits][words] fp32, 16-B aligned */
+    int64_t dst_off;     /* the tensor's first element in grads (== offsets[tensor]; multiple of 4) */
+    int64_t words;       /* elements of the tensor (multiple of 4) */
+    int splits;          /* >= 1 */
+    int tensor;          /* index into offsets / sumsq_out; at most one descriptor per tensor */
+} rt_grad_fold;
 int rt_grad_sqnorm(const float* grads, const int64_t* offsets, int n_tensors, double* sumsq_out,
                    int32_t* step_counter, int64_t* seed_counter, void* stream);
+int rt_grad_sqnorm_fold(float* grads, const int64_t* offsets, int n_tensors, double* sumsq_out,
+                        int32_t* step_counter, int64_t* seed_counter, const rt_grad_fold* folds,
+                        int n_folds, void* stream);
 int rt_clip_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq,
                       int64_t n, const double* sumsq, int n_tensors, float max_norm, float lr,
                       const float* lr_dev, float beta1, float beta2, float eps, float weight_decay,

@@ -1330,8 +1330,24 @@ __device__ __forceinline__ float pro_col(const Pro& p, float slope, int64_t r, i
 // from g and z with the per-column BN-backward coefficients, exactly as the dz
 // launch's phase A would; dgamma/dbeta (block 0) and dbias (row sums of the
 // computed dz) are added here too.
+//
+// LDS of one tile body, carved from the launch's one dynamic buffer (every
+// part a multiple of 16 B; no static LDS, so the base stays 16-B aligned):
+//   dz chunks [2][DW_R][LDN] | A chunks [2][DW_R][LDK] | BN affine [2][2][BK]
+//   (PRO != 0) | dz coefficients [2][5][BN] (DZF) | ticket flag | gather ids
+//   [rows per split] (only launches with a gathering set request them).
+// <64,64,0,·,false>: 49,168 B; <128,32,0,·,true>: 54,288 B + 4 B per staged id.
+__host__ __device__ constexpr int dw_lds_floats(int BN, int BK, int PRO, bool DZF) {
+    return 2 * DW_R * dw_ld(BN) + 2 * DW_R * dw_ld(BK) + (PRO != 0 ? 4 * BK : 0) + (DZF ? 10 * BN : 0) + 4;
+}
+
+// One BN x BK tile of one argument set over one row split. `bid` is the block's
+// index INSIDE its set's block range and the split count comes from m and
+// rows_per_split, so "block 0" work, the dbias ticket and padding splits are
+// the same whether the set has a launch to itself or shares one.
 template <int BN, int BK, int PRO, bool VEC, bool DZF>  // VEC: n, k, ld_src multiples of 4, 16-B aligned rows
-__global__ __launch_bounds__(DW_NT) void linear_bwd_dw_kernel(BwdLaunch L) {
+__device__ __forceinline__ void dw_tile(const rt_linear_bwd_args& a_set, const int64_t rows_per_split,
+                                        const unsigned tn, const unsigned tk, const unsigned bid, float* smem) {
     constexpr int NTN = BN / 32, WK = 4 / NTN, T = (BK / 32) / WK;
     static_assert(NTN * 32 == BN && 4 % NTN == 0 && T >= 1 && T * WK * 32 == BK, "dW tile");
     constexpr int LDN = dw_ld(BN), LDK = dw_ld(BK);
@@ -1340,23 +1356,15 @@ __global__ __launch_bounds__(DW_NT) void linear_bwd_dw_kernel(BwdLaunch L) {
     static_assert(DW_NT % VN == 0 && DW_NT % VK == 0, "fixed staging columns per thread");
     static_assert(2 * DW_R * LDN >= 4 * T * 16 * 64, "row-group reduction fits in the dz buffers");
     static_assert(2 * DW_R * LDK >= (DW_NT / 64) * VN * 4, "dbias partials fit in the A buffers");
-    __shared__ __attribute__((aligned(16))) float Ld[2][DW_R * LDN];
-    __shared__ __attribute__((aligned(16))) float La[2][DW_R * LDK];
-    // gather ids staged for the first Linear only (PRO 0): the other instances
-    // stay at <= 53 KB of LDS, 3 blocks per CU (the C2 layer-2 dW launch's ~750
-    // blocks then run as one wave of blocks instead of two)
-    __shared__ int srow[PRO == 0 ? DW_MAXR : 1];
-    __shared__ __attribute__((aligned(16))) float aff_s[2][2][BK];  // [segment][scale, shift][tile column]
-    __shared__ __attribute__((aligned(16))) float dzc_s[DZF ? 2 : 1][5][DZF ? BN : 4];  // DZF: [seg][A,B,C,M,I][col]
+    float* const Ld = smem;                                         // [2][DW_R * LDN]
+    float* const La = Ld + 2 * DW_R * LDN;                          // [2][DW_R * LDK]
+    float* const aff_s = La + 2 * DW_R * LDK;                       // [segment][scale, shift][BK] (PRO != 0)
+    float* const dzc_s = aff_s + (PRO != 0 ? 4 * BK : 0);           // DZF: [seg][A,B,C,M,I][BN]
+    int* const last_s = reinterpret_cast<int*>(dzc_s + (DZF ? 10 * BN : 0));
+    int* const srow = last_s + 4;                                   // gather ids of this split's rows
+    static_assert(dw_lds_floats(BN, BK, PRO, DZF) * sizeof(float) % 16 == 0, "16-B carve offsets");
 
-#ifdef RT_FOLD_FIRST
-    fold_side(L, 1);
-#endif
-    const bool g1 = blockIdx.x >= L.split;
-    const rt_linear_bwd_args a = g1 ? L.a1 : L.a0;  // by value: fields loaded once
-    const int64_t rows_per_split = g1 ? L.rps1 : L.rps0;
-    const unsigned bid = blockIdx.x - (g1 ? L.split : 0u);
-    const unsigned tn = g1 ? L.tn1 : L.tn0, tk = g1 ? L.tk1 : L.tk0;
+    const rt_linear_bwd_args a = a_set;  // by value: fields loaded once
     const unsigned bx = bid % tn, by = (bid / tn) % tk, bz = bid / (tn * tk);
     const int n = a.n, k = a.k;
     const int64_t m = a.m;
@@ -1365,12 +1373,7 @@ __global__ __launch_bounds__(DW_NT) void linear_bwd_dw_kernel(BwdLaunch L) {
     const int n0 = static_cast<int>(bx) * BN, k0 = static_cast<int>(by) * BK;
     const int64_t r_begin = static_cast<int64_t>(bz) * rows_per_split;
     const int64_t r_end = (r_begin + rows_per_split) < m ? (r_begin + rows_per_split) : m;
-    if (r_begin >= m) {  // a padding split (block-uniform, before any barrier)
-#ifndef RT_FOLD_FIRST
-        fold_side(L, 1);
-#endif
-        return;
-    }
+    if (r_begin >= m) return;  // a padding split (block-uniform, before any barrier)
     RT_PP_DECL
     // A rows: the forward's staged copy (a_in, read as is: PRO 0) or recomputed from src
     const bool gather = PRO == 0 && a.ids != nullptr && !a.a_in;  // (the host refuses ids with a transformed input)
@@ -1384,7 +1387,7 @@ __global__ __launch_bounds__(DW_NT) void linear_bwd_dw_kernel(BwdLaunch L) {
     // BN affine of the previous block for this thread's 4 A columns, per row segment
     float4 sc0 = make_float4(1.f, 1.f, 1.f, 1.f), sc1 = sc0;
     float4 sh0 = make_float4(0.f, 0.f, 0.f, 0.f), sh1 = sh0;
-    if ((a.prev_mode == 1 || a.prev_mode == 2) && !a.a_in) {
+    if (PRO != 0 && (a.prev_mode == 1 || a.prev_mode == 2) && !a.a_in) {
         // one load per (segment, column) for the whole block, through LDS: with
         // every thread loading its own 4 columns x 2 segments x 4 arrays, the
         // 512 threads x ~750 blocks of a C2 launch hammered the same few L2
@@ -1394,14 +1397,14 @@ __global__ __launch_bounds__(DW_NT) void linear_bwd_dw_kernel(BwdLaunch L) {
             const int so = two ? sg * k : 0;
             float scv = 1.f, shv = 0.f;
             if (cc < k) bn_affine(a.prev_gamma[cc], a.prev_beta[cc], a.prev_mean[so + cc], a.prev_invstd[so + cc], scv, shv);
-            aff_s[sg][0][cl] = scv;
-            aff_s[sg][1][cl] = shv;
+            aff_s[(sg * 2 + 0) * BK + cl] = scv;
+            aff_s[(sg * 2 + 1) * BK + cl] = shv;
         }
         __syncthreads();
-        sc0 = *reinterpret_cast<const float4*>(&aff_s[0][0][ck]);
-        sh0 = *reinterpret_cast<const float4*>(&aff_s[0][1][ck]);
-        sc1 = *reinterpret_cast<const float4*>(&aff_s[1][0][ck]);
-        sh1 = *reinterpret_cast<const float4*>(&aff_s[1][1][ck]);
+        sc0 = *reinterpret_cast<const float4*>(&aff_s[0 * BK + ck]);
+        sh0 = *reinterpret_cast<const float4*>(&aff_s[1 * BK + ck]);
+        sc1 = *reinterpret_cast<const float4*>(&aff_s[2 * BK + ck]);
+        sh1 = *reinterpret_cast<const float4*>(&aff_s[3 * BK + ck]);
     }
     const uint64_t pseed = a.prev_drop_seed + (a.seed_offset ? *a.seed_offset : 0ull);
     const Pro pro{a.prev_mode, a.prev_act, a.prev_drop_p, a.prev_drop_p > 0.f ? 1.f / (1.f - a.prev_drop_p) : 1.f,
@@ -1428,8 +1431,9 @@ __global__ __launch_bounds__(DW_NT) void linear_bwd_dw_kernel(BwdLaunch L) {
                     C = static_cast<float>(gs2) * inv_m;
                 }
             }
-            dzc_s[sg][0][cl] = A; dzc_s[sg][1][cl] = Bc; dzc_s[sg][2][cl] = C;
-            dzc_s[sg][3][cl] = M; dzc_s[sg][4][cl] = I;
+            float* const dc = dzc_s + sg * 5 * BN + cl;
+            dc[0] = A; dc[BN] = Bc; dc[2 * BN] = C;
+            dc[3 * BN] = M; dc[4 * BN] = I;
         }
         if (bid == 0 && (a.grad_mode == 1 || a.grad_mode == 2) && a.dgamma) {
             // dgamma/dbeta of each BN batch (segment), as the dz launch's block 0
@@ -1536,8 +1540,9 @@ __global__ __launch_bounds__(DW_NT) void linear_bwd_dw_kernel(BwdLaunch L) {
                     float4 d;
                     auto one = [&](float g, float z, int i) {
                         const int cl = cn + i;
-                        const float A = dzc_s[sg][0][cl], Bc = dzc_s[sg][1][cl], C = dzc_s[sg][2][cl];
-                        const float M = dzc_s[sg][3][cl], I = dzc_s[sg][4][cl];
+                        const float* const dc = dzc_s + sg * 5 * BN + cl;
+                        const float A = dc[0], Bc = dc[BN], C = dc[2 * BN];
+                        const float M = dc[3 * BN], I = dc[4 * BN];
                         const float xh = (act_pwl(dsl, z) - M) * I;
                         return (ok && gn + i < n) ? A * (g - Bc - xh * C) * (z > 0.f ? 1.f : dsl) : 0.f;
                     };
@@ -1547,7 +1552,7 @@ __global__ __launch_bounds__(DW_NT) void linear_bwd_dw_kernel(BwdLaunch L) {
                     d.w = one(rd[j].w, rz[j].w, 3);
                     rd[j] = d;
                 }
-                *reinterpret_cast<float4*>(&Ld[buf][row * LDN + cn]) = rd[j];
+                *reinterpret_cast<float4*>(&Ld[buf * DW_R * LDN + row * LDN + cn]) = rd[j];
                 bsum.x += rd[j].x; bsum.y += rd[j].y; bsum.z += rd[j].z; bsum.w += rd[j].w;
             }
         }
@@ -1564,7 +1569,7 @@ __global__ __launch_bounds__(DW_NT) void linear_bwd_dw_kernel(BwdLaunch L) {
                 v.y = (ok && gk + 1 < k) ? pro_col<PRO>(pro, slope, r, gk + 1, scs.y, shs.y, ra[j].y) : 0.f;
                 v.z = (ok && gk + 2 < k) ? pro_col<PRO>(pro, slope, r, gk + 2, scs.z, shs.z, ra[j].z) : 0.f;
                 v.w = (ok && gk + 3 < k) ? pro_col<PRO>(pro, slope, r, gk + 3, scs.w, shs.w, ra[j].w) : 0.f;
-                *reinterpret_cast<float4*>(&La[buf][row * LDK + ck]) = v;
+                *reinterpret_cast<float4*>(&La[buf * DW_R * LDK + row * LDK + ck]) = v;
             }
         }
     };
@@ -1584,8 +1589,8 @@ __global__ __launch_bounds__(DW_NT) void linear_bwd_dw_kernel(BwdLaunch L) {
         const bool more = base + DW_R < r_end;  // block-uniform
         if (more) load(base + DW_R);            // in flight during the MFMAs below
         // row pairs grp, grp + DW_G, ...: lane half h reads row 2·pair + h
-        const float* dl = &Ld[buf][(2 * grp + h) * LDN + ncol];
-        const float* al = &La[buf][(2 * grp + h) * LDK + kcol0];
+        const float* dl = &Ld[buf * DW_R * LDN + (2 * grp + h) * LDN + ncol];
+        const float* al = &La[buf * DW_R * LDK + (2 * grp + h) * LDK + kcol0];
 #pragma unroll
         for (int i = 0; i < DW_R / (2 * DW_G); ++i) {
             const float av = dl[2 * DW_G * i * LDN];
@@ -1606,8 +1611,8 @@ __global__ __launch_bounds__(DW_NT) void linear_bwd_dw_kernel(BwdLaunch L) {
     // (idle) dz buffers (both groups issue atomics: 1.5 µs/step faster than
     // group 0 adding all of it); the dbias partials go through the A buffers.
     RT_PP_MARK(2)
-    float* red = &Ld[0][0];
-    float* bred = &La[0][0];  // [8 waves][VN][4]
+    float* red = Ld;
+    float* bred = La;  // [8 waves][VN][4]
     if (do_bias) {
 #pragma unroll
         for (int o = VN; o < 64; o <<= 1) {
@@ -1673,17 +1678,16 @@ __global__ __launch_bounds__(DW_NT) void linear_bwd_dw_kernel(BwdLaunch L) {
             if ((r >> 3) == grp) add_row(t, r, kk);
     }
     if (slot_bias) {  // block-uniform
-        __shared__ int last_s;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's slot atomics are performed
         __syncthreads();
         if (tid == 0) {
             ticket_release();
             unsigned long long* cnt = reinterpret_cast<unsigned long long*>(a.dbias_slots + static_cast<int64_t>(RT_STAT_SLOTS) * n);
             const unsigned long long nsplit = static_cast<unsigned long long>((m + rows_per_split - 1) / rows_per_split);
-            last_s = atomicAdd(&cnt[bx], 1ull) == nsplit - 1 ? 1 : 0;
+            *last_s = atomicAdd(&cnt[bx], 1ull) == nsplit - 1 ? 1 : 0;
         }
         __syncthreads();
-        if (last_s) {
+        if (*last_s) {
             // every split of this tile has added: fold the slots in slot order
             // (returning adds of 0 read them at the memory side, where they live)
             for (int cl = tid; cl < BN; cl += DW_NT) {
@@ -1696,10 +1700,47 @@ __global__ __launch_bounds__(DW_NT) void linear_bwd_dw_kernel(BwdLaunch L) {
             }
         }
     }
+    RT_PP_END(3)
+}
+
+extern __shared__ __attribute__((aligned(16))) float dw_smem[];
+
+// one or two argument sets of one tile / prologue family (rt_linear_bwd_dw_f32_multi)
+template <int BN, int BK, int PRO, bool VEC, bool DZF>
+__global__ __launch_bounds__(DW_NT) void linear_bwd_dw_kernel(BwdLaunch L) {
+#ifdef RT_FOLD_FIRST
+    fold_side(L, 1);
+#endif
+    const bool g1 = blockIdx.x >= L.split;
+    dw_tile<BN, BK, PRO, VEC, DZF>(g1 ? L.a1 : L.a0, g1 ? L.rps1 : L.rps0, g1 ? L.tn1 : L.tn0, g1 ? L.tk1 : L.tk0,
+                                   blockIdx.x - (g1 ? L.split : 0u), dw_smem);
 #ifndef RT_FOLD_FIRST
     fold_side(L, 1);
 #endif
-    RT_PP_END(3)
+}
+
+// Up to DWJ_MAX argument sets of BOTH tile families in one launch
+// (rt_linear_bwd_dw_f32_joint): the dW of every Linear of a tower pair after
+// the dz chain. Set s owns blocks [end[s-1], end[s]); the host orders the sets
+// longest chain first (the fused-dz first-layer sets lead, the 64x64 sets
+// take the remaining slots). Bodies: 0 = <128,32,0,VS,true> (k <= 32,
+// dz fused), 1 = <64,64,0,true,false>. All of them carve the one dynamic LDS
+// buffer, so the launch's size is the largest body's, not their sum.
+constexpr int DWJ_MAX = 6;
+struct DwJointLaunch {
+    rt_linear_bwd_args a[DWJ_MAX];
+    int64_t rps[DWJ_MAX];
+    unsigned tn[DWJ_MAX], tk[DWJ_MAX], end[DWJ_MAX];
+    unsigned char body[DWJ_MAX];
+    int nsets;
+};
+template <bool VS>  // VS: float4 staging loads in body 0 (every k <= 32 set qualifies)
+__global__ __launch_bounds__(DW_NT) void linear_bwd_dw_joint_kernel(DwJointLaunch L) {
+    int s = 0;
+    while (s + 1 < L.nsets && blockIdx.x >= L.end[s]) ++s;  // block-uniform
+    const unsigned bid = blockIdx.x - (s ? L.end[s - 1] : 0u);
+    if (L.body[s] == 0) dw_tile<128, 32, 0, VS, true>(L.a[s], L.rps[s], L.tn[s], L.tk[s], bid, dw_smem);
+    else dw_tile<64, 64, 0, true, false>(L.a[s], L.rps[s], L.tn[s], L.tk[s], bid, dw_smem);
 }
 
 }  // namespace mlp
@@ -1928,13 +1969,14 @@ extern "C" int rt_linear_bwd_dz_f32(const rt_linear_bwd_args* args, void* stream
 #ifndef RT_DW_BLOCKS_SMALLK
 #define RT_DW_BLOCKS_SMALLK 256
 #endif
-static void dw_plan(const rt_linear_bwd_args* args, int n_args, bool small_k, unsigned* tn, unsigned* tk,
-                    int64_t* splits, int64_t& rps) {
-    const int bn = small_k ? 128 : 64, bk = small_k ? 32 : 64;
 #ifndef RT_DW_CAP_SMALLK
 #define RT_DW_CAP_SMALLK 128
 #endif
-    const int64_t cap = small_k ? RT_DW_CAP_SMALLK : 64;
+// target_blocks / split_cap > 0 replace the defaults above (the joint launch's plan)
+static void dw_plan(const rt_linear_bwd_args* args, int n_args, bool small_k, unsigned* tn, unsigned* tk,
+                    int64_t* splits, int64_t& rps, int64_t target_blocks = 0, int64_t split_cap = 0) {
+    const int bn = small_k ? 128 : 64, bk = small_k ? 32 : 64;
+    const int64_t cap = split_cap > 0 ? split_cap : small_k ? RT_DW_CAP_SMALLK : 64;
     int64_t work = 0, rmin = mlp::DW_R;
     for (int g = 0; g < n_args; ++g) {
         const rt_linear_bwd_args& a = args[g];
@@ -1944,7 +1986,7 @@ static void dw_plan(const rt_linear_bwd_args* args, int n_args, bool small_k, un
         const int64_t r = (a.m + cap - 1) / cap;
         rmin = r > rmin ? r : rmin;
     }
-    const int64_t target = small_k ? RT_DW_BLOCKS_SMALLK : RT_DW_BLOCKS;
+    const int64_t target = target_blocks > 0 ? target_blocks : small_k ? RT_DW_BLOCKS_SMALLK : RT_DW_BLOCKS;
     rps = (work + target - 1) / target;
     rps = rps > rmin ? rps : rmin;
     rps = (rps + mlp::DW_R - 1) / mlp::DW_R * mlp::DW_R;
@@ -1965,6 +2007,14 @@ static int dw_prologue(const rt_linear_bwd_args& a) {
 // (rt_linear_bwd_dw_splits follows the same rule)
 static bool dw_mixed(const rt_linear_bwd_args* args, int n_args) {
     return n_args == 2 && (dw_prologue(args[0]) == 0) != (dw_prologue(args[1]) == 0);
+}
+
+// float4 staging loads: n, k and the A row stride multiples of 4, 16-B aligned rows
+static bool dw_vec(const rt_linear_bwd_args& a) {
+    const float* asrc = a.a_in ? a.a_in : a.src;
+    const int ald = a.a_in ? a.k : a.ld_src;
+    return (a.n % 4) == 0 && (a.k % 4) == 0 && (ald % 4) == 0 && (reinterpret_cast<uintptr_t>(asrc) & 15) == 0 &&
+           (reinterpret_cast<uintptr_t>(a.dz_ws) & 15) == 0;
 }
 
 // one dW launch over n_args sets that share a prologue family; dzf: the dz
@@ -1989,11 +2039,7 @@ static int dw_launch(const rt_linear_bwd_args* args, int n_args, bool dzf, hipSt
         // one kernel for both: prologue 3 ⊇ 2 ⊇ 1 (dropout p = 0 keeps everything)
         const int p = dw_prologue(a);
         pro = p > pro ? p : pro;
-        const float* asrc = a.a_in ? a.a_in : a.src;
-        const int ald = a.a_in ? a.k : a.ld_src;
-        (g ? L.vec1 : L.vec0) = (a.n % 4) == 0 && (a.k % 4) == 0 && (ald % 4) == 0 &&
-                                (reinterpret_cast<uintptr_t>(asrc) & 15) == 0 &&
-                                (reinterpret_cast<uintptr_t>(a.dz_ws) & 15) == 0;
+        (g ? L.vec1 : L.vec0) = dw_vec(a);
     }
     L.a0 = args[0];
     L.a1 = n_args > 1 ? args[1] : args[0];
@@ -2004,14 +2050,19 @@ static int dw_launch(const rt_linear_bwd_args* args, int n_args, bool dzf, hipSt
     if (total == 0) return RT_OK;
     const dim3 grid(total);
     const bool vec = L.vec0 && L.vec1;
+    // gather ids are staged for one split's rows (rps <= DW_MAXR with ids: dw_plan)
+    size_t id_bytes = 0;
+    for (int g = 0; g < n_args; ++g)
+        if (args[g].ids && !args[g].a_in) id_bytes = static_cast<size_t>(rps) * sizeof(int);
 #define RT_DW(BN, BK, P)                                                                                                 \
     do {                                                                                                                 \
+        const size_t lds = mlp::dw_lds_floats(BN, BK, P, dzf) * sizeof(float) + id_bytes;                                \
         if (dzf) {                                                                                                       \
-            if (vec) hipLaunchKernelGGL((mlp::linear_bwd_dw_kernel<BN, BK, P, true, true>), grid, dim3(mlp::DW_NT), 0, st, L);  \
-            else hipLaunchKernelGGL((mlp::linear_bwd_dw_kernel<BN, BK, P, false, true>), grid, dim3(mlp::DW_NT), 0, st, L);     \
+            if (vec) hipLaunchKernelGGL((mlp::linear_bwd_dw_kernel<BN, BK, P, true, true>), grid, dim3(mlp::DW_NT), lds, st, L);  \
+            else hipLaunchKernelGGL((mlp::linear_bwd_dw_kernel<BN, BK, P, false, true>), grid, dim3(mlp::DW_NT), lds, st, L);     \
         } else {                                                                                                         \
-            if (vec) hipLaunchKernelGGL((mlp::linear_bwd_dw_kernel<BN, BK, P, true, false>), grid, dim3(mlp::DW_NT), 0, st, L); \
-            else hipLaunchKernelGGL((mlp::linear_bwd_dw_kernel<BN, BK, P, false, false>), grid, dim3(mlp::DW_NT), 0, st, L);    \
+            if (vec) hipLaunchKernelGGL((mlp::linear_bwd_dw_kernel<BN, BK, P, true, false>), grid, dim3(mlp::DW_NT), lds, st, L); \
+            else hipLaunchKernelGGL((mlp::linear_bwd_dw_kernel<BN, BK, P, false, false>), grid, dim3(mlp::DW_NT), lds, st, L);    \
         }                                                                                                                \
     } while (0)
     if (small_k) {
@@ -2074,6 +2125,181 @@ extern "C" int rt_linear_bwd_dw_splits(const rt_linear_bwd_args* args, int n_arg
 
 extern "C" int rt_linear_bwd_dw_f32(const rt_linear_bwd_args* args, void* stream) {
     return rt_linear_bwd_dw_f32_multi(args, 1, stream);
+}
+
+// ---------------------------------------------------------------------------
+// joint dW launch: every Linear of a tower pair after the dz chain
+// ---------------------------------------------------------------------------
+// Body of the joint kernel a set runs on, or -1: a set the kernel has no
+// instantiation for (a recomputing prologue, unaligned 64x64 operands, a
+// gather at k > 32, a k <= 32 layer whose dz is not fused) gets a launch of
+// its own through dw_launch, after the joint one.
+static int dwj_body(const rt_linear_bwd_args& a) {
+    if (dw_prologue(a) != 0) return -1;
+    if (a.k <= 32) return dz_fusable(a) ? 0 : -1;
+    return (!dz_fusable(a) && dw_vec(a) && !(a.ids && !a.a_in)) ? 1 : -1;
+}
+
+// Block slots the joint plan fills: two 512-thread blocks on each of the 256
+// CUs (LDS: 54-63 KB per block). The k <= 32 fused-dz sets are planned by
+// dw_plan for about RT_DWJ_BLOCKS_SMALLK blocks — half of what they get in a
+// launch of their own, where 256 blocks fill the GPU; here the other sets'
+// blocks fill it, and fewer, longer first-layer blocks leave them more slots.
+// The 64x64 sets share ONE rows per split chosen so that all blocks of the
+// launch fit the slots at once: their chains grow towards the first-layer
+// sets' length, which costs no launch time and cuts the split tiles (bytes
+// stored, then folded). At C2: 130 + 372 blocks, 288 / 608 rows per split, 31
+// splits of the 64x64 sets instead of 49 + 65. A/B of the slot budget and of
+// the first-layer target: profiles/dw_joint_ab.txt.
+#ifndef RT_DWJ_SLOTS
+#define RT_DWJ_SLOTS 512
+#endif
+#ifndef RT_DWJ_BLOCKS_SMALLK
+#define RT_DWJ_BLOCKS_SMALLK 128
+#endif
+#ifndef RT_DWJ_CAP_SMALLK
+#define RT_DWJ_CAP_SMALLK 64
+#endif
+#ifndef RT_DWJ_MIN_BLOCKS
+#define RT_DWJ_MIN_BLOCKS 128
+#endif
+struct DwJointPlan {
+    int body[mlp::DWJ_MAX];
+    unsigned tn[mlp::DWJ_MAX], tk[mlp::DWJ_MAX];
+    int64_t splits[mlp::DWJ_MAX], rps[mlp::DWJ_MAX];
+};
+static void dwj_plan(const rt_linear_bwd_args* args, int n_args, DwJointPlan& P) {
+    rt_linear_bwd_args small[mlp::DWJ_MAX];
+    int small_of[mlp::DWJ_MAX], ns = 0;
+    for (int g = 0; g < n_args; ++g) {
+        P.body[g] = dwj_body(args[g]);
+        P.tn[g] = P.tk[g] = 1u;
+        P.splits[g] = 0;
+        P.rps[g] = mlp::DW_R;
+        if (P.body[g] == 0) { small_of[ns] = g; small[ns++] = args[g]; }
+    }
+    int64_t blocks_small = 0;
+    if (ns) {
+        unsigned tn[mlp::DWJ_MAX], tk[mlp::DWJ_MAX];
+        int64_t sp[mlp::DWJ_MAX], rps = mlp::DW_R;
+        dw_plan(small, ns, true, tn, tk, sp, rps, RT_DWJ_BLOCKS_SMALLK, RT_DWJ_CAP_SMALLK);
+        for (int i = 0; i < ns; ++i) {
+            const int g = small_of[i];
+            P.tn[g] = tn[i]; P.tk[g] = tk[i]; P.splits[g] = sp[i]; P.rps[g] = rps;
+            blocks_small += static_cast<int64_t>(tn[i]) * tk[i] * sp[i];
+        }
+    }
+    int64_t work = 0, rmax = mlp::DW_R;
+    for (int g = 0; g < n_args; ++g) {
+        if (P.body[g] != 1) continue;
+        P.tn[g] = static_cast<unsigned>((args[g].n + 63) / 64);
+        P.tk[g] = static_cast<unsigned>((args[g].k + 63) / 64);
+        work += args[g].m * P.tn[g] * P.tk[g];
+        rmax = args[g].m > rmax ? args[g].m : rmax;
+    }
+    if (work > 0) {
+        int64_t target = RT_DWJ_SLOTS - blocks_small;
+        target = target > RT_DWJ_MIN_BLOCKS ? target : RT_DWJ_MIN_BLOCKS;
+        int64_t rps = (work + target - 1) / target;
+        rps = (rps + mlp::DW_R - 1) / mlp::DW_R * mlp::DW_R;
+        rmax = (rmax + mlp::DW_R - 1) / mlp::DW_R * mlp::DW_R;
+        for (;; rps += mlp::DW_R) {  // whole chunks; ends at one split per set at the latest
+            int64_t blocks = 0;
+            for (int g = 0; g < n_args; ++g)
+                if (P.body[g] == 1) blocks += ((args[g].m + rps - 1) / rps) * P.tn[g] * P.tk[g];
+            if (blocks <= target || rps >= rmax) break;
+        }
+        for (int g = 0; g < n_args; ++g)
+            if (P.body[g] == 1) { P.rps[g] = rps; P.splits[g] = args[g].m > 0 ? (args[g].m + rps - 1) / rps : 0; }
+    }
+    for (int g = 0; g < n_args; ++g) {  // a launch of its own: its own plan
+        if (P.body[g] >= 0) continue;
+        int64_t sp = 0;
+        dw_plan(&args[g], 1, args[g].k <= 32, &P.tn[g], &P.tk[g], &sp, P.rps[g]);
+        P.splits[g] = sp;
+    }
+}
+
+static int dwj_validate(const rt_linear_bwd_args* args, int n_args) {
+    if (!args || n_args < 1 || n_args > mlp::DWJ_MAX) return RT_ERR_INVALID;
+    for (int g = 0; g < n_args; ++g) {
+        const int v = validate_bwd(&args[g]);
+        if (v) return v;
+        if (args[g].ids && args[g].prev_mode != 0) return RT_ERR_UNSUPPORTED;  // a gather feeds the first Linear only
+        if (args[g].fold_src && args[g].fold_in == 1) return RT_ERR_INVALID;   // no launch follows to fold into
+    }
+    return RT_OK;
+}
+
+#ifdef RT_NO_AIN  // A/B build: no staged-input copy (as rt_linear_bwd_dw_f32_multi)
+#define RT_DWJ_NO_AIN(args, n_args)                                                        \
+    rt_linear_bwd_args noa[mlp::DWJ_MAX];                                                  \
+    for (int g = 0; g < n_args; ++g) { noa[g] = args[g]; noa[g].a_in = nullptr; }          \
+    args = noa;
+#else
+#define RT_DWJ_NO_AIN(args, n_args)
+#endif
+
+extern "C" int rt_linear_bwd_dw_joint_splits(const rt_linear_bwd_args* args, int n_args, int64_t* splits) {
+    if (!splits) return RT_ERR_INVALID;
+    const int v = dwj_validate(args, n_args);
+    if (v) return v;
+#ifdef RT_NO_DW_PART  // A/B build: callers keep the atomic dW adds
+    return RT_ERR_UNSUPPORTED;
+#endif
+    RT_DWJ_NO_AIN(args, n_args)
+    DwJointPlan P;
+    dwj_plan(args, n_args, P);
+    for (int g = 0; g < n_args; ++g) splits[g] = P.splits[g];
+    return RT_OK;
+}
+
+extern "C" int rt_linear_bwd_dw_f32_joint(const rt_linear_bwd_args* args, int n_args, void* stream) {
+    const int v = dwj_validate(args, n_args);
+    if (v) return v;
+    RT_DWJ_NO_AIN(args, n_args)
+    DwJointPlan P;
+    dwj_plan(args, n_args, P);
+    hipStream_t st = as_stream(stream);
+    mlp::DwJointLaunch L{};
+    bool vs = true;
+    size_t lds = 0;
+    int64_t total = 0;
+    for (int body = 0; body < 2; ++body) {  // longest chains first
+        for (int g = 0; g < n_args; ++g) {
+            if (P.body[g] != body) continue;
+            const int64_t nb = static_cast<int64_t>(P.tn[g]) * P.tk[g] * P.splits[g];
+            if (nb == 0) continue;
+            total += nb;
+            if (total > (1ll << 30)) return RT_ERR_UNSUPPORTED;
+            const int s = L.nsets++;
+            L.a[s] = args[g];
+            L.rps[s] = P.rps[g];
+            L.tn[s] = P.tn[g];
+            L.tk[s] = P.tk[g];
+            L.end[s] = static_cast<unsigned>(total);
+            L.body[s] = static_cast<unsigned char>(body);
+            size_t need = mlp::dw_lds_floats(body ? 64 : 128, body ? 64 : 32, 0, body == 0) * sizeof(float);
+            if (body == 0) {
+                vs = vs && dw_vec(args[g]);
+                if (args[g].ids && !args[g].a_in) need += static_cast<size_t>(P.rps[g]) * sizeof(int);
+            }
+            lds = need > lds ? need : lds;
+        }
+    }
+    if (total > 0) {
+        const dim3 grid(static_cast<unsigned>(total));
+        if (vs) hipLaunchKernelGGL(mlp::linear_bwd_dw_joint_kernel<true>, grid, dim3(mlp::DW_NT), lds, st, L);
+        else hipLaunchKernelGGL(mlp::linear_bwd_dw_joint_kernel<false>, grid, dim3(mlp::DW_NT), lds, st, L);
+        const int rc = check_launch("linear_bwd_dw_joint_kernel");
+        if (rc) return rc;
+    }
+    for (int g = 0; g < n_args; ++g) {
+        if (P.body[g] >= 0) continue;
+        const int rc = dw_launch(&args[g], 1, dz_fusable(args[g]), st);
+        if (rc) return rc;
+    }
+    return RT_OK;
 }
 
 #ifdef RT_PHASE_PROBE

@@ -2,8 +2,9 @@
 rt_linear_bwd_f32) and the flat parameter slab.
 
 A tower's ``mlp`` (src/models/two_tower.py:56-72: [Linear → act → BatchNorm1d →
-Dropout] × L → Linear) is run as L+1 kernel launches forward and 2(L+1)
-backward; the row gather of the input features (layer 1), BatchNorm (batch
+Dropout] × L → Linear) is run as L+1 kernel launches forward and L + 1
+backward (a dz launch per layer with an input gradient, then one joint dW
+launch; 2(L+1) − 1 in the per-layer order); the row gather of the input features (layer 1), BatchNorm (batch
 statistics finalised from fp64 column sums), activation, dropout and the final
 F.normalize are fused into those launches. Parameter gradients are
 accumulated straight into one flat fp32 grad slab (views are the params'
@@ -470,27 +471,120 @@ def chain_backward(blocks: List[Block], ctx: ChainCtx, dout: torch.Tensor, slab:
     layers, dsrc, keep = _backward_plan(blocks, ctx, dout, slab, want_dsrc, seed_offset, stats_arena, attach)
     st = _stream(dout)
     groups = [[a] for a in layers]
+    if dw_joint_enabled():  # every dz launch, then ONE dW launch (atomic adds: no fold sink here)
+        _launch_bwd_joint(groups, st, None)
+        return dsrc
     keep += _plan_partials(groups, dout.device)
     for g in groups:  # per Linear: dz (+dA) then dW (+dbias), timed separately (bench roofline)
         _launch_bwd(g, st)
     return dsrc
 
 
-def chain_backward_pair(first: tuple, second: tuple) -> None:
+def chain_backward_pair(first: tuple, second: tuple, fold_sink: Optional["FoldSink"] = None) -> None:
     """Backward of two independent chains (``chain_backward`` positional
-    arguments each, no dsrc); layer l of both runs as ONE dz launch and ONE dW
-    launch (``rt_linear_bwd_*_f32_multi``) when the depths match."""
+    arguments each, no dsrc). Matching depths: layer l of both runs as ONE dz
+    launch, last layer first, and ONE joint dW launch follows the dz chain
+    (``rt_linear_bwd_dw_f32_joint``). With a ``fold_sink`` the joint launch
+    stores its row-split tiles there and the sink's owner folds them
+    (``rt_grad_sqnorm_fold``); without one it adds them with atomics.
+    ``RTREC_DW_LEGACY=1`` (or a library without the joint entry points) keeps
+    the per-layer order: one dz and one dW launch per layer
+    (``rt_linear_bwd_*_f32_multi``), as depth-mismatched pairs always do."""
     # keep1/keep2 hold the planned buffers until every launch is enqueued
     l1, _, keep1 = _backward_plan(*first)
     l2, _, keep2 = _backward_plan(*second)
     st = _stream(first[2])
     if len(l1) == len(l2):
         groups = [[a, b] for a, b in zip(l1, l2)]
+        if dw_joint_enabled():
+            _launch_bwd_joint(groups, st, fold_sink)
+            return
         keep1 += _plan_partials(groups, first[2].device)
     else:
         groups = [[a] for a in l1 + l2]
     for g in groups:
         _launch_bwd(g, st)
+
+
+def dw_joint_enabled() -> bool:
+    """The joint backward order, unless ``RTREC_DW_LEGACY=1`` (read at every
+    call: the parent-order A/B and the equivalence tests flip it) or the loaded
+    library predates the joint entry points."""
+    lib = native.lib()
+    return (os.environ.get("RTREC_DW_LEGACY", "0") != "1" and hasattr(lib, "rt_linear_bwd_dw_f32_joint")
+            and hasattr(lib, "rt_linear_bwd_dw_joint_splits") and hasattr(lib, "rt_linear_bwd_dz_fused"))
+
+
+class FoldSink:
+    """The joint dW launch's row-split partial tiles and their fold descriptors,
+    owned by whoever folds them (``FusedTrainStep``: its norm launch runs after
+    ``chain_backward_pair`` has returned, so a buffer local to the backward
+    would be back in the caching allocator before its reader is enqueued, and
+    a captured graph keeps the pointer). Grow-only; earlier buffers stay alive
+    for the graphs that hold them."""
+
+    def __init__(self, slab: ParamSlab):
+        self.slab = slab
+        self.buf: Optional[torch.Tensor] = None
+        self.retired: list = []
+        self.folds: list = []   # native.GradFold of the backward enqueued last
+
+    def begin(self) -> None:
+        self.folds = []
+
+    def place(self, sets: list, splits: list) -> None:
+        """Give each set its [splits][n][k] region and record its fold."""
+        grad = self.slab.grad
+        index = {o: i for i, o in enumerate(self.slab.offsets)}
+        plan, total = [], 0
+        for a, sp in zip(sets, splits):
+            words = a.n * a.k
+            off = (a.dw - grad.data_ptr()) // 4
+            if sp < 1 or words % 4 or off not in index or len(plan) >= native.GRAD_FOLD_MAX:
+                continue  # this set adds with atomics
+            plan.append((a, sp, words, off, total))
+            total += sp * words
+        if self.buf is None or self.buf.numel() < total:
+            if self.buf is not None:
+                self.retired.append(self.buf)
+            self.buf = torch.empty(max(total, 64), dtype=torch.float32, device=grad.device)
+        base = self.buf.data_ptr()
+        for a, sp, words, off, start in plan:
+            a.dw_part = base + 4 * start
+            self.folds.append(native.GradFold(a.dw_part, off, words, sp, index[off]))
+
+
+def _launch_bwd_joint(groups: list, st, sink: Optional[FoldSink]) -> None:
+    """``groups``: per layer (last first) the argument sets of one dz launch.
+    Every dz launch, then the dW of all sets as one launch per
+    ``native.DW_JOINT_MAX`` sets (one launch for a 3-Linear tower pair)."""
+    lib = native.lib()
+    for g in groups:
+        arr = (LinearBwdArgs * len(g))(*g)
+        if lib.rt_linear_bwd_dz_fused(arr, len(g)):
+            continue  # these sets' dW blocks compute dz
+        for a in g:
+            a.fuse_dz = 0  # the joint launch decides the fusion per set: this dz launch runs
+        _launch_dz(g, st)
+    sets = [a for g in groups for a in g]
+    chunks = [sets[i:i + native.DW_JOINT_MAX] for i in range(0, len(sets), native.DW_JOINT_MAX)]
+    if sink is not None:
+        # all layers but the first (the last group) store their split tiles, as in the per-layer order
+        cand = {id(a) for g in groups[:-1] for a in g}
+        part_sets, part_splits = [], []
+        for ch in chunks:
+            splits = (ctypes.c_int64 * len(ch))()
+            if lib.rt_linear_bwd_dw_joint_splits((LinearBwdArgs * len(ch))(*ch), len(ch), splits) != 0:
+                continue  # no plan to size the tiles by: these sets add with atomics (the launch reports errors)
+            for a, sp in zip(ch, splits):
+                if id(a) in cand:
+                    part_sets.append(a)
+                    part_splits.append(int(sp))
+        sink.place(part_sets, part_splits)
+    with TIMER.region("linear_bwd_dw", flops=sum(2.0 * a.m * a.k * a.n for a in sets),
+                      bytes_=sum(4.0 * (a.m * a.n + a.m * a.k + a.n * a.k) for a in sets)):
+        for ch in chunks:
+            call("rt_linear_bwd_dw_f32_joint", (LinearBwdArgs * len(ch))(*ch), len(ch), st)
 
 
 def _plan_partials(groups: list, dev) -> list:
@@ -527,18 +621,27 @@ def _plan_partials(groups: list, dev) -> list:
 
 
 def _launch_bwd(group: list, st) -> None:
-    da = [a.g_prev is not None or a.dsrc is not None for a in group]
-    flops = sum((2.0 if d else 0.0) * a.m * a.k * a.n for a, d in zip(group, da))
-    nbytes = sum(4.0 * (3 * a.m * a.n + (2 * a.m * a.k if d else 0) + a.n * a.k) for a, d in zip(group, da))
+    """The per-layer order: this group's dz launch (unless fused), then its dW launch."""
     arr = (LinearBwdArgs * len(group))(*group)
     lib = native.lib()
     fused = hasattr(lib, "rt_linear_bwd_dz_fused") and lib.rt_linear_bwd_dz_fused(arr, len(group))
     if not fused:  # else the dW launch computes dz (older library builds: always the dz launch)
-        with TIMER.region("linear_bwd_dz", flops=flops, bytes_=nbytes):
-            call("rt_linear_bwd_dz_f32_multi", arr, len(group), st)
+        _launch_dz(group, st)
+    _launch_dw(group, st)
+
+
+def _launch_dz(group: list, st) -> None:
+    da = [a.g_prev is not None or a.dsrc is not None for a in group]
+    flops = sum((2.0 if d else 0.0) * a.m * a.k * a.n for a, d in zip(group, da))
+    nbytes = sum(4.0 * (3 * a.m * a.n + (2 * a.m * a.k if d else 0) + a.n * a.k) for a, d in zip(group, da))
+    with TIMER.region("linear_bwd_dz", flops=flops, bytes_=nbytes):
+        call("rt_linear_bwd_dz_f32_multi", (LinearBwdArgs * len(group))(*group), len(group), st)
+
+
+def _launch_dw(group: list, st) -> None:
     with TIMER.region("linear_bwd_dw", flops=sum(2.0 * a.m * a.k * a.n for a in group),
                       bytes_=sum(4.0 * (a.m * a.n + a.m * a.k + a.n * a.k) for a in group)):
-        call("rt_linear_bwd_dw_f32_multi", arr, len(group), st)
+        call("rt_linear_bwd_dw_f32_multi", (LinearBwdArgs * len(group))(*group), len(group), st)
 
 
 def _backward_plan(blocks: List[Block], ctx: ChainCtx, dout: torch.Tensor, slab: ParamSlab,

@@ -74,6 +74,15 @@ class LinearBwdArgs(ctypes.Structure):
     ]
 
 
+class GradFold(ctypes.Structure):
+    """rt_grad_fold: one tensor's row-split partials for rt_grad_sqnorm_fold."""
+    _fields_ = [("part", vp), ("dst_off", c_i64), ("words", c_i64), ("splits", c_int), ("tensor", c_int)]
+
+
+GRAD_FOLD_MAX = 8    # RT_GRAD_FOLD_MAX
+DW_JOINT_MAX = 6     # argument sets of one rt_linear_bwd_dw_f32_joint call
+
+
 # name -> (restype, argtypes); mirrors include/rtrec_hip.h one-to-one
 SIGNATURES = {
     "rt_abi_version": (c_int, []),
@@ -107,6 +116,8 @@ SIGNATURES = {
     "rt_linear_fwd_f32_multi": (c_int, [ctypes.POINTER(LinearFwdArgs), c_int, vp]),
     "rt_linear_bwd_dz_f32_multi": (c_int, [ctypes.POINTER(LinearBwdArgs), c_int, vp]),
     "rt_linear_bwd_dw_f32_multi": (c_int, [ctypes.POINTER(LinearBwdArgs), c_int, vp]),
+    "rt_linear_bwd_dw_f32_joint": (c_int, [ctypes.POINTER(LinearBwdArgs), c_int, vp]),
+    "rt_linear_bwd_dw_joint_splits": (c_int, [ctypes.POINTER(LinearBwdArgs), c_int, ctypes.POINTER(c_i64)]),
     "rt_twotower_loss_workspace_bytes": (c_size, [c_i64, c_int]),
     "rt_twotower_loss_fwd_bwd": (c_int, [vp, vp, vp, c_int, c_i64, c_int, c_int, c_f32, vp, vp, c_f32,
                                          c_f32, vp, vp, vp, vp, vp, vp, vp, c_size, vp]),
@@ -116,6 +127,7 @@ SIGNATURES = {
     "rt_inbatch_loss_fwd_bwd": (c_int, [vp, vp, c_int, c_i64, c_i64, c_int, c_i64, c_f32, vp, vp, vp, vp, c_size, vp]),
     "rt_similarity_f32": (c_int, [vp, vp, c_i64, c_int, c_f32, vp, vp, vp, vp]),
     "rt_grad_sqnorm": (c_int, [vp, vp, c_int, vp, vp, vp, vp]),
+    "rt_grad_sqnorm_fold": (c_int, [vp, vp, c_int, vp, vp, vp, ctypes.POINTER(GradFold), c_int, vp]),
     "rt_clip_adam_step": (c_int, [vp, vp, vp, vp, c_i64, vp, c_int, c_f32, c_f32, vp, c_f32, c_f32, c_f32,
                                   c_f32, c_int, vp, vp, c_i64, vp]),
     "rt_l2_augment_f32": (c_int, [vp, c_i64, c_int, vp, c_int, c_int, vp]),

@@ -4,8 +4,9 @@ launches, with no autograd and no torch compute:
 
   user tower fwd │ pos item tower fwd │ neg item tower fwd   (gather fused into layer 1)
   fused loss fwd+bwd (0.7·contrastive + 0.3·in-batch)          rt_twotower_loss_fwd_bwd
-  neg / pos / user tower bwd  (grads → flat slab, atomics)      rt_linear_bwd_f32 × 2(L+1) each
-  clip_grad_norm_(1.0) + Adam(lr, wd)                           rt_grad_sqnorm + rt_clip_adam_step
+  tower bwd: one dz launch per layer with a dA, then ONE dW     rt_linear_bwd_dz_f32_multi × L
+  launch for every Linear of both towers (grads → flat slab)    + rt_linear_bwd_dw_f32_joint
+  clip_grad_norm_(1.0) + Adam(lr, wd)                           rt_grad_sqnorm(_fold) + rt_clip_adam_step
 
 Parameters, grads and Adam moments live in flat fp32 slabs; the step counter
 and learning rate live on the device so the whole step can be captured in a
@@ -20,7 +21,7 @@ from typing import Dict, Optional
 import torch
 
 from .. import kernels, native
-from ..models.fused import (blocks_from_sequential, chain_backward, chain_backward_pair, chain_forward,
+from ..models.fused import (FoldSink, blocks_from_sequential, chain_backward, chain_backward_pair, chain_forward,
                             chain_forward_pair, stats_arena_size)
 from ..models.two_tower import TwoTowerModel
 from ..native import call, ptr
@@ -66,6 +67,9 @@ class FusedTrainStep:
         # its pointer): grow-only, earlier buffers stay alive for graphs that hold them
         self._loss_ws: Optional[torch.Tensor] = None
         self._loss_ws_retired = []
+        # the joint dW launch's row-split tiles, folded by this step's norm launch:
+        # owned here for the same reason (models/fused.py FoldSink)
+        self._fold = FoldSink(self.slab)
         # fp64 accumulators, cleared without memset launches: the BN column sums of
         # the 3 tower calls (fwd + bwd) and the dbias slots live in ``arena``, which
         # clip+Adam zeroes as the step's last launch (with the grads it consumes);
@@ -219,9 +223,15 @@ class FusedTrainStep:
                  ptr(slab.grad_of(ubias)) if ubias is not None else None,
                  ptr(slab.grad_of(ibias)) if ibias is not None else None, ptr(ws), ws.numel(), st)
         # backward: independent chains (grads meet in the slab through atomics)
-        if merged:  # user and item tower layer l in one dz and one dW launch
+        self._fold.begin()
+        if merged:
+            # user and item tower layer l in one dz launch, then one dW launch for all
+            # layers. Single process: its row-split tiles are folded by the norm launch
+            # (_fold_norm); with a process group the all-reduce sits between the
+            # gradients and the norm, so the dW launch adds with atomics instead
             chain_backward_pair((ib, pq, dpq, slab, False, so, self.a_pqb, False),
-                                (ub, u, du, slab, False, so, self.a_ub, False))
+                                (ub, u, du, slab, False, so, self.a_ub, False),
+                                fold_sink=self._fold if self.pg is None else None)
         else:
             s_u.wait_stream(main)
             with torch.cuda.stream(s_u):
@@ -256,16 +266,36 @@ class FusedTrainStep:
 
     def _update(self):
         """clip_grad_norm_ + Adam on the flat slabs (device step counter / lr)."""
+        nb = self.slab.data.numel() * 4.0
+        with TIMER.region("clip_adam", flops=0.0, bytes_=nb * 7):
+            self._fold_norm()
+            self._adam()
+        return self.loss_buf
+
+    def _fold_norm(self):
+        """First half of ``_update``: the per-tensor grad norms (and the step /
+        dropout counters); the backward's row-split tiles, if it stored any, are
+        folded into the grad slab on the way. The slab holds the step's complete
+        gradients from here until ``_adam`` consumes them."""
         slab = self.slab
         st = native.stream_of(slab.data)
-        nb = slab.data.numel() * 4.0
-        with TIMER.region("clip_adam", flops=0.0, bytes_=nb * 7):
+        folds = self._fold.folds
+        if folds:
+            arr = (native.GradFold * len(folds))(*folds)
+            call("rt_grad_sqnorm_fold", ptr(slab.grad), ptr(slab.tensor_offsets()), len(slab.params),
+                 ptr(self.sumsq), ptr(self.step_dev), ptr(self.seed_dev), arr, len(folds), st)
+            self._fold.begin()  # folded: a second norm over the same gradients must not add them again
+        else:
             call("rt_grad_sqnorm", ptr(slab.grad), ptr(slab.tensor_offsets()), len(slab.params), ptr(self.sumsq),
                  ptr(self.step_dev), ptr(self.seed_dev), st)
-            call("rt_clip_adam_step", ptr(slab.data), ptr(slab.grad), ptr(self.exp_avg), ptr(self.exp_avg_sq),
-                 slab.data.numel(), ptr(self.sumsq), len(slab.params), self.max_norm, self.lr, ptr(self.lr_dev),
-                 self.b1, self.b2, self.eps, self.wd, 1, ptr(self.step_dev), ptr(self.arena), self.arena.numel(), st)
-        return self.loss_buf
+
+    def _adam(self):
+        """Second half of ``_update``: clip + Adam; zeroes the grads and the stats arena."""
+        slab = self.slab
+        st = native.stream_of(slab.data)
+        call("rt_clip_adam_step", ptr(slab.data), ptr(slab.grad), ptr(self.exp_avg), ptr(self.exp_avg_sq),
+             slab.data.numel(), ptr(self.sumsq), len(slab.params), self.max_norm, self.lr, ptr(self.lr_dev),
+             self.b1, self.b2, self.eps, self.wd, 1, ptr(self.step_dev), ptr(self.arena), self.arena.numel(), st)
 
     def __call__(self, user_src: torch.Tensor, pos_src: torch.Tensor, neg_src: Optional[torch.Tensor],
                  user_ids: Optional[torch.Tensor] = None, pos_ids: Optional[torch.Tensor] = None,
