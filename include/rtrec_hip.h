@@ -92,6 +92,33 @@ int rt_flatip_topk(const void* queries, int64_t nq, const void* items, int64_t n
                    float* out_scores, int64_t* out_ids, void* workspace, size_t workspace_bytes,
                    void* stream);
 
+/* Online (small-batch) search: the same contract as rt_flatip_topk — same
+ * arguments, same result rows, fp32 scores bit-identical to the oracle, and
+ * f16/bf16 scores the same fp32 fmaf chain over the widened elements — for
+ * 1 <= nq <= RT_ONLINE_MAX_NQ and k <= RT_ONLINE_MAX_K, bound by one streaming
+ * pass over the corpus instead of by query tiles. Serves the reference's
+ * per-request path: faiss.IndexFlatIP.search with ONE user embedding
+ * (src/serving/retrieval.py:141-197 at Q = 1, called from
+ * src/serving/service.py:268-302). Two launches (a scan whose grid is sized by
+ * rows, one finish block per query), stream-ordered, capturable.
+ *   rt_flatip_topk_online: RT_ERR_UNSUPPORTED for nq > RT_ONLINE_MAX_NQ or
+ *     k > RT_ONLINE_MAX_K (and for the d / dtype / id range rt_flatip_topk
+ *     refuses); RT_ERR_INVALID and RT_ERR_WORKSPACE as rt_flatip_topk;
+ *     nx == 0: every slot (-FLT_MAX, -1). The workspace is 8-byte aligned.
+ *   rt_flatip_topk_online_workspace_bytes: the per-block partial lists
+ *     [nq][k][blocks] of 8-byte composite keys (256 for a refused shape).
+ *   rt_flatip_topk_online_plan: host only, no device work: out = {blocks,
+ *     rows_per_block} of the scan (block b owns the contiguous rows
+ *     [b * rows_per_block, min(nx, (b + 1) * rows_per_block))). */
+#define RT_ONLINE_MAX_NQ 8
+#define RT_ONLINE_MAX_K 128
+size_t rt_flatip_topk_online_workspace_bytes(int64_t nq, int64_t nx, int d, int dtype, int k);
+int rt_flatip_topk_online_plan(int64_t nq, int64_t nx, int d, int dtype, int k, int64_t* out);
+int rt_flatip_topk_online(const void* queries, int64_t nq, const void* items, int64_t nx, int d, int dtype,
+                          int k, const uint32_t* exclude_bits, int64_t exclude_words, int64_t id_offset,
+                          float* out_scores, int64_t* out_ids, void* workspace, size_t workspace_bytes,
+                          void* stream);
+
 /* Corpus-sharded search with ONE corpus-wide threshold per query (several
  * GPUs, each holding a row shard of the corpus that faiss.IndexFlatIP.search
  * would scan whole, src/serving/retrieval.py:141-197): every rank samples its

@@ -129,6 +129,63 @@ def flatip_topk(queries: torch.Tensor, items: torch.Tensor, k: int,
 
 TOPK_MAX_K = 512  # rt_flatip_topk: k <= 512 per launch (include/rtrec_hip.h)
 
+ONLINE_MAX_NQ = 8   # RT_ONLINE_MAX_NQ
+ONLINE_MAX_K = 128  # RT_ONLINE_MAX_K
+
+
+def flatip_topk_online_plan(nq: int, nx: int, d: int, dtype: torch.dtype, k: int) -> Tuple[int, int]:
+    """Host-only plan of the online scan (rt_flatip_topk_online_plan):
+    ``(blocks, rows_per_block)``; block b owns the contiguous rows
+    ``[b * rows_per_block, min(nx, (b + 1) * rows_per_block))``. No device work."""
+    out = (ctypes.c_int64 * 2)()
+    call("rt_flatip_topk_online_plan", int(nq), int(nx), int(d), native.dtype_code(dtype), int(k),
+         ctypes.cast(out, ctypes.c_void_p))
+    return int(out[0]), int(out[1])
+
+
+def flatip_topk_online(queries: torch.Tensor, items: torch.Tensor, k: int,
+                       exclude_bits: Optional[torch.Tensor] = None, id_offset: int = 0,
+                       out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                       workspace_buf: Optional[torch.Tensor] = None
+                       ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """:func:`flatip_topk` for 1..8 queries and k <= 128 (rt_flatip_topk_online):
+    the same results, from one streaming pass over the corpus — the shape of
+    the serving path (one user per request, src/serving/retrieval.py:141-197).
+    ``workspace_buf``: a caller-owned uint8 device buffer of at least
+    ``rt_flatip_topk_online_workspace_bytes`` (default: the shared grow-only one)."""
+    native.require_device(queries, items, what="flatip_topk_online")
+    if queries.dim() != 2 or items.dim() != 2 or queries.shape[1] != items.shape[1]:
+        raise ValueError(f"shape mismatch: queries {tuple(queries.shape)} items {tuple(items.shape)}")
+    if queries.dtype != items.dtype:
+        raise TypeError("queries and items must share a dtype")
+    if k <= 0:
+        raise ValueError("k must be positive")
+    if not queries.is_contiguous() or not items.is_contiguous():
+        raise ValueError("flatip_topk_online expects contiguous queries and items")
+    nq, d = queries.shape
+    nx = items.shape[0]
+    dt = native.dtype_code(queries.dtype)
+    if out is None:
+        scores = torch.empty((nq, k), dtype=torch.float32, device=queries.device)
+        ids = torch.empty((nq, k), dtype=torch.int64, device=queries.device)
+    else:
+        scores, ids = out
+    if nq == 0:
+        return scores, ids
+    words = 0
+    if exclude_bits is not None:
+        if exclude_bits.dtype not in (torch.int32, torch.uint32) or exclude_bits.shape[0] != nq \
+                or not exclude_bits.is_contiguous():
+            raise ValueError("exclude_bits must be contiguous int32/uint32 [nq, words]")
+        words = exclude_bits.shape[1]
+    ws = workspace_buf
+    if ws is None:
+        ws = workspace(queries.device, native.lib().rt_flatip_topk_online_workspace_bytes(nq, nx, d, dt, k),
+                       "topk_online")
+    call("rt_flatip_topk_online", ptr(queries), nq, ptr(items) if nx else None, nx, d, dt, k, ptr(exclude_bits),
+         words, id_offset, ptr(scores), ptr(ids), ptr(ws), ws.numel(), stream_of(queries))
+    return scores, ids
+
 
 def _flatip_topk_wide(queries, items, k, exclude_bits, id_offset, out):
     """k > 512 (faiss.IndexFlatIP.search takes any k, src/serving/retrieval.py:

@@ -94,6 +94,10 @@ SIGNATURES = {
     "rt_flatip_topk_workspace_bytes": (c_size, [c_i64, c_i64, c_int, c_int, c_int]),
     "rt_flatip_topk": (c_int, [vp, c_i64, vp, c_i64, c_int, c_int, c_int, vp, c_i64, c_i64, vp, vp, vp,
                                c_size, vp]),
+    "rt_flatip_topk_online_workspace_bytes": (c_size, [c_i64, c_i64, c_int, c_int, c_int]),
+    "rt_flatip_topk_online_plan": (c_int, [c_i64, c_i64, c_int, c_int, c_int, vp]),
+    "rt_flatip_topk_online": (c_int, [vp, c_i64, vp, c_i64, c_int, c_int, c_int, vp, c_i64, c_i64, vp, vp, vp,
+                                      c_size, vp]),
     "rt_topk_merge": (c_int, [vp, vp, c_i64, c_int, c_int, c_int, vp, vp, vp]),
     "rt_flatip_topk_tuning": (c_int, [c_int, c_int, c_int]),
     "rt_flatip_topk_shard_workspace_bytes": (c_size, [c_i64, c_i64, c_int, c_int, c_int]),
