@@ -552,6 +552,54 @@ int rt_clip_adam_step(float* params, float* grads, float* exp_avg, float* exp_av
                       void* stream);
 
 /* ------------------------------------------------------------------------
+ * Tower inference for one request: UserTower.forward in eval mode
+ * (src/models/two_tower.py:98-134) as the serving path calls it,
+ * `model.get_user_embeddings(...)` on one feature row
+ * (src/serving/service.py:286-293) — every Linear, activation, BatchNorm1d
+ * (running statistics) and the final F.normalize in ONE launch of ONE
+ * workgroup, for m = 1..RT_TOWER_MAX_ROWS rows. Dropout is off (eval).
+ *   per row:   a = src[ids ? ids[r] : r][0 : layers[0].k]
+ *   per layer: z = a . W^T + bias;  a = act(z);  with bn_gamma != NULL:
+ *              a = (a - mean) / sqrt(var + eps) * gamma + beta
+ *   normalize: out[r] = z / max(||z||_2, 1e-12) of the last layer's rows;
+ *              norms_out[r] = ||z||_2 (optional, with or without normalize).
+ * The reference tower sets act and BatchNorm on every Linear but the last
+ * (act = RT_ACT_NONE, bn_gamma = NULL there).
+ * An id outside [0, src_rows) reads a row of zeros; nothing outside src is
+ * read. fp32 fmaf sums throughout. A row's output bits depend neither on m
+ * nor on the row's slot in the call.
+ * RT_ERR_INVALID: NULL args / src / out / w, m or n_layers out of range, a
+ *   width < 1, ld_src < layers[0].k, ids == NULL with src_rows < m, an
+ *   incomplete BatchNorm set. RT_ERR_UNSUPPORTED: a width above
+ *   RT_TOWER_MAX_WIDTH, or layers[i].k != layers[i-1].n.
+ * ------------------------------------------------------------------------ */
+#define RT_TOWER_MAX_LAYERS 8
+#define RT_TOWER_MAX_ROWS   8
+#define RT_TOWER_MAX_WIDTH  512
+typedef struct {
+    const float* w;        /* [n, k] row-major */
+    const float* bias;     /* [n] or NULL */
+    int k, n;
+    int act;               /* rt_act applied to this Linear's output; RT_ACT_NONE on the last */
+    const float* bn_gamma; /* NULL = no BatchNorm after act */
+    const float* bn_beta;
+    const float* bn_mean;  /* running_mean */
+    const float* bn_var;   /* running_var  */
+    float bn_eps;
+} rt_tower_layer;
+typedef struct {
+    const float* src; int64_t src_rows; int ld_src;
+    const int64_t* ids;    /* optional [m] rows of src (fused gather); NULL = rows 0..m-1 */
+    int m;                 /* 1..RT_TOWER_MAX_ROWS */
+    int n_layers;          /* 1..RT_TOWER_MAX_LAYERS */
+    rt_tower_layer layers[RT_TOWER_MAX_LAYERS];
+    int normalize;         /* 1: F.normalize(p=2, eps=1e-12) of the last layer's rows */
+    float* out;            /* [m, n_last] */
+    float* norms_out;      /* optional [m] */
+} rt_tower_infer_args;
+int rt_tower_infer_f32(const rt_tower_infer_args* args, void* stream);
+
+/* ------------------------------------------------------------------------
  * Offline evaluation (scripts/evaluate_model.py:162-234, src/evaluation/
  * metrics.py:73-228,248-319).
  *

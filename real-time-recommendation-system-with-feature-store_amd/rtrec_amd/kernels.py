@@ -187,6 +187,13 @@ def flatip_topk_online(queries: torch.Tensor, items: torch.Tensor, k: int,
     return scores, ids
 
 
+def tower_infer(args: "native.TowerInferArgs", stream) -> None:
+    """The whole eval-mode tower for 1..8 rows in one launch (rt_tower_infer_f32;
+    UserTower.forward as src/serving/service.py:286-293 calls it). ``args`` holds
+    raw device pointers: the caller keeps their tensors alive and on a device."""
+    call("rt_tower_infer_f32", ctypes.byref(args), stream)
+
+
 def _flatip_topk_wide(queries, items, k, exclude_bits, id_offset, out):
     """k > 512 (faiss.IndexFlatIP.search takes any k, src/serving/retrieval.py:
     170-171): ceil(k/512) exact passes of rt_flatip_topk, each excluding every

@@ -79,6 +79,21 @@ class GradFold(ctypes.Structure):
     _fields_ = [("part", vp), ("dst_off", c_i64), ("words", c_i64), ("splits", c_int), ("tensor", c_int)]
 
 
+TOWER_MAX_LAYERS, TOWER_MAX_ROWS, TOWER_MAX_WIDTH = 8, 8, 512   # RT_TOWER_MAX_*
+
+
+class TowerLayer(ctypes.Structure):
+    """rt_tower_layer: one Linear and the activation / eval BatchNorm that follow it."""
+    _fields_ = [("w", vp), ("bias", vp), ("k", c_int), ("n", c_int), ("act", c_int), ("bn_gamma", vp),
+                ("bn_beta", vp), ("bn_mean", vp), ("bn_var", vp), ("bn_eps", c_f32)]
+
+
+class TowerInferArgs(ctypes.Structure):
+    _fields_ = [("src", vp), ("src_rows", c_i64), ("ld_src", c_int), ("ids", vp), ("m", c_int),
+                ("n_layers", c_int), ("layers", TowerLayer * TOWER_MAX_LAYERS), ("normalize", c_int),
+                ("out", vp), ("norms_out", vp)]
+
+
 GRAD_FOLD_MAX = 8    # RT_GRAD_FOLD_MAX
 DW_JOINT_MAX = 6     # argument sets of one rt_linear_bwd_dw_f32_joint call
 
@@ -122,6 +137,7 @@ SIGNATURES = {
     "rt_linear_bwd_dw_f32_multi": (c_int, [ctypes.POINTER(LinearBwdArgs), c_int, vp]),
     "rt_linear_bwd_dw_f32_joint": (c_int, [ctypes.POINTER(LinearBwdArgs), c_int, vp]),
     "rt_linear_bwd_dw_joint_splits": (c_int, [ctypes.POINTER(LinearBwdArgs), c_int, ctypes.POINTER(c_i64)]),
+    "rt_tower_infer_f32": (c_int, [ctypes.POINTER(TowerInferArgs), vp]),
     "rt_twotower_loss_workspace_bytes": (c_size, [c_i64, c_int]),
     "rt_twotower_loss_fwd_bwd": (c_int, [vp, vp, vp, c_int, c_i64, c_int, c_int, c_f32, vp, vp, c_f32,
                                          c_f32, vp, vp, vp, vp, vp, vp, vp, c_size, vp]),

@@ -401,11 +401,17 @@ class OnlineSearcher:
         self._generation = -1
         self._rows: Optional[torch.Tensor] = None
 
-    def _sequence(self, nq: int, k: int):
-        """The stream-ordered chain of one call, on torch's current stream."""
+    def _upload(self, nq: int):
+        """H2D copy of the pinned queries into the fp32 device query rows."""
+        self._d_q32[:nq].copy_(self._h_q[:nq], non_blocking=True)
+
+    def _device_chain(self, nq: int, k: int):
+        """``_d_q32[:nq]`` (fp32 device rows, however they got there: ``_upload``,
+        or a kernel that wrote them — :class:`rtrec_amd.serving.online.OnlineRecommender`)
+        -> ``l2_renorm`` for the cosine metric (in place) -> storage-dtype cast ->
+        ``rt_flatip_topk_online`` into the device scores / positions."""
         n = nq * k
         q32 = self._d_q32[:nq]
-        q32.copy_(self._h_q[:nq], non_blocking=True)
         if self.index.metric == "cosine":
             kernels.l2_renorm_(q32)
         q = self._d_q[:nq]
@@ -413,8 +419,34 @@ class OnlineSearcher:
             q.copy_(q32)
         kernels.flatip_topk_online(q, self._rows, k, out=(self._d_s[:n].view(nq, k), self._d_p[:n].view(nq, k)),
                                    workspace_buf=self._ws)
+
+    def _download(self, nq: int, k: int):
+        """D2H copies of scores and positions into the pinned result buffers."""
+        n = nq * k
         self._h_s[:n].copy_(self._d_s[:n], non_blocking=True)
         self._h_p[:n].copy_(self._d_p[:n], non_blocking=True)
+
+    def _sequence(self, nq: int, k: int):
+        """The stream-ordered chain of one call, on torch's current stream."""
+        self._upload(nq)
+        self._device_chain(nq, k)
+        self._download(nq, k)
+
+    def _revalidate(self) -> bool:
+        """Under ``lock``: pick up the index's rows again when ``build`` / ``add`` /
+        ``load`` moved or grew them (the graphs hold stale pointers: dropped).
+        True when they were stale."""
+        idx = self.index
+        if self._generation == idx._generation:
+            return False
+        self._graphs.clear()
+        if idx._l2 or idx.dimension != self._h_q.shape[1] or idx.storage_dtype != self._d_q.dtype:
+            # a load changed what the buffers were sized and checked for
+            raise ValueError("the index changed its dimension, metric or storage dtype since this "
+                             "searcher was made: obtain a new one (index.online_searcher)")
+        self._rows = idx.index[: idx.current_size]
+        self._generation = idx._generation
+        return True
 
     def search(self, query_embeddings: Array, k: int) -> Tuple[np.ndarray, np.ndarray]:
         """(scores [nq, k] f32, positions [nq, k] int64, (-FLT_MAX, -1) padded) as
@@ -433,14 +465,7 @@ class OnlineSearcher:
         if t.shape[1] != idx.dimension:
             raise ValueError(f"expected dimension {idx.dimension}, got {t.shape[1]}")
         with self.lock:
-            if self._generation != idx._generation:  # the rows moved or grew: the graphs hold stale pointers
-                self._graphs.clear()
-                if idx._l2 or idx.dimension != self._h_q.shape[1] or idx.storage_dtype != self._d_q.dtype:
-                    # a load changed what the buffers were sized and checked for
-                    raise ValueError("the index changed its dimension, metric or storage dtype since this "
-                                     "searcher was made: obtain a new one (index.online_searcher)")
-                self._rows = idx.index[: idx.current_size]
-                self._generation = idx._generation
+            self._revalidate()
             self._h_q[:nq].copy_(t)
             key = (nq, k)
             stream = torch.cuda.current_stream(self._d_s.device)

@@ -15,14 +15,31 @@ Legs
                 top-K kernels alone (``kernel``: rt_flatip_topk; ``kernel_online``:
                 the rt_flatip_topk_online pair).
 
-Every leg is timed with ``online_max_batch`` off and on, alternating call by
-call in one process (two indexes over the same rows, so neither finds its
-corpus in the Infinity Cache). The ``on`` side of serve_q1_ref is also broken
-down into host copy / graph replay / synchronise.
+  embed_b1      one user row to its embedding on the host: ``get_user_embeddings(
+                ...).cpu().numpy()`` (``two_step``) against ``OnlineRecommender.embed``
+                (``recommender``); the reference publishes 0.059 ms.
+  serve_e2e     one user row to its lists at N = 1,000, d = 128, k = 50, cosine fp32:
+                ``get_user_embeddings`` -> ``.cpu().numpy()`` -> ``RetrievalEngine.
+                retrieve(use_cache=False)`` with ``online_max_batch = 8`` against
+                ``OnlineRecommender.recommend``; the reference publishes 0.101 ms.
+                Both legs run with the service-default tower (input 10) and with
+                the C2 user tower by id (``user_ids`` into a resident table), 3
+                rounds each way; ``bar``: the recommender's p50 of every round
+                against the two-step path's minimum p50 over its rounds.
+  tower_kernel  (not in the default list) rt_tower_infer_f32 launches alone at m = 1
+                and 8, for ``rocprofv3 --kernel-trace -- python tools/serve_latency.py
+                --legs tower_kernel --towers service``.
+
+The first two legs are timed with ``online_max_batch`` off and on, alternating
+call by call in one process (two indexes over the same rows, so neither finds
+its corpus in the Infinity Cache). The ``on`` side of serve_q1_ref and the
+recommender side of serve_e2e are also broken down into host copy / graph
+replay / synchronise / list building.
 
 ``--baseline`` uses only the API of the commit before the online path (no
-``online_max_batch``, no rt_flatip_topk_online), so the same tool measures an
-older build of the library: RTREC_HIP_LIB=<its librtrec_hip.so>.
+``online_max_batch``, no rt_flatip_topk_online, no OnlineRecommender: the new
+legs time their two-step side alone), so the same tool measures an older build
+of the library: RTREC_HIP_LIB=<its librtrec_hip.so>.
 
 Run it under a time limit, e.g. ``timeout 600 python tools/serve_latency.py``.
 """
@@ -175,20 +192,160 @@ def leg_corpus_1m(args):
     return out
 
 
+# (name, user-tower input width, hidden layers, served by id from a resident user table)
+TOWERS = (("service", 10, [512, 256, 128], False), ("c2_by_id", 3, [256, 128], True))
+N_USERS = 6040  # MovieLens-1M
+
+
+def _towers(args):
+    want = args.towers.split(",")
+    unknown = [t for t in want if t not in [x[0] for x in TOWERS]]
+    if unknown:
+        raise SystemExit(f"unknown tower {unknown}")
+    return [t for t in TOWERS if t[0] in want]
+
+
+def _request_setup(args, in_dim, hidden, by_id):
+    """Model, index and the two sides of one request at the reference's serving
+    shape (N = 1,000, d = 128, k = 50, cosine fp32): the two-step path of the
+    parent (get_user_embeddings -> .cpu().numpy() -> RetrievalEngine.retrieve,
+    online_max_batch = 8) and OnlineRecommender."""
+    from rtrec_amd.models.two_tower import ItemTower, TwoTowerModel, UserTower
+    n, d, k = 1000, 128, 50
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(0)
+    model = TwoTowerModel(UserTower(in_dim, d, hidden), ItemTower(20, d, [64], use_content_embedding=False))
+    model = model.to(dev).eval()
+    rng = np.random.default_rng(0)
+    x = rng.standard_normal((n, d)).astype(np.float32)
+    ids = [f"item_{i}" for i in range(n)]
+    feats = rng.standard_normal((N_USERS, in_dim)).astype(np.float32)
+    table = torch.from_numpy(feats).to(dev)
+    base = {"index_type": "hip_flat", "embedding_dim": d, "top_k": k}
+    eng = RetrievalEngine(dict(base) if args.baseline else dict(base, hip_flat={"online_max_batch": 8}))
+    eng.build_index(x, ids)
+    state = {"i": 0}
+
+    def user():
+        state["i"] += 1
+        return (state["i"] * 7919) % N_USERS
+
+    def two_step_embed():
+        u = user()
+        with torch.no_grad():
+            row = table[u:u + 1] if by_id else torch.from_numpy(feats[u:u + 1]).to(dev)
+            return model.get_user_embeddings({"numerical": row, "categorical": {}}).cpu().numpy()
+
+    def two_step_e2e():
+        return eng.retrieve(two_step_embed(), k=k, use_cache=False)
+
+    sides_embed, sides_e2e, rec = {"two_step": two_step_embed}, {"two_step": two_step_e2e}, None
+    if not args.baseline:
+        from rtrec_amd.serving.online import OnlineRecommender
+        eng2 = RetrievalEngine(dict(base))   # its own copy of the corpus, as in the other legs
+        eng2.build_index(x, ids)
+        rec = OnlineRecommender(model, eng2, max_batch=8, user_table=table if by_id else None)
+        if by_id:
+            sides_embed["recommender"] = lambda: rec.embed(user_ids=[user()])
+            sides_e2e["recommender"] = lambda: rec.recommend(user_ids=[user()], k=k)
+        else:
+            sides_embed["recommender"] = lambda: rec.embed(feats[user()])
+            sides_e2e["recommender"] = lambda: rec.recommend(feats[user()], k=k)
+    return sides_embed, sides_e2e, rec, feats, k
+
+
+def _rounds(sides, args):
+    """3 rounds each way (the order of the two sides within a call pair swapped),
+    alternating call by call; the bar: the recommender's p50 of every round is
+    below the two-step path's MINIMUM p50 over its rounds."""
+    out = []
+    for r in range(6):
+        order = list(sides) if r % 2 == 0 else list(sides)[::-1]
+        res = timed_alternating({name: sides[name] for name in order}, args.calls, args.warmup)
+        out.append({"first": order[0], **res})
+    verdict = None
+    if "recommender" in sides:
+        floor = min(r["two_step"]["p50_ms"] for r in out)
+        verdict = {"two_step_min_p50_ms": floor,
+                   "recommender_p50_ms": [r["recommender"]["p50_ms"] for r in out],
+                   "lower_in_every_round": all(r["recommender"]["p50_ms"] < floor for r in out)}
+    return {"rounds": out, "bar": verdict}
+
+
+def _breakdown(rec, feats, k, by_id, calls):
+    """OnlineRecommender.recommend at nq = 1 in pieces."""
+    from rtrec_amd.serving.retrieval import _lists_from_positions
+    s = rec._searcher
+    g = rec._graphs[(1, k, by_id)]
+    stream = torch.cuda.current_stream()
+    parts = {"host_copy": [], "graph_replay": [], "synchronise": [], "lists": []}
+    for i in range(calls):
+        u = (i * 7919) % N_USERS
+        t0 = time.perf_counter()
+        if by_id:
+            rec._h_ids_np[:1] = u
+        else:
+            rec._h_x[:1].copy_(torch.as_tensor(feats[u]).reshape(1, -1))
+        t1 = time.perf_counter()
+        g.replay()
+        t2 = time.perf_counter()
+        stream.synchronize()
+        t3 = time.perf_counter()
+        _lists_from_positions(s._h_s_np[:k].reshape(1, k), s._h_p_np[:k].reshape(1, k), rec.index.id_map, k, None)
+        t4 = time.perf_counter()
+        for name, dt in zip(parts, (t1 - t0, t2 - t1, t3 - t2, t4 - t3)):
+            parts[name].append(dt * 1e3)
+    return {name: pct(v) for name, v in parts.items()}
+
+
+def leg_embed_b1(args):
+    out = {"reference_ms": 0.059}
+    for name, in_dim, hidden, by_id in _towers(args):
+        sides, _, _, _, _ = _request_setup(args, in_dim, hidden, by_id)
+        out[name] = _rounds(sides, args)
+    return out
+
+
+def leg_serve_e2e(args):
+    out = {"reference_ms": 0.101}
+    for name, in_dim, hidden, by_id in _towers(args):
+        _, sides, rec, feats, k = _request_setup(args, in_dim, hidden, by_id)
+        out[name] = _rounds(sides, args)
+        if rec is not None:
+            out[name]["recommender_breakdown"] = _breakdown(rec, feats, k, by_id, args.calls)
+    return out
+
+
+def leg_tower_kernel(args):
+    """rt_tower_infer_f32 alone, for a kernel trace: both towers, m = 1 and 8."""
+    for name, in_dim, hidden, by_id in _towers(args):
+        _, _, rec, feats, _ = _request_setup(args, in_dim, hidden, by_id)
+        rec._d_ids.copy_(torch.arange(8, device=rec._d_ids.device))
+        rec._d_x.copy_(torch.from_numpy(feats[:8]))
+        for m in (1, 8):
+            for _ in range(args.calls):
+                rec._tower(m, by_id)
+            torch.cuda.synchronize()
+    return {"launches_per_tower_and_m": args.calls}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--baseline", action="store_true", help="only the API of the commit before the online path")
     ap.add_argument("--calls", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--rows", type=int, default=1_000_000, help="rows of the corpus_1m leg")
-    ap.add_argument("--legs", default="serve_q1_ref,corpus_1m")
+    ap.add_argument("--legs", default="serve_q1_ref,corpus_1m,embed_b1,serve_e2e")
+    ap.add_argument("--towers", default=",".join(t[0] for t in TOWERS),
+                    help="towers of the embed_b1 / serve_e2e / tower_kernel legs")
     args = ap.parse_args()
     if args.calls < 1:
         ap.error("--calls must be positive")
     torch.cuda.init()
     res = {"tool": "serve_latency", "baseline": bool(args.baseline), "calls": args.calls, "warmup": args.warmup,
            "lib": os.environ.get("RTREC_HIP_LIB", "in-tree"), "device": torch.cuda.get_device_name(0)}
-    legs = {"serve_q1_ref": leg_serve_q1_ref, "corpus_1m": leg_corpus_1m}
+    legs = {"serve_q1_ref": leg_serve_q1_ref, "corpus_1m": leg_corpus_1m, "embed_b1": leg_embed_b1,
+            "serve_e2e": leg_serve_e2e, "tower_kernel": leg_tower_kernel}
     for name in args.legs.split(","):
         if name not in legs:
             ap.error(f"unknown leg {name!r}")
