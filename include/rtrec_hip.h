@@ -66,6 +66,45 @@ int rt_scatter_add_rows_f32(float* grad_table, int64_t n_rows, int dim, const in
                             int64_t n_ids, const float* grad_out, int64_t padding_idx, void* stream);
 
 /* ------------------------------------------------------------------------
+ * In-place row overwrite and order-preserving row removal of a dense corpus.
+ * Replaces: FaissIndex.update / FaissIndex.remove, which on a Flat index only
+ * log "Flat index doesn't support direct updates / removal. Consider periodic
+ * rebuilds." (src/serving/retrieval.py:228-246), so that the streaming
+ * item_update path (RetrievalEngine.update_index, :629-641) appends a changed
+ * item a second time and a withdrawn item never leaves.
+ * Both: row_bytes % 16 == 0, row pointers 16-byte aligned (RT_ERR_INVALID
+ * otherwise; every stored row width of the index qualifies), row_bytes <= 2^24
+ * (RT_ERR_UNSUPPORTED above).
+ *
+ * rt_scatter_rows: dst[positions[i]] = src[i], i < n. A position outside
+ *   [0, dst_rows) is skipped and counted in *oob_count (may be NULL).
+ *   POSITIONS MUST BE UNIQUE (the caller guarantees it): two rows scattered to
+ *   one position leave that row a mix of both. n == 0: RT_OK, no launch.
+ *
+ * rt_rows_compact: stable stream compaction, out of place. Row r < n_rows is
+ *   kept iff bit r % 32 of keep_bits[r / 32] is set (bits of the last word
+ *   beyond n_rows are ignored). Kept rows land in dst[0 .. *n_kept) in source
+ *   order, as faiss.IndexFlat.remove_ids shifts later rows down; dst rows at
+ *   and beyond *n_kept are not written; src is not written. n_kept is a DEVICE
+ *   int64, always written (n_rows == 0 writes 0; with n_rows == 0 it may be
+ *   NULL and the call is then host-only). No host read: stream-ordered and
+ *   capturable. Two launches (segment offsets by one workgroup, then the move),
+ *   no cross-workgroup hand-off.
+ *   RT_ERR_INVALID: dst_rows < n_rows (the host side does not know the count,
+ *   so the safe bound is the contract); [src, src + n_rows*row_bytes) and
+ *   [dst, dst + dst_rows*row_bytes) overlapping; keep_words < ceil(n_rows/32);
+ *   workspace_bytes < rt_rows_compact_workspace_bytes(n_rows); a workspace
+ *   that is NULL or not 8-byte aligned.
+ * ------------------------------------------------------------------------ */
+int rt_scatter_rows(const void* src, int64_t n, int64_t row_bytes, const int64_t* positions,
+                    void* dst, int64_t dst_rows, int32_t* oob_count, void* stream);
+size_t rt_rows_compact_workspace_bytes(int64_t n_rows);
+int rt_rows_compact(const void* src, int64_t n_rows, int64_t row_bytes,
+                    const uint32_t* keep_bits, int64_t keep_words,
+                    void* dst, int64_t dst_rows, int64_t* n_kept,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * faiss.normalize_L2 (src/serving/retrieval.py:86,167,214), in place:
  * x[i] *= 1/sqrtf(sum_j x[i][j]^2) when the sum is > 0. The sum is a
  * sequential fmaf chain over j (the order oracle/flatip.c defines).

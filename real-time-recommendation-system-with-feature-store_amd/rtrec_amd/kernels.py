@@ -73,6 +73,64 @@ def scatter_add_rows(grad_table: torch.Tensor, ids: torch.Tensor, grad_out: torc
 
 
 # ---------------------------------------------------------------------------
+# in-place row overwrite / order-preserving removal (the Flat index's update and
+# remove, src/serving/retrieval.py:228-246)
+# ---------------------------------------------------------------------------
+
+def _row_bytes(t: torch.Tensor, what: str) -> int:
+    if t.dim() != 2 or not t.is_contiguous():
+        raise ValueError(f"{what} expects contiguous [rows, width] tensors")
+    nbytes = t.shape[1] * t.element_size()
+    if nbytes == 0 or nbytes % 16 or t.data_ptr() % 16:
+        raise ValueError(f"{what}: rows must be a multiple of 16 bytes and 16-byte aligned "
+                         f"(row of {nbytes} bytes at {t.data_ptr():#x})")
+    return nbytes
+
+
+def scatter_rows(src: torch.Tensor, positions: torch.Tensor, dst: torch.Tensor,
+                 oob: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``dst[positions[i]] = src[i]`` (rt_scatter_rows). Positions must be unique;
+    one outside ``[0, len(dst))`` is skipped and counted in ``oob`` (int32 [1]) if given."""
+    native.require_device(src, positions, dst, oob, what="scatter_rows")
+    row_bytes = _row_bytes(src, "scatter_rows")
+    if src.dtype != dst.dtype or _row_bytes(dst, "scatter_rows") != row_bytes:
+        raise ValueError(f"scatter_rows: src rows {tuple(src.shape)} {src.dtype} do not match dst "
+                         f"{tuple(dst.shape)} {dst.dtype}")
+    if positions.dtype != torch.int64 or positions.dim() != 1 or positions.numel() != src.shape[0]:
+        raise ValueError("scatter_rows: positions must be int64 [len(src)]")
+    positions = positions.contiguous()
+    call("rt_scatter_rows", ptr(src), src.shape[0], row_bytes, ptr(positions), ptr(dst), dst.shape[0], ptr(oob),
+         stream_of(dst))
+    return dst
+
+
+def rows_compact(src: torch.Tensor, keep_bits: torch.Tensor, dst: torch.Tensor,
+                 n_kept: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Stable compaction of the rows of ``src`` whose bit is set in ``keep_bits``
+    (int32/uint32 words, bit j of word w = row 32w + j) into ``dst[:n_kept]``
+    (rt_rows_compact; out of place, ``len(dst) >= len(src)``). Returns ``n_kept``,
+    a device int64 [1]; nothing is read back to the host."""
+    native.require_device(src, keep_bits, dst, n_kept, what="rows_compact")
+    row_bytes = _row_bytes(src, "rows_compact")
+    if src.dtype != dst.dtype or _row_bytes(dst, "rows_compact") != row_bytes:
+        raise ValueError(f"rows_compact: src rows {tuple(src.shape)} {src.dtype} do not match dst "
+                         f"{tuple(dst.shape)} {dst.dtype}")
+    if keep_bits.dtype not in (torch.int32, torch.uint32) or keep_bits.dim() != 1:
+        raise ValueError("rows_compact: keep_bits must be int32/uint32 [words]")
+    keep_bits = keep_bits.contiguous()
+    if n_kept is None:
+        n_kept = torch.empty(1, dtype=torch.int64, device=src.device)
+    elif n_kept.dtype != torch.int64 or n_kept.numel() != 1:
+        raise ValueError("rows_compact: n_kept must be int64 [1]")
+    n = src.shape[0]
+    ws = workspace(src.device, native.lib().rt_rows_compact_workspace_bytes(n), "rows_compact")
+    with TIMER.region("rows_compact", bytes_=float(2 * n * row_bytes)):
+        call("rt_rows_compact", ptr(src), n, row_bytes, ptr(keep_bits), keep_bits.numel(), ptr(dst), dst.shape[0],
+             ptr(n_kept), ptr(ws), ws.numel(), stream_of(src))
+    return n_kept
+
+
+# ---------------------------------------------------------------------------
 # Faiss normalize_L2 + IndexFlatIP search (src/serving/retrieval.py:86,167,171)
 # ---------------------------------------------------------------------------
 

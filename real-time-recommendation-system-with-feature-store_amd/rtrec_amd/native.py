@@ -105,6 +105,9 @@ SIGNATURES = {
     "rt_last_error": (ctypes.c_char_p, []),
     "rt_gather_rows": (c_int, [vp, c_i64, c_i64, c_i64, vp, c_i64, vp, vp, vp]),
     "rt_scatter_add_rows_f32": (c_int, [vp, c_i64, c_int, vp, c_i64, vp, c_i64, vp]),
+    "rt_scatter_rows": (c_int, [vp, c_i64, c_i64, vp, vp, c_i64, vp, vp]),
+    "rt_rows_compact_workspace_bytes": (c_size, [c_i64]),
+    "rt_rows_compact": (c_int, [vp, c_i64, c_i64, vp, c_i64, vp, c_i64, vp, vp, c_size, vp]),
     "rt_l2_renorm_f32": (c_int, [vp, c_i64, c_int, vp]),
     "rt_flatip_topk_workspace_bytes": (c_size, [c_i64, c_i64, c_int, c_int, c_int]),
     "rt_flatip_topk": (c_int, [vp, c_i64, vp, c_i64, c_int, c_int, c_int, vp, c_i64, c_i64, vp, vp, vp,

@@ -22,7 +22,7 @@ import torch.nn as nn
 
 from .. import kernels, native
 from ..models.fused import blocks_from_sequential
-from .retrieval import HipFlatIPIndex, OnlineSearcher, RetrievalEngine, _lists_from_positions
+from .retrieval import HipFlatIPIndex, OnlineSearcher, RetrievalEngine, _capture, _lists_from_positions
 
 Features = Union[np.ndarray, torch.Tensor, Dict[str, Any]]
 Rows = Union[np.ndarray, torch.Tensor]
@@ -256,7 +256,7 @@ class OnlineRecommender:
                 self._sequence(nq, k, by_ids)
                 stream.synchronize()
                 g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                with _capture(g):
                     self._sequence(nq, k, by_ids)
                 while len(self._graphs) >= self.MAX_GRAPHS:
                     self._graphs.popitem(last=False)

@@ -10,6 +10,8 @@ Flat-IP top-K kernel (MFMA scoring + wavefront select) instead of Faiss-CPU.
 """
 from __future__ import annotations
 
+import contextlib
+import gc
 import hashlib
 import json
 import os
@@ -113,6 +115,17 @@ class HipFlatIPIndex(IndexBase):
     d = 128, k = 100, float16 and float32, nq = 1 and 8.
     Larger calls take the default path. Inner-product metrics only: with the L2
     metric the option raises ``ValueError``.
+
+    ``mutable`` (default False: ``update`` and ``remove`` only warn, like the
+    reference's Flat index, retrieval.py:228-246). With it on, ``update`` is an
+    upsert — a known id's row is overwritten in place (``rt_scatter_rows``; no
+    pointer or size changes, so resident searchers keep their captured graphs
+    and see the new row at their next replay), an unknown id is appended
+    through ``add`` — and ``remove`` compacts the corpus in row order
+    (``rt_rows_compact``), as ``faiss.IndexFlat.remove_ids`` does: later rows
+    shift down, the corpus stays dense, and the index is indistinguishable
+    from one built on the surviving rows (stored bits, positions, the
+    lower-position-wins tie rule). Every metric and storage dtype.
     """
 
     def __init__(self, config: Optional[Dict[str, Any]] = None):
@@ -141,7 +154,8 @@ class HipFlatIPIndex(IndexBase):
         self.reverse_id_map: Dict[str, int] = {}
         self._ids: List[str] = []                  # position -> id (vectorised id_map)
         self.current_size = 0
-        self._generation = 0                       # bumped by build / add / load (OnlineSearcher validity)
+        self._generation = 0                       # bumped by build / add / load / remove (OnlineSearcher validity)
+        self.mutable = bool(self.config.get("mutable", False))
         self.online_max_batch = int(self.config.get("online_max_batch", 0) or 0)
         if not 0 <= self.online_max_batch <= OnlineSearcher.MAX_BATCH:
             raise ValueError(f"online_max_batch={self.online_max_batch}: 0 (off) or 1..{OnlineSearcher.MAX_BATCH}")
@@ -177,8 +191,19 @@ class HipFlatIPIndex(IndexBase):
         ([x, -||x||^2/2, 0, 0, 0], rt_l2_augment_f32)."""
         return self.dimension + 4 if self._l2 else self.dimension
 
-    def _store(self, rows: torch.Tensor):
+    def _to_storage(self, rows: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Prepared rows -> the rows as stored ([n, _row_width()] storage dtype):
+        the dtype cast, and ``l2_augment`` in the L2 mode. Per row, so a row's
+        stored bits do not depend on what it is stored with."""
         rows = rows.to(self.storage_dtype)
+        if self._l2:
+            return kernels.l2_augment(rows, 1, out=out)
+        if out is None:
+            return rows
+        out.copy_(rows)
+        return out
+
+    def _store(self, rows: torch.Tensor):
         n_new = self.current_size + rows.shape[0]
         if self.index is None or self.index.shape[0] < n_new:
             cap = max(n_new, 2 * (self.index.shape[0] if self.index is not None else 0), 1024)
@@ -186,10 +211,7 @@ class HipFlatIPIndex(IndexBase):
             if self.index is not None and self.current_size:
                 buf[: self.current_size].copy_(self.index[: self.current_size])
             self.index = buf
-        if self._l2:
-            kernels.l2_augment(rows, 1, out=self.index[self.current_size:n_new])
-        else:
-            self.index[self.current_size:n_new].copy_(rows)
+        self._to_storage(rows, out=self.index[self.current_size:n_new])
 
     # -- IndexBase ---------------------------------------------------------
     def build(self, embeddings: Array, ids: List[str]):
@@ -237,7 +259,7 @@ class HipFlatIPIndex(IndexBase):
         if self.index is None:
             raise ValueError("Index not built yet")
         k_search = min(k * 2, self.current_size) if filter_ids else k
-        if k_search <= 0:
+        if k_search <= 0 or (self.mutable and self.current_size == 0):  # emptied by remove: nothing to scan
             n = 1 if np.ndim(query_embeddings) == 1 else len(query_embeddings)
             return [[] for _ in range(n)], [[] for _ in range(n)]
         if self.online_max_batch and not self._l2 and k_search <= OnlineSearcher.MAX_K:
@@ -255,7 +277,10 @@ class HipFlatIPIndex(IndexBase):
         """retrieval.py:199-226: incremental append (Kafka item_update path)."""
         if self.index is None:
             raise ValueError("Index not built yet")
-        rows = self._prepare(embeddings)
+        self._append(self._prepare(embeddings), ids)
+
+    def _append(self, rows: torch.Tensor, ids: List[str]):
+        """Append prepared rows and their ids (``add``; the unknown ids of ``update``)."""
         self._store(rows)
         for i, item_id in enumerate(ids):
             new_idx = self.current_size + i
@@ -266,12 +291,92 @@ class HipFlatIPIndex(IndexBase):
         self._generation += 1
         logger.info("Added %d items to index. Total size: %d", rows.shape[0], self.current_size)
 
-    def update(self, embeddings: Array, ids: List[str]):
-        """retrieval.py:228-237 (no-op with a warning, like the reference)."""
-        logger.warning("Flat index doesn't support direct updates. Consider periodic rebuilds.")
+    def _searcher_lock(self):
+        """The resident searcher's lock when the index holds one: its replays read the rows."""
+        return self._online.lock if self._online is not None else contextlib.nullcontext()
 
-    def remove(self, ids: List[str]):
-        logger.warning("Flat index doesn't support removal. Consider periodic rebuilds.")
+    def update(self, embeddings: Array, ids: List[str]):
+        """retrieval.py:228-237: a no-op with a warning, like the reference, unless
+        the index is ``mutable``. Then an upsert: rows are prepared and stored as
+        ``build`` would store them; a known id's row is overwritten in place (the
+        last occurrence of an id given more than once wins; an id stored twice
+        through ``add`` has its last row overwritten, the one ``reverse_id_map``
+        names) without a generation bump — no pointer or size changes, captured
+        graphs of resident searchers stay valid; unknown ids are appended as by
+        ``add``, in call order."""
+        if not self.mutable:
+            logger.warning("Flat index doesn't support direct updates. Consider periodic rebuilds.")
+            return
+        if self.index is None:
+            raise ValueError("Index not built yet")
+        ids = list(ids)
+        rows = self._prepare(embeddings)
+        if rows.shape[0] != len(ids):
+            raise ValueError(f"{rows.shape[0]} embeddings for {len(ids)} ids")
+        known: Dict[str, int] = {}     # id -> its last row in the call (positions stay unique)
+        unknown: Dict[str, int] = {}   # in order of first appearance, the last row wins too
+        for i, item_id in enumerate(ids):
+            (known if item_id in self.reverse_id_map else unknown)[item_id] = i
+        if known:
+            take = torch.tensor(list(known.values()), dtype=torch.int64, device=rows.device)
+            pos = torch.tensor([self.reverse_id_map[i] for i in known], dtype=torch.int64, device=rows.device)
+            new_rows = self._to_storage(rows[take])
+            with self._searcher_lock():
+                kernels.scatter_rows(new_rows, pos, self.index)
+        if unknown:
+            take = torch.tensor(list(unknown.values()), dtype=torch.int64, device=rows.device)
+            self._append(rows[take], list(unknown))
+        logger.info("Updated %d items in place, appended %d. Total size: %d", len(known), len(unknown),
+                    self.current_size)
+
+    def remove(self, ids: List[str]) -> Optional[int]:
+        """retrieval.py:239-246: a no-op with a warning, like the reference, unless
+        the index is ``mutable``. Then every row stored under one of ``ids`` leaves
+        and later rows shift down in order (``faiss.IndexFlat.remove_ids``);
+        unknown ids are ignored. Returns the number of rows removed."""
+        if not self.mutable:
+            logger.warning("Flat index doesn't support removal. Consider periodic rebuilds.")
+            return None
+        if self.index is None:
+            raise ValueError("Index not built yet")
+        hit = {i for i in ids if i in self.reverse_id_map}
+        if not hit:
+            return 0
+        n = self.current_size
+        keep = np.ones(n, dtype=bool)
+        keep[[self.reverse_id_map[i] for i in hit]] = False
+        unnamed = self._ids.count(None)
+        if n - unnamed != len(self.reverse_id_map):
+            # an id stored more than once through add: every one of its rows goes
+            keep[[p for p, i in enumerate(self._ids) if i in hit]] = False
+        # bit j of word w = row 32w + j (little-endian bytes of little-endian words)
+        bits = np.packbits(keep, bitorder="little")
+        words = np.zeros(-(-n // 32), dtype="<u4")
+        words.view(np.uint8)[: bits.size] = bits
+        d_bits = torch.from_numpy(words.view(np.int32)).to(self._dev())
+        buf = torch.empty_like(self.index)  # the old capacity
+        # the O(N) host side: the surviving ids as the runs between removed rows (list
+        # slices, not a per-row loop), then both maps in ascending position — the last
+        # row of an id names it, as add leaves it
+        old_ids, new_ids, a = self._ids, [], 0
+        for r in np.flatnonzero(~keep).tolist():
+            new_ids.extend(old_ids[a:r])
+            a = r + 1
+        new_ids.extend(old_ids[a:])
+        if unnamed:
+            id_map = {p: i for p, i in enumerate(new_ids) if i is not None}
+            reverse_id_map = {i: p for p, i in id_map.items()}
+        else:
+            id_map = dict(enumerate(new_ids))
+            reverse_id_map = dict(zip(new_ids, range(len(new_ids))))
+        with self._searcher_lock():
+            kernels.rows_compact(self.index[:n], d_bits, buf)
+            self.index = buf
+            self.current_size = len(new_ids)    # the host's own count: no device read
+            self._ids, self.id_map, self.reverse_id_map = new_ids, id_map, reverse_id_map
+            self._generation += 1               # the rows moved: resident searchers drop their graphs
+        logger.info("Removed %d items from index. Total size: %d", n - self.current_size, self.current_size)
+        return n - self.current_size
 
     def vectors(self) -> np.ndarray:
         if self.index is None:
@@ -302,6 +407,7 @@ class HipFlatIPIndex(IndexBase):
         self.config = data.get("config", self.config)
         self.metric = self.config.get("metric", self.metric)
         self._l2 = self.metric not in ("cosine", "inner_product")
+        self.mutable = bool(self.config.get("mutable", False))
         self.dimension = vecs.shape[1]
         self.index = None
         self.current_size = 0
@@ -343,6 +449,26 @@ def read_flat_index(path: Path) -> Tuple[np.ndarray, bool]:
     return vecs, four == _FOURCC_IP
 
 
+@contextlib.contextmanager
+def _capture(graph: "torch.cuda.CUDAGraph"):
+    """``torch.cuda.graph(graph, capture_error_mode="thread_local")`` with the
+    cyclic garbage collector paused. A collection that starts inside the
+    capture may finalise a dead cycle that holds device objects — a dropped
+    index and its resident searcher refer to each other, with pinned buffers
+    and captured graphs — and freeing those is not a capturable call: the
+    process aborts. torch does not collect before a capture
+    (``torch.compiler.config.force_cudagraph_gc`` is off by default), so such a
+    cycle simply waits for the first collection after the capture."""
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+            yield
+    finally:
+        if was_enabled:
+            gc.enable()
+
+
 class OnlineSearcher:
     """Resident small-batch searcher over one :class:`HipFlatIPIndex`
     (``index.online_searcher(max_batch)``): the per-request shape of the
@@ -363,8 +489,10 @@ class OnlineSearcher:
     torch allocation.
 
     The searcher holds the index's row pointer and size: ``build`` / ``add`` /
-    ``load`` bump the index's generation, and a searcher that finds its
-    generation stale drops its graphs and captures again.
+    ``load`` / ``remove`` bump the index's generation, and a searcher that finds
+    its generation stale drops its graphs and captures again. An in-place
+    ``update`` of a ``mutable`` index moves nothing and bumps nothing: the
+    graphs stay and read the new row at their next replay.
 
     Thread safety: calls are serialised by ``lock`` (re-entrant). ``search``
     returns views of the searcher's own host buffers, valid until the next
@@ -484,7 +612,7 @@ class OnlineSearcher:
                     g = torch.cuda.CUDAGraph()
                     # thread_local: CUDA work of other threads (an allocation, a default-path
                     # search) during the capture neither enters it nor invalidates it
-                    with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                    with _capture(g):
                         self._sequence(nq, k)
                     while len(self._graphs) >= self.MAX_GRAPHS:
                         self._graphs.popitem(last=False)
@@ -531,7 +659,10 @@ class HipShardedFlatIPIndex(IndexBase):
 
     Config keys: those of :class:`HipFlatIPIndex` for the inner-product
     metrics ("cosine", "inner_product"), plus ``process_group`` (default: the
-    default group; world 1 without one) and ``query_tile``.
+    default group; world 1 without one) and ``query_tile``. The ``mutable``
+    option of :class:`HipFlatIPIndex` is not served here yet: ``update`` and
+    ``remove`` keep the reference's warning stubs (a cross-rank compaction has
+    to re-balance the shards).
     """
 
     MAX_K = 512  # rt_topk_merge: k_out <= 512
@@ -937,9 +1068,23 @@ class RetrievalEngine:
                    "avg_score": float(np.mean(flat)) if flat else float("nan")}
         return item_ids, scores, metrics
 
-    def update_index(self, new_embeddings: Array, new_ids: List[str]):
-        self.index.add(new_embeddings, new_ids)
+    def update_index(self, new_embeddings: Array, new_ids: List[str], upsert: bool = False):
+        """retrieval.py:629-641 appends (``index.add``): an item whose embedding
+        changed is then stored twice. ``upsert=True`` calls ``index.update``
+        instead (a ``mutable`` index overwrites known ids in place and appends
+        the rest)."""
+        if upsert:
+            self.index.update(new_embeddings, new_ids)
+        else:
+            self.index.add(new_embeddings, new_ids)
         self.cache.clear()
+
+    def remove_items(self, ids: List[str]) -> Optional[int]:
+        """Withdraw items (``index.remove``; a ``mutable`` index returns the number
+        of rows removed)."""
+        removed = self.index.remove(ids)
+        self.cache.clear()
+        return removed
 
     def _clear_expired_cache(self):
         now = time.time()

@@ -30,6 +30,18 @@ Legs
                 and 8, for ``rocprofv3 --kernel-trace -- python tools/serve_latency.py
                 --legs tower_kernel --towers service``.
 
+  mutate        (not in the default list) N = 1,000,000, d = 128, cosine, float16 and
+                float32, ``mutable: True``: ``update`` of 1 and of 64 rows, ``remove``
+                of 1 and of 1,000 ids (the corpus restored between calls, outside
+                the timing) against ``index.build`` on the device-resident surviving
+                rows with their ids — all an index without the option offers. The
+                sides alternate call by call, 3 rounds each way, ``--mutate-calls``
+                calls per case and round; ``bar``: the p50 of every case in every
+                round against the build's minimum p50 over its rounds. Also the
+                compaction alone by hipEvent pairs ((bytes read + written) / time
+                as a fraction of 8 TB/s) and the host bookkeeping of ``remove``
+                (the call minus its device work).
+
 The first two legs are timed with ``online_max_batch`` off and on, alternating
 call by call in one process (two indexes over the same rows, so neither finds
 its corpus in the Infinity Cache). The ``on`` side of serve_q1_ref and the
@@ -329,12 +341,113 @@ def leg_tower_kernel(args):
     return {"launches_per_tower_and_m": args.calls}
 
 
+def leg_mutate(args):
+    """``update`` / ``remove`` of a ``mutable`` index at N = ``--rows``, d = 128,
+    cosine, against the only thing an index without the option offers:
+    ``index.build`` on the device-resident surviving rows with their ids."""
+    n, d = args.rows, 128
+    calls = max(1, args.mutate_calls)
+    out = {"calls_per_round": calls}
+    ids = [str(i) for i in range(n)]
+    rng = np.random.default_rng(3)
+    pick = {m: rng.choice(n, m, replace=False) for m in (1, 64, 1000)}
+    for storage in ("float16", "float32"):
+        g = torch.Generator(device="cuda").manual_seed(1)
+        x = torch.randn((n, d), generator=g, device="cuda")
+        new = {m: torch.randn((2, m, d), generator=g, device="cuda") for m in (1, 64)}
+        cfg = {"dimension": d, "metric": "cosine", "storage_dtype": storage}
+        ix = HipFlatIPIndex(dict(cfg, mutable=True))
+        ix.build(x, ids)
+        # the parent's side: a build on the surviving rows of the largest removal (the
+        # fewest rows any case leaves it: the cheapest build) — rows and ids made outside the timing
+        gone = np.zeros(n, dtype=bool)
+        gone[pick[1000]] = True
+        x_surv = x[torch.from_numpy(~gone).cuda()].contiguous()
+        ids_surv = [i for i, dead in zip(ids, gone.tolist()) if not dead]
+        rebuilt = HipFlatIPIndex(dict(cfg))
+        snap = (ix.index, ix._ids, ix.id_map, ix.reverse_id_map, ix.current_size)
+        state = {"i": 0}
+
+        def restore():
+            # remove is out of place and builds new id structures: the old ones are intact
+            ix.index, ix._ids, ix.id_map, ix.reverse_id_map, ix.current_size = snap
+            ix._generation += 1
+
+        def update(m):
+            upd_ids = [ids[p] for p in pick[m]]
+
+            def f():
+                state["i"] += 1
+                ix.update(new[m][state["i"] % 2], upd_ids)   # other values every call; nothing to restore
+                torch.cuda.synchronize()
+            return f
+
+        def remove(m):
+            rm_ids = [ids[p] for p in pick[m]]
+
+            def f():
+                ix.remove(rm_ids)
+                torch.cuda.synchronize()
+            return f
+
+        def build():
+            rebuilt.build(x_surv, ids_surv)
+            torch.cuda.synchronize()
+
+        sides = {"update_1": update(1), "update_64": update(64), "remove_1": remove(1), "remove_1000": remove(1000),
+                 "build": build}
+        for f in sides.values():   # warm: kernels loaded, buffers of the allocator sized
+            f()
+            restore()
+        rounds = []
+        for r in range(6):  # 3 rounds each way: the parent's build last, then first
+            order = list(sides) if r % 2 == 0 else ["build"] + [s for s in sides if s != "build"]
+            samples = {name: [] for name in sides}
+            for _ in range(calls):
+                for name in order:
+                    t0 = time.perf_counter()
+                    sides[name]()
+                    samples[name].append((time.perf_counter() - t0) * 1e3)
+                    if name.startswith("remove"):
+                        restore()   # outside the timed region
+            rounds.append({"first": order[0], **{name: pct(v) for name, v in samples.items()}})
+        floor = min(r["build"]["p50_ms"] for r in rounds)
+        bar = {"build_min_p50_ms": floor}
+        for name in sides:
+            if name != "build":
+                p50s = [r[name]["p50_ms"] for r in rounds]
+                bar[name] = {"p50_ms": p50s, "lower_in_every_round": all(p < floor for p in p50s)}
+        # the compaction alone (hipEvent pairs): offsets + move launches on the index's rows
+        rows = ix.index[:n]
+        dst = torch.empty_like(rows)
+        dev = {}
+        for m in (1, 1000):
+            keep = np.ones(-(-n // 32) * 32, dtype=bool)
+            keep[pick[m]] = False
+            bits = torch.from_numpy(np.packbits(keep, bitorder="little").view("<u4").view(np.int32).copy()).cuda()
+            t = event_timed_alternating({"compact": lambda bits=bits: kernels.rows_compact(rows, bits, dst)}, 50, 5)
+            moved = (2 * n - m) * rows.shape[1] * rows.element_size()   # bytes read + bytes written
+            t["compact"]["bytes_moved"] = moved
+            t["compact"]["fraction_of_8TBps"] = round(moved / (t["compact"]["p50_ms"] * 1e-3) / 8e12, 4)
+            dev[f"remove_{m}"] = t["compact"]
+        # host bookkeeping of remove = the call minus its device work (the launches come
+        # last in remove, after the id structures are rebuilt, so the two add up)
+        host = {name: round(min(r[name]["p50_ms"] for r in rounds) - dev[name]["p50_ms"], 5) for name in dev}
+        out[storage] = {"rounds": rounds, "bar": bar, "compaction_device": dev, "remove_host_ms": host,
+                        "c5_gather_yardstick_fraction_of_8TBps": [0.72, 0.77]}
+        del ix, rebuilt, x, x_surv, rows, dst, snap
+        torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--baseline", action="store_true", help="only the API of the commit before the online path")
     ap.add_argument("--calls", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=50)
-    ap.add_argument("--rows", type=int, default=1_000_000, help="rows of the corpus_1m leg")
+    ap.add_argument("--rows", type=int, default=1_000_000, help="rows of the corpus_1m and mutate legs")
+    ap.add_argument("--mutate-calls", type=int, default=3,
+                    help="timed calls per case and round of the mutate leg (a call at 10^6 rows is O(N) host work)")
     ap.add_argument("--legs", default="serve_q1_ref,corpus_1m,embed_b1,serve_e2e")
     ap.add_argument("--towers", default=",".join(t[0] for t in TOWERS),
                     help="towers of the embed_b1 / serve_e2e / tower_kernel legs")
@@ -345,7 +458,7 @@ def main():
     res = {"tool": "serve_latency", "baseline": bool(args.baseline), "calls": args.calls, "warmup": args.warmup,
            "lib": os.environ.get("RTREC_HIP_LIB", "in-tree"), "device": torch.cuda.get_device_name(0)}
     legs = {"serve_q1_ref": leg_serve_q1_ref, "corpus_1m": leg_corpus_1m, "embed_b1": leg_embed_b1,
-            "serve_e2e": leg_serve_e2e, "tower_kernel": leg_tower_kernel}
+            "serve_e2e": leg_serve_e2e, "tower_kernel": leg_tower_kernel, "mutate": leg_mutate}
     for name in args.legs.split(","):
         if name not in legs:
             ap.error(f"unknown leg {name!r}")
