@@ -562,6 +562,10 @@ int rt_similarity_f32(const float* u, const float* v, int64_t b, int d, float in
  *   from `step` / `lr`. The grads are CONSUMED: every element is zeroed after
  *   use, and zero_buf[0, zero_words) (fp64, may be NULL) is zeroed too — the
  *   next step's accumulators start at zero without memset launches.
+ *   zero_buf must not overlap sumsq (blocks read sumsq while others already zero).
+ *   n == 0 returns before any launch: zero_buf is NOT zeroed then.
+ *   A NaN in sumsq makes coef NaN (as torch.clamp(max=1) keeps it): all of
+ *   params / exp_avg / exp_avg_sq become NaN.
  * rt_grad_sqnorm_fold: rt_grad_sqnorm that first folds row-split partial sums
  *   (rt_linear_bwd_args.dw_part of rt_linear_bwd_dw_f32_joint) into the tensors
  *   the n_folds <= RT_GRAD_FOLD_MAX descriptors name (host array, copied at the

@@ -130,16 +130,16 @@ def in_batch_negative_loss(u: torch.Tensor, i: torch.Tensor, temperature: float)
 
 def param_names(user_state: Dict[str, torch.Tensor], item_state: Dict[str, torch.Tensor],
                 use_bias: bool = True) -> List[str]:
-    """Order of ``model.parameters()`` for a reference TwoTowerModel:
-    user_tower params, item_tower params, user_bias, item_bias."""
+    """Order of ``model.parameters()`` for a reference TwoTowerModel (the order
+    of ``torch.optim.Adam.state_dict()["state"]``): user_bias, item_bias — a
+    module's own parameters come before its children's, whatever the order of
+    assignment in ``__init__`` — then user_tower params, item_tower params."""
     def tower(prefix, st):
         return [f"{prefix}.{k}" for k in st
                 if not (k.endswith("running_mean") or k.endswith("running_var")
                         or k.endswith("num_batches_tracked"))]
-    names = tower("user_tower", user_state) + tower("item_tower", item_state)
-    if use_bias:
-        names += ["user_bias", "item_bias"]
-    return names
+    names = ["user_bias", "item_bias"] if use_bias else []
+    return names + tower("user_tower", user_state) + tower("item_tower", item_state)
 
 
 def adam_update(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, step: int,

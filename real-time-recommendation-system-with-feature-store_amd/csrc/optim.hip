@@ -143,7 +143,7 @@ __global__ __launch_bounds__(256) void clip_adam_kernel(float* __restrict__ p, f
         if (threadIdx.x == 0) {
             const float total = static_cast<float>(sqrt(tot));
             const float coef = max_norm / (total + 1e-6f);
-            coef_s = coef < 1.f ? coef : 1.f;
+            coef_s = coef > 1.f ? 1.f : coef;  // torch.clamp(max=1): a NaN norm stays NaN
             const int st = step_dev ? *step_dev : step;
             const float lr_v = lr_dev ? *lr_dev : lr;
             const double bc1 = 1.0 - pow(static_cast<double>(b1), st);
