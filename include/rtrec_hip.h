@@ -158,6 +158,42 @@ int rt_flatip_topk_online(const void* queries, int64_t nq, const void* items, in
                           float* out_scores, int64_t* out_ids, void* workspace, size_t workspace_bytes,
                           void* stream);
 
+/* Online search with exclusion LISTS: rt_flatip_topk_online with the dense
+ * bitmap replaced by up to RT_ONLINE_MAX_EXCL_SOURCES CSR sources that the
+ * scan reads itself (the request schema's exclude_items, src/api/schemas.py:
+ * 31-34, and the evaluator's per-user train items, src/evaluation/metrics.py:
+ * 252-282, for the serving path): no bitmap in HBM, no launch to fill one.
+ *   A source: device CSR `offsets` [n_rows + 1] / `items`; query q uses CSR row
+ *   rows ? rows[q] : q (`rows`: device, [nq]); a row outside [0, n_rows) = no
+ *   exclusions — the row convention of rt_exclusion_bitmap. Items are LOCAL
+ *   corpus positions (before id_offset, as bit j of the bitmap is), ascending
+ *   within a CSR row; duplicates are allowed, items >= nx are ignored. A row
+ *   that does not ascend gives unspecified exclusions for that query, nothing
+ *   worse. Query q skips the union of its rows in all sources. Any list
+ *   length: a list may exclude every row (then every slot is (-FLT_MAX, -1)).
+ *   n_lists == 0: rt_flatip_topk_online without a bitmap, bit for bit.
+ *   Result rows, workspace (rt_flatip_topk_online_workspace_bytes) and plan
+ *   (rt_flatip_topk_online_plan) are rt_flatip_topk_online's.
+ *   Status, before any device work: RT_ERR_INVALID for n_lists < 0, lists ==
+ *   NULL with n_lists > 0, a source with offsets == NULL, n_rows < 0, or items
+ *   == NULL with n_rows > 0; RT_ERR_UNSUPPORTED for n_lists >
+ *   RT_ONLINE_MAX_EXCL_SOURCES; then every refusal of rt_flatip_topk_online.
+ *   The batch kernel rt_flatip_topk keeps the bitmap operand. */
+typedef struct {
+    const int64_t* offsets;   /* CSR offsets [n_rows + 1]                                  */
+    const int32_t* items;     /* corpus positions, ascending within a CSR row;             */
+                              /* duplicates allowed; entries >= nx are ignored              */
+    int64_t        n_rows;
+    const int64_t* rows;      /* optional [nq]: query q uses CSR row rows[q] (NULL: row q); */
+                              /* a row outside [0, n_rows) = no exclusions                  */
+} RtExclusionLists;
+
+#define RT_ONLINE_MAX_EXCL_SOURCES 2
+int rt_flatip_topk_online_lists(const void* queries, int64_t nq, const void* items, int64_t nx, int d, int dtype,
+                                int k, const RtExclusionLists* lists, int n_lists, int64_t id_offset,
+                                float* out_scores, int64_t* out_ids, void* workspace, size_t workspace_bytes,
+                                void* stream);
+
 /* Corpus-sharded search with ONE corpus-wide threshold per query (several
  * GPUs, each holding a row shard of the corpus that faiss.IndexFlatIP.search
  * would scan whole, src/serving/retrieval.py:141-197): every rank samples its

@@ -31,6 +31,12 @@
 //        and query, positions by ballot); before a tile, a buffer above kRoom
 //        (decided through the barrier that ended the tile before) is
 //        compacted by the v4 radix compaction (threshold raised, never lowered).
+//      * exclusions: a dense bitmap read per lane in the selection
+//        (rt_flatip_topk_online), or CSR lists that the scan reads itself
+//        (rt_flatip_topk_online_lists, the LISTS instantiation): cursors per
+//        (query, source) in LDS, a 256-bit window per query built one tile
+//        ahead, one wave-uniform LDS read per query in the selection. An
+//        excluded row is never appended: nothing below changes.
 //      * the block then writes each query's best min(k, rows) entries, sorted,
 //        as composite keys (score key << 32 | ~id; 0 = none) to
 //        partials[query][rank][block] — rank-major, so that the finish reads
@@ -74,15 +80,149 @@ static_assert(kRoom + kTileRows <= kCap, "online: a buffer at kRoom overflows be
 static_assert(kRoom >= kMaxK, "online: a compaction must be able to keep the k best");
 static_assert(kMaxK <= v4::kFinishCap, "online: the block's list is sorted by the 128-entry register sort");
 
-template <int NQ>
+// Exclusion lists (rt_flatip_topk_online_lists): up to kMaxSrc CSR sources per
+// call, query q skipping the union of its rows. The scan keeps, per (query,
+// source), a cursor into the source's items; the (query, row) test of the
+// selection reads a per-tile WINDOW of 256 bits per query in LDS, built one
+// tile ahead from the cursors — never global memory.
+constexpr int kMaxSrc = 2;  // RT_ONLINE_MAX_EXCL_SOURCES
+constexpr int kWinWords = kTileRows / 32;
+
+struct ListSrc {
+    const int64_t* offsets;
+    const int32_t* items;
+    const int64_t* rows;
+    int64_t n_rows;
+};
+template <bool LISTS>
+struct ListArgs {};
+template <>
+struct ListArgs<true> {
+    ListSrc src[kMaxSrc];
+    int n;
+};
+
+template <int NQ, bool LISTS = false>
 struct Lds {
     static constexpr int kStage = kWavesS * kStageBytes;
     static constexpr int kCand = NQ * kCap * static_cast<int>(sizeof(Cand));
     static constexpr int kQuery = NQ * 256 * 4;  // fp32 queries, d <= 256
     static constexpr int kHist = kWavesS * 256 * 4;
-    static constexpr int kBytes = kStage + kCand + kQuery + kHist;
+    // lists: cursor + end (int64) and next item (int32) per (query, source); two windows
+    static constexpr int kPairs = NQ * kMaxSrc;
+    static constexpr int kLists = LISTS ? kPairs * (8 + 8 + 4) + 2 * NQ * kWinWords * 4 : 0;
+    static constexpr int kBytes = kStage + kCand + kQuery + kHist + kLists;
+    static_assert(kLists % 8 == 0, "online: the list state holds 8-byte words");
     static_assert(2 * (kBytes + 128) <= 163840, "online: two blocks per CU");
 };
+
+// The list state of one block in LDS. Query qi is OWNED by wave qi % kWavesS:
+// only that wave reads or writes the query's cursors, and only it writes the
+// query's windows; the other waves read a window after a block barrier.
+struct ListState {
+    int64_t* cur;    // [pairs] index of the first item not yet consumed
+    int64_t* end;    // [pairs] end of the CSR row
+    int32_t* next;   // [pairs] items[cur] (a hint: INT32_MAX when the row is consumed)
+    uint32_t* win;   // [2][NQ][kWinWords]: bit r of window t & 1 = row r of tile t is excluded
+};
+
+// Prologue, per wave: 16-lane group g serves (query wave + 4 (g >> 1), source
+// g & 1): the CSR row's range, then the first item >= row_begin by a 17-ary
+// search (one probe per lane and round: 166 items take two dependent loads).
+template <int NQ>
+__device__ __forceinline__ void lists_begin(const ListArgs<true>& la, const ListState& ls, int nq, int64_t row_begin) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int g = lane >> 4, gl = lane & 15;
+    const int qi = wave + kWavesS * (g >> 1), s = g & 1;
+    const bool mine = qi < nq && qi < NQ && s < la.n;
+    const int64_t* offsets = s ? la.src[1].offsets : la.src[0].offsets;
+    const int32_t* items = s ? la.src[1].items : la.src[0].items;
+    const int64_t* rows = s ? la.src[1].rows : la.src[0].rows;
+    const int64_t n_rows = s ? la.src[1].n_rows : la.src[0].n_rows;
+    int64_t lo = 0, hi = 0;
+    if (mine) {
+        const int64_t r = rows ? rows[qi] : static_cast<int64_t>(qi);
+        if (r >= 0 && r < n_rows) {
+            lo = offsets[r];
+            hi = offsets[r + 1];
+            if (hi < lo) hi = lo;
+        }
+    }
+    const int64_t row_last = hi;
+    // invariant: every item before lo is < row_begin; the item at hi (or none) is not
+    bool act = hi > lo;
+    while (__any(act)) {
+        const int64_t step = (hi - lo + 15) >> 4;
+        const int64_t idx = lo + (gl + 1) * step - 1;
+        const bool in = act && idx < hi;
+        const int32_t v = in ? items[idx] : 0;
+        const uint64_t bm = __ballot(in && static_cast<int64_t>(v) < row_begin);
+        const int c = __popc(static_cast<uint32_t>(bm >> (g * 16)) & 0xFFFFu);
+        if (act) {
+            const int64_t a = lo + c * step, b = lo + (c + 1) * step - 1;
+            lo = a < hi ? a : hi;
+            hi = b < hi ? b : hi;
+            act = hi > lo;
+        }
+    }
+    if (qi < NQ && s < kMaxSrc && gl == 0) {
+        const int p = qi * kMaxSrc + s;
+        ls.cur[p] = lo;
+        ls.end[p] = row_last;
+        ls.next[p] = (mine && lo < row_last) ? items[lo] : INT32_MAX;
+    }
+}
+
+// Window of tile tt for the queries this wave owns: the items of every source
+// in [tile_lo, tile_hi), consumed from the cursors. A row's items ascend, so
+// they are a run from the cursor; a lane takes one item per round, a round
+// consumes up to 64, and a run of any length is consumed in further rounds.
+// `next` keeps the common case — no item of the row in this tile — free of
+// any global load. Bits are set only for tile_lo <= item < tile_hi: a row that
+// does not ascend excludes the wrong rows, but writes inside its window.
+template <int NQ>
+__device__ __forceinline__ void lists_window(const ListArgs<true>& la, const ListState& ls, int nq, int tt,
+                                             int64_t row_begin, int64_t row_end) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t tile_lo = row_begin + static_cast<int64_t>(tt) * kTileRows;
+    const int64_t tile_hi = (tile_lo + kTileRows) < row_end ? (tile_lo + kTileRows) : row_end;
+    for (int qi = wave; qi < nq && qi < NQ; qi += kWavesS) {
+        uint32_t* const w = ls.win + ((tt & 1) * NQ + qi) * kWinWords;
+        if (lane < kWinWords) w[lane] = 0u;
+        wave_lds_sync();
+#pragma unroll
+        for (int s = 0; s < kMaxSrc; ++s) {
+            if (s >= la.n) break;  // block-uniform
+            const int p = qi * kMaxSrc + s;
+            if (static_cast<int64_t>(ls.next[p]) >= tile_hi) continue;  // wave-uniform
+            const int32_t* items = la.src[s].items;
+            int64_t c = ls.cur[p];
+            const int64_t e = ls.end[p];
+            int32_t nv = INT32_MAX;
+            for (;;) {
+                const int64_t idx = c + lane;
+                const int32_t v = idx < e ? items[idx] : INT32_MAX;
+                const bool take = static_cast<int64_t>(v) < tile_hi;  // INT32_MAX: only when idx < e
+                if (take && idx < e && v >= tile_lo) {
+                    const uint32_t r = static_cast<uint32_t>(v - tile_lo);
+                    atomicOr(&w[r >> 5], 1u << (r & 31u));
+                }
+                const int adv = __popcll(__ballot(take && idx < e));
+                c += adv;
+                if (adv < 64) {
+                    nv = __shfl(v, adv, 64);  // the first item not consumed (INT32_MAX: none)
+                    break;
+                }
+            }
+            wave_lds_sync();
+            if (lane == 0) {
+                ls.cur[p] = c;
+                ls.next[p] = nv;
+            }
+        }
+        wave_lds_sync();
+    }
+}
 
 __device__ __forceinline__ void widen(const uint4& v, float (&x)[4], float) {
     x[0] = __uint_as_float(v.x); x[1] = __uint_as_float(v.y);
@@ -105,13 +245,15 @@ __device__ __forceinline__ void widen(const uint4& v, float (&x)[8], __hip_bfloa
     }
 }
 
-template <typename T, int NQ>
+// LISTS: the exclusions are `la`'s CSR lists (excl is not read); otherwise the
+// optional dense bitmap `excl`.
+template <typename T, int NQ, bool LISTS>
 __global__ __launch_bounds__(kThreads, 2) void flatip_online_scan(
     const T* __restrict__ Q, int nq, const char* __restrict__ X, int64_t nx, int d, int k,
     const uint32_t* __restrict__ excl, int64_t excl_words, int64_t rows_per_block, int blocks,
-    uint64_t* __restrict__ partials) {
+    uint64_t* __restrict__ partials, const ListArgs<LISTS> la) {
     constexpr int EPU = 16 / static_cast<int>(sizeof(T));  // elements per 16-byte unit
-    __shared__ __attribute__((aligned(16))) char lds[Lds<NQ>::kBytes];
+    __shared__ __attribute__((aligned(16))) char lds[Lds<NQ, LISTS>::kBytes];
     __shared__ int cnt[kMaxNq];
     __shared__ float thr[kMaxNq];
     char* const stage = lds + (threadIdx.x >> 6) * kStageBytes;
@@ -154,6 +296,19 @@ __global__ __launch_bounds__(kThreads, 2) void flatip_online_scan(
         }
     };
     load_step(0, 0);
+    ListState ls{};
+    if constexpr (LISTS) {
+        // while the first step is in flight: the cursors and tile 0's window
+        char* const base = lds + Lds<NQ>::kBytes;
+        constexpr int P = Lds<NQ, true>::kPairs;
+        ls.cur = reinterpret_cast<int64_t*>(base);
+        ls.end = ls.cur + P;
+        ls.next = reinterpret_cast<int32_t*>(ls.end + P);
+        ls.win = reinterpret_cast<uint32_t*>(ls.next + P);
+        lists_begin<NQ>(la, ls, nq, row_begin);
+        wave_lds_sync();
+        lists_window<NQ>(la, ls, nq, 0, row_begin, row_end);
+    }
     __syncthreads();
 
     // `over`: some buffer holds more than kRoom entries. The decision is taken
@@ -230,7 +385,13 @@ __global__ __launch_bounds__(kThreads, 2) void flatip_online_scan(
                 // load before it drained, the next tile's prefetch included: a
                 // call with exclusions loses the one-step-ahead streaming
                 bool pass = valid && acc[qi] >= th[qi];
-                if (excl && pass)
+                if constexpr (LISTS) {
+                    // bit wave * 64 + lane of the query's window: one wave-uniform
+                    // 8-byte LDS read, no global load between the scores and the ballot
+                    const uint64_t wbits = *reinterpret_cast<const uint64_t*>(
+                        ls.win + ((t & 1) * NQ + qi) * kWinWords + wave * 2);
+                    pass = pass && ((wbits >> lane) & 1ull) == 0ull;
+                } else if (excl && pass)
                     pass = ((excl[qi * excl_words + (row >> 5)] >> (row & 31)) & 1u) == 0u;
                 const uint64_t bm = __ballot(pass);
                 if (bm) {
@@ -244,6 +405,12 @@ __global__ __launch_bounds__(kThreads, 2) void flatip_online_scan(
                     if (pass) cand[qi * kCap + pos] = Cand{acc[qi], static_cast<uint32_t>(row)};
                 }
             }
+        }
+        if constexpr (LISTS) {
+            // the next tile's window, into the buffer whose last readers (tile t - 1's
+            // selection) are behind the barrier that ended that tile; the barrier
+            // below publishes it
+            if (t + 1 < tiles) lists_window<NQ>(la, ls, nq, t + 1, row_begin, row_end);
         }
         over = __syncthreads_or(mine_over);
     }
@@ -404,15 +571,16 @@ inline size_t workspace_bytes(int64_t nq, int k, const OnlinePlan& p) {
     return static_cast<size_t>(nq) * k * p.blocks * sizeof(uint64_t);
 }
 
-template <typename T>
+template <typename T, bool LISTS = false>
 int launch_scan(const void* Q, int nq, const void* X, int64_t nx, int d, int k, const uint32_t* excl,
-                int64_t excl_words, const OnlinePlan& p, uint64_t* partials, hipStream_t st) {
+                int64_t excl_words, const OnlinePlan& p, uint64_t* partials, hipStream_t st,
+                const ListArgs<LISTS>& la = ListArgs<LISTS>()) {
     const dim3 grid(static_cast<unsigned>(p.blocks)), block(kThreads);
     const T* q = static_cast<const T*>(Q);
     const char* x = static_cast<const char*>(X);
 #define RT_ONLINE_LAUNCH(NQ)                                                                                       \
-    hipLaunchKernelGGL((flatip_online_scan<T, NQ>), grid, block, 0, st, q, nq, x, nx, d, k, excl, excl_words,      \
-                       p.rows_per_block, p.blocks, partials)
+    hipLaunchKernelGGL((flatip_online_scan<T, NQ, LISTS>), grid, block, 0, st, q, nq, x, nx, d, k, excl,           \
+                       excl_words, p.rows_per_block, p.blocks, partials, la)
     if (nq <= 1) RT_ONLINE_LAUNCH(1);
     else if (nq <= 2) RT_ONLINE_LAUNCH(2);
     else if (nq <= 4) RT_ONLINE_LAUNCH(4);
@@ -451,10 +619,13 @@ extern "C" size_t rt_flatip_topk_online_workspace_bytes(int64_t nq, int64_t nx, 
     return need < 256 ? 256 : need;
 }
 
-extern "C" int rt_flatip_topk_online(const void* queries, int64_t nq, const void* items, int64_t nx, int d,
-                                     int dtype, int k, const uint32_t* exclude_bits, int64_t exclude_words,
-                                     int64_t id_offset, float* out_scores, int64_t* out_ids, void* workspace,
-                                     size_t workspace_bytes, void* stream) {
+static_assert(RT_ONLINE_MAX_EXCL_SOURCES == on::kMaxSrc, "rtrec_hip.h restates the kernel's limits");
+
+// both entry points: the dense bitmap (la == nullptr) or the lists
+static int online_search(const void* queries, int64_t nq, const void* items, int64_t nx, int d, int dtype, int k,
+                         const uint32_t* exclude_bits, int64_t exclude_words, const on::ListArgs<true>* la,
+                         int64_t id_offset, float* out_scores, int64_t* out_ids, void* workspace,
+                         size_t workspace_bytes, void* stream) {
     if (nq < 0 || nx < 0 || d <= 0 || k <= 0) return RT_ERR_INVALID;
     if (nq == 0) return RT_OK;
     if (!queries || !out_scores || !out_ids || (nx > 0 && !items)) return RT_ERR_INVALID;
@@ -474,10 +645,18 @@ extern "C" int rt_flatip_topk_online(const void* queries, int64_t nq, const void
     if (nx > 0) {
         int rc;
         const int n = static_cast<int>(nq);
-        switch (dtype) {
-            case RT_F32: rc = on::launch_scan<float>(queries, n, items, nx, d, k, exclude_bits, exclude_words, p, partials, st); break;
-            case RT_F16: rc = on::launch_scan<__half>(queries, n, items, nx, d, k, exclude_bits, exclude_words, p, partials, st); break;
-            default: rc = on::launch_scan<__hip_bfloat16>(queries, n, items, nx, d, k, exclude_bits, exclude_words, p, partials, st); break;
+        if (la) {
+            switch (dtype) {
+                case RT_F32: rc = on::launch_scan<float, true>(queries, n, items, nx, d, k, nullptr, 0, p, partials, st, *la); break;
+                case RT_F16: rc = on::launch_scan<__half, true>(queries, n, items, nx, d, k, nullptr, 0, p, partials, st, *la); break;
+                default: rc = on::launch_scan<__hip_bfloat16, true>(queries, n, items, nx, d, k, nullptr, 0, p, partials, st, *la); break;
+            }
+        } else {
+            switch (dtype) {
+                case RT_F32: rc = on::launch_scan<float>(queries, n, items, nx, d, k, exclude_bits, exclude_words, p, partials, st); break;
+                case RT_F16: rc = on::launch_scan<__half>(queries, n, items, nx, d, k, exclude_bits, exclude_words, p, partials, st); break;
+                default: rc = on::launch_scan<__hip_bfloat16>(queries, n, items, nx, d, k, exclude_bits, exclude_words, p, partials, st); break;
+            }
         }
         if (rc) return rc;
         blocks = p.blocks;
@@ -485,4 +664,30 @@ extern "C" int rt_flatip_topk_online(const void* queries, int64_t nq, const void
     hipLaunchKernelGGL(on::flatip_online_finish, dim3(static_cast<unsigned>(nq)), dim3(on::kMaxBlocks), 0, st,
                        partials, blocks, k, out_scores, out_ids, id_offset);
     return check_launch("flatip_online_finish");
+}
+
+extern "C" int rt_flatip_topk_online(const void* queries, int64_t nq, const void* items, int64_t nx, int d,
+                                     int dtype, int k, const uint32_t* exclude_bits, int64_t exclude_words,
+                                     int64_t id_offset, float* out_scores, int64_t* out_ids, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+    return online_search(queries, nq, items, nx, d, dtype, k, exclude_bits, exclude_words, nullptr, id_offset,
+                         out_scores, out_ids, workspace, workspace_bytes, stream);
+}
+
+extern "C" int rt_flatip_topk_online_lists(const void* queries, int64_t nq, const void* items, int64_t nx, int d,
+                                           int dtype, int k, const RtExclusionLists* lists, int n_lists,
+                                           int64_t id_offset, float* out_scores, int64_t* out_ids, void* workspace,
+                                           size_t workspace_bytes, void* stream) {
+    if (n_lists < 0 || (n_lists > 0 && !lists)) return RT_ERR_INVALID;
+    if (n_lists > RT_ONLINE_MAX_EXCL_SOURCES) return RT_ERR_UNSUPPORTED;
+    on::ListArgs<true> la{};
+    la.n = n_lists;
+    for (int s = 0; s < n_lists; ++s) {
+        const RtExclusionLists& L = lists[s];
+        if (!L.offsets || L.n_rows < 0 || (L.n_rows > 0 && !L.items)) return RT_ERR_INVALID;
+        la.src[s] = on::ListSrc{L.offsets, L.items, L.rows, L.n_rows};
+    }
+    // no source: the plain scan, bit for bit rt_flatip_topk_online without a bitmap
+    return online_search(queries, nq, items, nx, d, dtype, k, nullptr, 0, n_lists ? &la : nullptr, id_offset,
+                         out_scores, out_ids, workspace, workspace_bytes, stream);
 }

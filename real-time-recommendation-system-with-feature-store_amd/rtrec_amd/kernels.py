@@ -204,13 +204,24 @@ def flatip_topk_online_plan(nq: int, nx: int, d: int, dtype: torch.dtype, k: int
 def flatip_topk_online(queries: torch.Tensor, items: torch.Tensor, k: int,
                        exclude_bits: Optional[torch.Tensor] = None, id_offset: int = 0,
                        out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
-                       workspace_buf: Optional[torch.Tensor] = None
-                       ) -> Tuple[torch.Tensor, torch.Tensor]:
+                       workspace_buf: Optional[torch.Tensor] = None,
+                       exclude_lists=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """:func:`flatip_topk` for 1..8 queries and k <= 128 (rt_flatip_topk_online):
     the same results, from one streaming pass over the corpus — the shape of
     the serving path (one user per request, src/serving/retrieval.py:141-197).
     ``workspace_buf``: a caller-owned uint8 device buffer of at least
-    ``rt_flatip_topk_online_workspace_bytes`` (default: the shared grow-only one)."""
+    ``rt_flatip_topk_online_workspace_bytes`` (default: the shared grow-only one).
+
+    ``exclude_lists`` (rt_flatip_topk_online_lists; not together with
+    ``exclude_bits``): one ``(offsets, items[, rows])`` tuple of device tensors,
+    or a sequence of one or two of them — CSR sources the scan reads itself.
+    ``offsets`` int64 ``[n_rows + 1]``, ``items`` int32 corpus positions
+    ascending within a row (duplicates allowed, positions >= nx ignored),
+    ``rows`` optional int64 ``[nq]``: query q skips CSR row ``rows[q]`` (default
+    q; a row outside the CSR: nothing) of every source."""
+    if exclude_lists is not None and exclude_bits is not None:
+        raise ValueError("exclude_bits and exclude_lists are mutually exclusive")
+    sources = _exclusion_sources(exclude_lists, queries)
     native.require_device(queries, items, what="flatip_topk_online")
     if queries.dim() != 2 or items.dim() != 2 or queries.shape[1] != items.shape[1]:
         raise ValueError(f"shape mismatch: queries {tuple(queries.shape)} items {tuple(items.shape)}")
@@ -240,9 +251,51 @@ def flatip_topk_online(queries: torch.Tensor, items: torch.Tensor, k: int,
     if ws is None:
         ws = workspace(queries.device, native.lib().rt_flatip_topk_online_workspace_bytes(nq, nx, d, dt, k),
                        "topk_online")
+    if exclude_lists is not None:
+        for src in sources:
+            native.require_device(*src, what="flatip_topk_online")
+        # a source without items excludes nothing (and has no items pointer to give)
+        sources = [src for src in sources if src[1].numel()]
+        arr = (native.ExclusionLists * native.ONLINE_MAX_EXCL_SOURCES)()
+        for a, (offsets, its, rows) in zip(arr, sources):
+            a.offsets, a.items, a.n_rows, a.rows = ptr(offsets), ptr(its), offsets.numel() - 1, ptr(rows)
+        call("rt_flatip_topk_online_lists", ptr(queries), nq, ptr(items) if nx else None, nx, d, dt, k, arr,
+             len(sources), id_offset, ptr(scores), ptr(ids), ptr(ws), ws.numel(), stream_of(queries))
+        return scores, ids
     call("rt_flatip_topk_online", ptr(queries), nq, ptr(items) if nx else None, nx, d, dt, k, ptr(exclude_bits),
          words, id_offset, ptr(scores), ptr(ids), ptr(ws), ws.numel(), stream_of(queries))
     return scores, ids
+
+
+def _exclusion_sources(exclude_lists, queries: torch.Tensor):
+    """``exclude_lists`` of :func:`flatip_topk_online` as a list of
+    ``(offsets, items, rows-or-None)``; ``ValueError`` / ``TypeError`` for a
+    malformed one (checked on the host, before any device is needed)."""
+    if exclude_lists is None:
+        return []
+    if len(exclude_lists) and isinstance(exclude_lists[0], torch.Tensor):
+        exclude_lists = [exclude_lists]   # one bare (offsets, items[, rows]) tuple
+    if not 1 <= len(exclude_lists) <= native.ONLINE_MAX_EXCL_SOURCES:
+        raise ValueError(f"exclude_lists: {len(exclude_lists)} sources; one or "
+                         f"{native.ONLINE_MAX_EXCL_SOURCES} (offsets, items[, rows]) tuples")
+    out = []
+    for src in exclude_lists:
+        if not 2 <= len(src) <= 3:
+            raise ValueError("an exclusion source is (offsets, items) or (offsets, items, rows)")
+        offsets, its = src[0], src[1]
+        rows = src[2] if len(src) == 3 else None
+        if offsets.dtype != torch.int64 or its.dtype != torch.int32:
+            raise TypeError("an exclusion source is a CSR of int64 offsets and int32 ascending items")
+        if offsets.dim() != 1 or offsets.numel() < 1 or its.dim() != 1 or not offsets.is_contiguous() \
+                or not its.is_contiguous():
+            raise ValueError("an exclusion source needs contiguous 1-d offsets [n_rows + 1] and items")
+        if rows is not None:
+            if rows.dtype != torch.int64:
+                raise TypeError("exclusion rows must be int64")
+            if rows.dim() != 1 or rows.numel() < queries.shape[0] or not rows.is_contiguous():
+                raise ValueError(f"exclusion rows must be a contiguous [nq = {queries.shape[0]}] tensor")
+        out.append((offsets, its, rows))
+    return out
 
 
 def tower_infer(args: "native.TowerInferArgs", stream) -> None:

@@ -94,6 +94,14 @@ class TowerInferArgs(ctypes.Structure):
                 ("out", vp), ("norms_out", vp)]
 
 
+ONLINE_MAX_EXCL_SOURCES = 2   # RT_ONLINE_MAX_EXCL_SOURCES
+
+
+class ExclusionLists(ctypes.Structure):
+    """RtExclusionLists: one CSR source of rt_flatip_topk_online_lists (device pointers)."""
+    _fields_ = [("offsets", vp), ("items", vp), ("n_rows", c_i64), ("rows", vp)]
+
+
 GRAD_FOLD_MAX = 8    # RT_GRAD_FOLD_MAX
 DW_JOINT_MAX = 6     # argument sets of one rt_linear_bwd_dw_f32_joint call
 
@@ -116,6 +124,8 @@ SIGNATURES = {
     "rt_flatip_topk_online_plan": (c_int, [c_i64, c_i64, c_int, c_int, c_int, vp]),
     "rt_flatip_topk_online": (c_int, [vp, c_i64, vp, c_i64, c_int, c_int, c_int, vp, c_i64, c_i64, vp, vp, vp,
                                       c_size, vp]),
+    "rt_flatip_topk_online_lists": (c_int, [vp, c_i64, vp, c_i64, c_int, c_int, c_int,
+                                            ctypes.POINTER(ExclusionLists), c_int, c_i64, vp, vp, vp, c_size, vp]),
     "rt_topk_merge": (c_int, [vp, vp, c_i64, c_int, c_int, c_int, vp, vp, vp]),
     "rt_flatip_topk_tuning": (c_int, [c_int, c_int, c_int]),
     "rt_flatip_topk_shard_workspace_bytes": (c_size, [c_i64, c_i64, c_int, c_int, c_int]),

@@ -22,7 +22,8 @@ import torch.nn as nn
 
 from .. import kernels, native
 from ..models.fused import blocks_from_sequential
-from .retrieval import HipFlatIPIndex, OnlineSearcher, RetrievalEngine, _capture, _lists_from_positions
+from .retrieval import (HipFlatIPIndex, OnlineSearcher, RetrievalEngine, _capture, _exclude_positions,
+                        _lists_from_positions, _per_query)
 
 Features = Union[np.ndarray, torch.Tensor, Dict[str, Any]]
 Rows = Union[np.ndarray, torch.Tensor]
@@ -60,8 +61,16 @@ class OnlineRecommender:
     ``RTREC_ONLINE_GRAPH=0`` (read at every call) runs the chains eagerly.
 
     Calls outside the graphs' range (``k_search`` > 128, more than
-    ``max_batch`` rows) embed in chunks of ``max_batch`` and call
-    ``index.search``: the same lists, not resident.
+    ``max_batch`` rows, more than ``max_exclude`` excluded items in one call)
+    embed in chunks of ``max_batch`` and call ``index.search``: the same lists,
+    not resident.
+
+    Exclusions (``recommend(exclude_items=..., exclude_seen=True)``,
+    :meth:`set_seen`): the scan of the same chain reads them as CSR sources
+    (``rt_flatip_topk_online_lists``) — the per-request ids through the
+    searcher's two fixed-size H2D copies, the seen items from a resident CSR
+    indexed by the device ids the tower gather reads. Graphs with exclusions
+    are keyed ``(nq, k_search, by_ids, items, seen)``.
 
     Staleness. Index: ``build`` / ``add`` / ``load`` bump its generation and
     the search graphs are dropped and captured again. Model: the graphs hold the live
@@ -81,7 +90,7 @@ class OnlineRecommender:
     MAX_GRAPHS = 64
 
     def __init__(self, model: nn.Module, index: Union[HipFlatIPIndex, RetrievalEngine], max_batch: int = 8,
-                 user_table: Optional[torch.Tensor] = None):
+                 user_table: Optional[torch.Tensor] = None, max_exclude: int = 8192):
         if not 1 <= int(max_batch) <= self.MAX_BATCH:
             raise ValueError(f"max_batch={max_batch}: 1..{self.MAX_BATCH}")
         self.max_batch = int(max_batch)
@@ -135,8 +144,11 @@ class OnlineRecommender:
         self.user_table = user_table
         native.lib()
         mb, f, d = self.max_batch, self.input_dim, self.dimension
-        self._searcher = OnlineSearcher(index, mb)
+        self._searcher = OnlineSearcher(index, mb, max_exclude)
         self.lock = self._searcher.lock
+        self._seen_ids = None       # histories as given (set_seen)
+        self._seen = None           # their device CSR of positions: (offsets, items)
+        self._seen_generation = -1  # the index generation the CSR was mapped for
         self._h_x = torch.empty((mb, f), dtype=torch.float32).pin_memory()
         self._h_ids = torch.empty(mb, dtype=torch.int64).pin_memory()
         self._h_e = torch.empty((mb, d), dtype=torch.float32).pin_memory()
@@ -192,8 +204,10 @@ class OnlineRecommender:
         a.out = native.ptr(self._searcher._d_q32)
         kernels.tower_infer(a, native.stream_of(self._d_x))
 
-    def _sequence(self, nq: int, k: int, by_ids: bool):
-        """The stream-ordered chain of one call (k = 0: embed only)."""
+    def _sequence(self, nq: int, k: int, by_ids: bool, items: bool = False, seen: bool = False):
+        """The stream-ordered chain of one call (k = 0: embed only). ``items``: the
+        per-request lists staged in the searcher's pinned CSR; ``seen``: the resident
+        seen-items CSR, its rows the device ids the tower gather reads."""
         if by_ids:
             self._d_ids[:nq].copy_(self._h_ids[:nq], non_blocking=True)
         else:
@@ -202,8 +216,63 @@ class OnlineRecommender:
         # the embedding leaves before the renorm rewrites the rows in place
         self._h_e[:nq].copy_(self._searcher._d_q32[:nq], non_blocking=True)
         if k:
-            self._searcher._device_chain(nq, k)
+            sources = []
+            if seen:
+                sources.append((self._seen[0], self._seen[1], self._d_ids))
+            if items:
+                self._searcher._upload_lists()
+                sources.append(self._searcher._list_source())
+            self._searcher._device_chain(nq, k, sources)
             self._searcher._download(nq, k)
+
+    # -- seen items ----------------------------------------------------------------
+    def set_seen(self, histories) -> None:
+        """The items each user has already seen, for ``recommend(user_ids=...,
+        exclude_seen=True)``: one sequence of item ids per ``user_table`` row, or a
+        dict from row to sequence (other rows: nothing seen). Kept on the host as
+        given and mapped to a device CSR of corpus positions (int64 offsets
+        ``[n_users + 1]``, int32 positions ascending; ids the index does not know
+        are ignored). Positions move on ``remove`` / ``build`` / ``load``: the CSR
+        is mapped again from the kept id lists when the index generation changed;
+        an in-place ``update`` moves nothing. ``None`` forgets the histories."""
+        with self.lock:
+            if histories is None:
+                self._seen_ids = self._seen = None
+            else:
+                if self.user_table is None:
+                    raise ValueError("set_seen needs the user_table the recommender was made with: histories "
+                                     "are looked up by user_ids")
+                n_users = self.user_table.shape[0]
+                if isinstance(histories, dict):
+                    if any(not 0 <= int(r) < n_users for r in histories):
+                        raise IndexError(f"history row out of range for a table of {n_users} rows")
+                elif len(histories) != n_users:
+                    raise ValueError(f"{len(histories)} histories for a user_table of {n_users} rows")
+                self._seen_ids = histories
+                self._map_seen()
+            for key in [key for key in self._graphs if len(key) > 3 and key[4]]:
+                del self._graphs[key]
+
+    def _history(self, row: int):
+        h = self._seen_ids
+        return h.get(row, ()) if isinstance(h, dict) else h[row]
+
+    def _map_seen(self):
+        """Kept id lists -> the device CSR of positions, for the index as it is now."""
+        rev = self.index.reverse_id_map
+        n_users = self.user_table.shape[0]
+        offsets = np.zeros(n_users + 1, np.int64)
+        parts = []
+        rows = sorted(int(r) for r in self._seen_ids) if isinstance(self._seen_ids, dict) else range(n_users)
+        for r in rows:
+            pos = np.unique(np.asarray([rev[i] for i in self._history(r) if i in rev], dtype=np.int64))
+            offsets[r + 1] = pos.size
+            parts.append(pos)
+        np.cumsum(offsets, out=offsets)
+        flat = np.concatenate(parts).astype(np.int32) if parts else np.zeros(0, np.int32)
+        dev = self._d_ids.device
+        self._seen = (torch.from_numpy(offsets).to(dev), torch.from_numpy(flat).to(dev))
+        self._seen_generation = self.index._generation
 
     # -- inputs ------------------------------------------------------------------
     def _rows_of(self, user_features: Optional[Features], user_ids) -> Tuple[Optional[Rows], Optional[np.ndarray]]:
@@ -232,7 +301,7 @@ class OnlineRecommender:
             raise ValueError(f"expected features [nq, {self.input_dim}], got {tuple(t.shape)}")
         return t, None
 
-    def _run(self, x: Optional[Rows], ids: Optional[np.ndarray], k: int):
+    def _run(self, x: Optional[Rows], ids: Optional[np.ndarray], k: int, items: bool = False, seen: bool = False):
         """Stage the rows, run / replay the chain, synchronise. Under ``lock``."""
         by_ids = ids is not None
         nq = len(ids) if by_ids else x.shape[0]
@@ -243,9 +312,10 @@ class OnlineRecommender:
         else:
             self._h_x_np[:nq] = x
         stream = torch.cuda.current_stream(self._d_x.device)
-        key = (nq, k, by_ids)
+        # without exclusions the keys (and graphs) of a recommender that has none
+        key = (nq, k, by_ids, items, seen) if (items or seen) else (nq, k, by_ids)
         if os.environ.get("RTREC_ONLINE_GRAPH", "1") == "0":
-            self._sequence(nq, k, by_ids)
+            self._sequence(nq, k, by_ids, items, seen)
         else:
             g = self._graphs.get(key)
             if g is not None:
@@ -253,11 +323,11 @@ class OnlineRecommender:
             else:
                 # as OnlineSearcher.search: the first call at a shape answers from an
                 # eager run, then the chain is captured (a capture executes nothing)
-                self._sequence(nq, k, by_ids)
+                self._sequence(nq, k, by_ids, items, seen)
                 stream.synchronize()
                 g = torch.cuda.CUDAGraph()
                 with _capture(g):
-                    self._sequence(nq, k, by_ids)
+                    self._sequence(nq, k, by_ids, items, seen)
                 while len(self._graphs) >= self.MAX_GRAPHS:
                     self._graphs.popitem(last=False)
                 self._graphs[key] = g
@@ -288,24 +358,53 @@ class OnlineRecommender:
             return self._embed_any(x, ids)
 
     def recommend(self, user_features: Optional[Features] = None, *, user_ids=None, k: int = 10,
-                  filter_ids: Optional[List[str]] = None) -> Tuple[List[List[str]], List[List[float]]]:
-        """``(ids, scores)`` lists, as ``index.search(embed(...), k, filter_ids)``."""
+                  filter_ids: Optional[List[str]] = None, exclude_items=None, exclude_seen: bool = False
+                  ) -> Tuple[List[List[str]], List[List[float]]]:
+        """``(ids, scores)`` lists, as ``index.search(embed(...), k, filter_ids)``.
+
+        ``exclude_items`` (the request schema's field, src/api/schemas.py:31-34):
+        item ids not to return, as ``exclude_ids`` of ``HipFlatIPIndex.search`` —
+        one list for every row or one per row, unknown ids ignored, exact.
+        ``exclude_seen``: also leave out what :meth:`set_seen` recorded for each of
+        ``user_ids`` (the evaluator's train-item mask, src/evaluation/metrics.py:
+        252-282); the scan reads the resident CSR through the device ids of the
+        tower gather, so a request uploads no history. Both may be given: two
+        sources of one scan. ``ValueError`` without ``user_ids`` or before
+        ``set_seen``."""
         x, ids = self._rows_of(user_features, user_ids)
         idx = self.index
         if idx.index is None:
             raise ValueError("Index not built yet")
+        if exclude_seen and ids is None:
+            raise ValueError("exclude_seen looks histories up by user_ids")
+        if exclude_seen and self._seen_ids is None:
+            raise ValueError("exclude_seen needs set_seen(histories) first")
         nq = len(ids) if ids is not None else x.shape[0]
         k_search = min(k * 2, idx.current_size) if filter_ids else k
         if k_search <= 0 or nq == 0:
             return [[] for _ in range(nq)], [[] for _ in range(nq)]
+        items = exclude_items is not None
         with self.lock:
-            if k_search > OnlineSearcher.MAX_K or nq > self.max_batch:
-                return idx.search(self._embed_any(x, ids), k, filter_ids)
             s = self._searcher
+            resident = k_search <= OnlineSearcher.MAX_K and nq <= self.max_batch
+            if resident and items:
+                resident = s._stage_lists(nq, _exclude_positions(idx.reverse_id_map, exclude_items, nq))
+            if not resident:
+                excl = None
+                if items or exclude_seen:  # per row: the request's ids and the row's history
+                    excl = [list(e) for e in _per_query(exclude_items, nq)] if items else [[] for _ in range(nq)]
+                    if exclude_seen:
+                        for q, u in enumerate(ids):
+                            excl[q].extend(self._history(int(u)))
+                return idx.search(self._embed_any(x, ids), k, filter_ids, exclude_ids=excl)
             if s._revalidate():  # the corpus rows moved or grew: the search graphs hold stale pointers
                 for key in [key for key in self._graphs if key[1]]:
                     del self._graphs[key]
-            self._run(x, ids, k_search)
+            if exclude_seen and self._seen_generation != idx._generation:
+                self._map_seen()  # positions moved (remove / build / load): new tensors, no graph holds the old
+                for key in [key for key in self._graphs if len(key) > 3 and key[4]]:
+                    del self._graphs[key]
+            self._run(x, ids, k_search, items, exclude_seen)
             n = nq * k_search
             return _lists_from_positions(s._h_s_np[:n].reshape(nq, k_search), s._h_p_np[:n].reshape(nq, k_search),
                                          idx.id_map, k, filter_ids)

@@ -231,10 +231,11 @@ class HipFlatIPIndex(IndexBase):
         self._online = None  # sized for the index as it was; the next small call makes a new one
         logger.info("Index built in %.2f seconds", time.time() - start)
 
-    def online_searcher(self, max_batch: int = 8) -> "OnlineSearcher":
+    def online_searcher(self, max_batch: int = 8, max_exclude: int = 8192) -> "OnlineSearcher":
         """A resident searcher for calls of at most ``max_batch`` (1..8) queries
-        and k <= 128 over this index (inner-product metrics)."""
-        return OnlineSearcher(self, max_batch)
+        and k <= 128 over this index (inner-product metrics); ``max_exclude``:
+        the exclusion-list entries one call may carry through its resident buffers."""
+        return OnlineSearcher(self, max_batch, max_exclude)
 
     def search_tensors(self, query_embeddings: Array, k: int,
                        exclude_bits: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -252,25 +253,34 @@ class HipFlatIPIndex(IndexBase):
                                        exclude_bits=exclude_bits)
         return kernels.flatip_topk(q, self.index[: self.current_size], k, exclude_bits=exclude_bits)
 
-    def search(self, query_embeddings: Array, k: int = 10,
-               filter_ids: Optional[List[str]] = None) -> Tuple[List[List[str]], List[List[float]]]:
+    def search(self, query_embeddings: Array, k: int = 10, filter_ids: Optional[List[str]] = None,
+               exclude_ids=None) -> Tuple[List[List[str]], List[List[float]]]:
         """retrieval.py:141-197: normalise, top-k_search (2k when filtering), map
-        positions to ids, drop -1 padding, apply the filter, stop at k."""
+        positions to ids, drop -1 padding, apply the filter, stop at k.
+
+        ``exclude_ids`` (the request schema's ``exclude_items``, src/api/schemas.py:
+        31-34): item ids that must not be returned — one list for every query, or
+        one list per query; unknown ids are ignored. Unlike ``filter_ids`` the
+        exclusion is applied IN the search and is exact: k results whenever k
+        eligible items exist, in every configuration (the online searcher reads
+        the lists in its scan; the other paths mask through a bitmap). With
+        ``filter_ids`` as well, the allow-list then applies to the 2k over-fetch."""
         if self.index is None:
             raise ValueError("Index not built yet")
         k_search = min(k * 2, self.current_size) if filter_ids else k
+        nq = 1 if np.ndim(query_embeddings) == 1 else len(query_embeddings)
         if k_search <= 0 or (self.mutable and self.current_size == 0):  # emptied by remove: nothing to scan
-            n = 1 if np.ndim(query_embeddings) == 1 else len(query_embeddings)
-            return [[] for _ in range(n)], [[] for _ in range(n)]
+            return [[] for _ in range(nq)], [[] for _ in range(nq)]
+        excl = None if exclude_ids is None else _exclude_positions(self.reverse_id_map, exclude_ids, nq)
         if self.online_max_batch and not self._l2 and k_search <= OnlineSearcher.MAX_K:
-            nq = 1 if np.ndim(query_embeddings) == 1 else len(query_embeddings)
             if 1 <= nq <= self.online_max_batch:
                 if self._online is None:
                     self._online = self.online_searcher(self.online_max_batch)
                 with self._online.lock:  # the returned buffers are the searcher's: read them under its lock
-                    scores, pos = self._online.search(query_embeddings, k_search)
+                    scores, pos = self._online.search(query_embeddings, k_search, exclude=excl)
                     return _lists_from_positions(scores, pos, self.id_map, k, filter_ids)
-        scores, pos = self.search_tensors(query_embeddings, k_search)
+        bits = None if excl is None else kernels.exclusion_bitmap(nq, self.current_size, excl, self._dev())
+        scores, pos = self.search_tensors(query_embeddings, k_search, exclude_bits=bits)
         return _lists_from_positions(scores.cpu().numpy(), pos.cpu().numpy(), self.id_map, k, filter_ids)
 
     def add(self, embeddings: Array, ids: List[str]):
@@ -488,6 +498,13 @@ class OnlineSearcher:
     eagerly instead. After the first call at a given (nq, k) a call makes no
     torch allocation.
 
+    Exclusion lists (``search(q, k, exclude=...)``, ``max_exclude`` entries per
+    call, default 8,192): pinned CSR buffers (``offsets [max_batch + 1]``,
+    ``items [max_exclude]``) and their device twins are allocated here too; a
+    call with lists replays a graph keyed (nq, k, True) whose chain carries two
+    fixed-size H2D copies of them in front of ``rt_flatip_topk_online_lists``
+    — the lists are data, so one graph serves every list length.
+
     The searcher holds the index's row pointer and size: ``build`` / ``add`` /
     ``load`` / ``remove`` bump the index's generation, and a searcher that finds
     its generation stale drops its graphs and captures again. An in-place
@@ -505,13 +522,16 @@ class OnlineSearcher:
     MAX_K = kernels.ONLINE_MAX_K
     MAX_GRAPHS = 32
 
-    def __init__(self, index: "HipFlatIPIndex", max_batch: int = 8):
+    def __init__(self, index: "HipFlatIPIndex", max_batch: int = 8, max_exclude: int = 8192):
         if not 1 <= int(max_batch) <= self.MAX_BATCH:
             raise ValueError(f"max_batch={max_batch}: 1..{self.MAX_BATCH}")
+        if int(max_exclude) < 0:
+            raise ValueError(f"max_exclude={max_exclude}: 0 or more entries per call")
         if index._l2:
             raise ValueError("OnlineSearcher serves the inner-product metrics ('cosine', 'inner_product')")
         self.index = index
         self.max_batch = int(max_batch)
+        self.max_exclude = int(max_exclude)
         self.lock = threading.RLock()
         dev, d, mb = index._dev(), index.dimension, self.max_batch
         self._h_q = torch.empty((mb, d), dtype=torch.float32).pin_memory()
@@ -525,7 +545,14 @@ class OnlineSearcher:
         self._d_p = torch.empty(mb * self.MAX_K, dtype=torch.int64, device=dev)
         # the largest workspace any corpus size asks for: [mb][128][512 blocks] keys
         self._ws = torch.empty(mb * self.MAX_K * 512 * 8, dtype=torch.uint8, device=dev)
-        self._graphs: "OrderedDict[Tuple[int, int], torch.cuda.CUDAGraph]" = OrderedDict()
+        # the per-call exclusion lists, a CSR over the call's queries: row q = query q
+        self._h_xo = torch.zeros(mb + 1, dtype=torch.int64).pin_memory()
+        self._h_xi = torch.zeros(max(self.max_exclude, 1), dtype=torch.int32).pin_memory()
+        self._h_xo_np, self._h_xi_np = self._h_xo.numpy(), self._h_xi.numpy()
+        self._d_xo = torch.zeros(mb + 1, dtype=torch.int64, device=dev)
+        self._d_xi = torch.zeros(max(self.max_exclude, 1), dtype=torch.int32, device=dev)
+        # keys (nq, k) without lists — as before lists existed — and (nq, k, True) with
+        self._graphs: "OrderedDict[tuple, torch.cuda.CUDAGraph]" = OrderedDict()
         self._generation = -1
         self._rows: Optional[torch.Tensor] = None
 
@@ -533,11 +560,38 @@ class OnlineSearcher:
         """H2D copy of the pinned queries into the fp32 device query rows."""
         self._d_q32[:nq].copy_(self._h_q[:nq], non_blocking=True)
 
-    def _device_chain(self, nq: int, k: int):
+    def _stage_lists(self, nq: int, exclude) -> bool:
+        """Write ``exclude`` (per query: ascending unique positions, int arrays) into
+        the pinned CSR. False when the call holds more than ``max_exclude`` entries."""
+        total = sum(len(e) for e in exclude)
+        if total > self.max_exclude:
+            return False
+        o = 0
+        self._h_xo_np[0] = 0
+        for q in range(nq):
+            n = len(exclude[q])
+            self._h_xi_np[o:o + n] = exclude[q]
+            o += n
+            self._h_xo_np[q + 1] = o
+        self._h_xo_np[nq + 1:] = o
+        return True
+
+    def _upload_lists(self):
+        """The two fixed-size H2D copies of the per-call lists: whole buffers, so that
+        one captured graph serves every list length."""
+        self._d_xo.copy_(self._h_xo, non_blocking=True)
+        self._d_xi.copy_(self._h_xi, non_blocking=True)
+
+    def _list_source(self):
+        """The per-call lists as a source of ``kernels.flatip_topk_online(exclude_lists=...)``."""
+        return (self._d_xo, self._d_xi)
+
+    def _device_chain(self, nq: int, k: int, sources=None):
         """``_d_q32[:nq]`` (fp32 device rows, however they got there: ``_upload``,
         or a kernel that wrote them — :class:`rtrec_amd.serving.online.OnlineRecommender`)
         -> ``l2_renorm`` for the cosine metric (in place) -> storage-dtype cast ->
-        ``rt_flatip_topk_online`` into the device scores / positions."""
+        ``rt_flatip_topk_online`` (``sources``: ``rt_flatip_topk_online_lists`` with
+        these exclusion sources) into the device scores / positions."""
         n = nq * k
         q32 = self._d_q32[:nq]
         if self.index.metric == "cosine":
@@ -546,7 +600,7 @@ class OnlineSearcher:
         if q.data_ptr() != q32.data_ptr():
             q.copy_(q32)
         kernels.flatip_topk_online(q, self._rows, k, out=(self._d_s[:n].view(nq, k), self._d_p[:n].view(nq, k)),
-                                   workspace_buf=self._ws)
+                                   workspace_buf=self._ws, exclude_lists=sources or None)
 
     def _download(self, nq: int, k: int):
         """D2H copies of scores and positions into the pinned result buffers."""
@@ -554,10 +608,12 @@ class OnlineSearcher:
         self._h_s[:n].copy_(self._d_s[:n], non_blocking=True)
         self._h_p[:n].copy_(self._d_p[:n], non_blocking=True)
 
-    def _sequence(self, nq: int, k: int):
+    def _sequence(self, nq: int, k: int, lists: bool = False):
         """The stream-ordered chain of one call, on torch's current stream."""
         self._upload(nq)
-        self._device_chain(nq, k)
+        if lists:
+            self._upload_lists()
+        self._device_chain(nq, k, [self._list_source()] if lists else None)
         self._download(nq, k)
 
     def _revalidate(self) -> bool:
@@ -576,9 +632,19 @@ class OnlineSearcher:
         self._generation = idx._generation
         return True
 
-    def search(self, query_embeddings: Array, k: int) -> Tuple[np.ndarray, np.ndarray]:
+    def search(self, query_embeddings: Array, k: int, exclude=None) -> Tuple[np.ndarray, np.ndarray]:
         """(scores [nq, k] f32, positions [nq, k] int64, (-FLT_MAX, -1) padded) as
-        numpy views of the searcher's pinned buffers: valid until the next call."""
+        numpy views of the searcher's pinned buffers: valid until the next call.
+
+        ``exclude``: ``nq`` sequences of corpus positions that query q must not
+        return (sorted and de-duplicated here; positions outside the corpus are
+        ignored). They travel as data through two fixed-size H2D copies in front of
+        the scan, which reads them itself (``rt_flatip_topk_online_lists``): one
+        graph per (nq, k) serves every list length up to ``max_exclude`` entries
+        per call. A call with more takes the non-resident path — a dense bitmap
+        and ``search_tensors(..., exclude_bits=...)`` — and returns the same result
+        in fresh arrays. ``exclude=None`` replays the graphs of a searcher without
+        lists."""
         idx = self.index
         if idx.index is None:
             raise ValueError("Index not built yet")
@@ -592,13 +658,23 @@ class OnlineSearcher:
             raise ValueError(f"{nq} queries: the online searcher takes 1..{self.max_batch}")
         if t.shape[1] != idx.dimension:
             raise ValueError(f"expected dimension {idx.dimension}, got {t.shape[1]}")
+        lists = exclude is not None
+        if lists:
+            if len(exclude) != nq:
+                raise ValueError(f"exclude holds {len(exclude)} lists for {nq} queries")
+            exclude = [_sorted_positions(e, idx.current_size) for e in exclude]
         with self.lock:
             self._revalidate()
+            if lists and not self._stage_lists(nq, exclude):
+                # more entries than the resident buffers hold: the dense bitmap of the default path
+                bits = kernels.exclusion_bitmap(nq, idx.current_size, exclude, self._d_s.device)
+                s, p = idx.search_tensors(t, k, exclude_bits=bits)
+                return s.cpu().numpy(), p.cpu().numpy()
             self._h_q[:nq].copy_(t)
-            key = (nq, k)
+            key = (nq, k, True) if lists else (nq, k)
             stream = torch.cuda.current_stream(self._d_s.device)
             if os.environ.get("RTREC_ONLINE_GRAPH", "1") == "0":
-                self._sequence(nq, k)
+                self._sequence(nq, k, lists)
             else:
                 g = self._graphs.get(key)
                 if g is not None:
@@ -607,13 +683,13 @@ class OnlineSearcher:
                     # the first call at this shape: its answer comes from an eager run
                     # (which also loads every kernel), then the chain is captured —
                     # a capture executes nothing, the host buffers keep the answer
-                    self._sequence(nq, k)
+                    self._sequence(nq, k, lists)
                     stream.synchronize()
                     g = torch.cuda.CUDAGraph()
                     # thread_local: CUDA work of other threads (an allocation, a default-path
                     # search) during the capture neither enters it nor invalidates it
                     with _capture(g):
-                        self._sequence(nq, k)
+                        self._sequence(nq, k, lists)
                     while len(self._graphs) >= self.MAX_GRAPHS:
                         self._graphs.popitem(last=False)
                     self._graphs[key] = g
@@ -662,7 +738,8 @@ class HipShardedFlatIPIndex(IndexBase):
     default group; world 1 without one) and ``query_tile``. The ``mutable``
     option of :class:`HipFlatIPIndex` is not served here yet: ``update`` and
     ``remove`` keep the reference's warning stubs (a cross-rank compaction has
-    to re-balance the shards).
+    to re-balance the shards). Nor is ``exclude_ids``: ``search`` here takes the
+    allow-list ``filter_ids`` only.
     """
 
     MAX_K = 512  # rt_topk_merge: k_out <= 512
@@ -972,6 +1049,39 @@ class _PositionIds:
         return str(p)
 
 
+def _sorted_positions(positions, n: int) -> np.ndarray:
+    """Ascending unique int32 corpus positions in [0, n) of one exclusion list."""
+    a = np.asarray(positions.cpu() if isinstance(positions, torch.Tensor) else positions).reshape(-1)
+    if a.size == 0:
+        return np.zeros(0, np.int32)
+    if not np.issubdtype(a.dtype, np.integer):
+        raise TypeError("excluded positions must be integers")
+    a = np.unique(a.astype(np.int64, copy=False))
+    return a[(a >= 0) & (a < n)].astype(np.int32)
+
+
+def _per_query(ids, nq: int) -> List:
+    """``exclude_ids`` as ``nq`` lists: one flat list of ids serves every query."""
+    ids = list(ids)
+    if all(isinstance(i, (str, bytes)) or not hasattr(i, "__iter__") for i in ids):
+        return [ids] * nq
+    if len(ids) != nq:
+        raise ValueError(f"exclude_ids holds {len(ids)} lists for {nq} queries")
+    return [list(i) for i in ids]
+
+
+def _exclude_positions(reverse_id_map: Dict[str, int], exclude_ids, nq: int) -> List[np.ndarray]:
+    """Per query: the ascending unique positions of the known ids of ``exclude_ids``."""
+    out, memo = [], {}
+    for ids in _per_query(exclude_ids, nq):
+        got = memo.get(id(ids))
+        if got is None:
+            pos = [reverse_id_map[i] for i in ids if i in reverse_id_map]
+            got = memo[id(ids)] = np.unique(np.asarray(pos, dtype=np.int64)).astype(np.int32)
+        out.append(got)
+    return out
+
+
 def _lists_from_positions(scores: np.ndarray, pos: np.ndarray, id_map: Dict[int, str], k: int,
                           filter_ids: Optional[List[str]]) -> Tuple[List[List[str]], List[List[float]]]:
     """retrieval.py:176-195: positions -> string ids, -1 padding dropped, the
@@ -1038,12 +1148,14 @@ class RetrievalEngine:
         logger.info("Built index with %d items", len(embeddings))
 
     def retrieve(self, query_embeddings: Array, k: Optional[int] = None,
-                 filter_ids: Optional[List[str]] = None, use_cache: bool = True
+                 filter_ids: Optional[List[str]] = None, use_cache: bool = True, exclude_ids=None
                  ) -> Tuple[List[List[str]], List[List[float]], Dict[str, Any]]:
+        """``exclude_ids``: as ``HipFlatIPIndex.search``; like ``filter_ids`` it keeps
+        the call out of the query cache (neither read nor filled)."""
         start = time.time()
         k = k or self.top_k
         cache_key = None
-        if use_cache and filter_ids is None:
+        if use_cache and filter_ids is None and exclude_ids is None:
             qb = query_embeddings.detach().cpu().numpy().tobytes() if isinstance(query_embeddings, torch.Tensor) \
                 else np.asarray(query_embeddings).tobytes()
             cache_key = hashlib.md5(qb).hexdigest()
@@ -1054,7 +1166,10 @@ class RetrievalEngine:
                 self.total_queries += 1
                 self.total_latency += latency
                 return entry["ids"], entry["scores"], {"latency_ms": latency * 1000, "cache_hit": True}
-        item_ids, scores = self.index.search(query_embeddings, k, filter_ids)
+        if exclude_ids is None:
+            item_ids, scores = self.index.search(query_embeddings, k, filter_ids)
+        else:  # HipFlatIPIndex (the sharded index does not take exclusions)
+            item_ids, scores = self.index.search(query_embeddings, k, filter_ids, exclude_ids=exclude_ids)
         if use_cache and cache_key:
             self.cache[cache_key] = {"ids": item_ids, "scores": scores, "timestamp": time.time()}
             if time.time() - self.last_cache_clear > self.cache_ttl:

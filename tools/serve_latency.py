@@ -42,6 +42,20 @@ Legs
                 as a fraction of 8 TB/s) and the host bookkeeping of ``remove``
                 (the call minus its device work).
 
+  exclude       (not in the default list) seen-item exclusion on the resident search:
+                N = --rows, d = 128, k = 100, float16 and float32, nq in {1, 8}, 166
+                random positions per query. Sides ``none`` (no exclusion), ``lists``
+                (``OnlineSearcher.search(exclude=...)``) and ``bitmap`` (what a build
+                without the list entry offers: rt_exclusion_bitmap into a resident
+                bitmap + ``search_tensors(exclude_bits=...)``) alternate call by call,
+                3 rounds with each side first in turn; ``bar``: the p50 of ``lists``
+                in every round against the minimum p50 of ``bitmap`` over its rounds.
+                Plus the online kernel pair alone by hipEvent pairs, three ways
+                (no exclusion, lists, dense bitmap). The leg stops if the list and
+                bitmap forms of the online kernel differ in any bit, or if the two
+                sides return different ids (``sides_agree`` also records whether their
+                scores are equal; the bitmap side runs the batch kernel).
+
 The first two legs are timed with ``online_max_batch`` off and on, alternating
 call by call in one process (two indexes over the same rows, so neither finds
 its corpus in the Infinity Cache). The ``on`` side of serve_q1_ref and the
@@ -440,6 +454,107 @@ def leg_mutate(args):
     return out
 
 
+def leg_exclude(args):
+    """Seen-item exclusion on the resident search path: N = --rows, d = 128,
+    k = 100, float16 and float32 rows, nq = 1 and 8, 166 random positions per
+    query (MovieLens-1M's mean history). Three sides, alternating call by call,
+    3 rounds with each side first in turn, every side ending in the id lists:
+      none   the resident searcher without exclusion;
+      lists  the resident searcher with ``exclude=`` (the scan reads the lists);
+      bitmap what a build without the list entry offers: the lists to the device,
+             rt_exclusion_bitmap into a resident bitmap, search_tensors(
+             exclude_bits=...), the result to the host.
+    The bar: the p50 of ``lists`` in every round is below the MINIMUM p50 of
+    ``bitmap`` over its rounds. Then the kernel pair alone (hipEvent pairs):
+    without exclusion, with lists, and with the dense bitmap through
+    rt_flatip_topk_online."""
+    from rtrec_amd.serving.retrieval import _lists_from_positions, _sorted_positions
+    n, d, k, per_q = args.rows, 128, 100, 166
+    out = {}
+    ids = [str(i) for i in range(n)]
+    rng = np.random.default_rng(3)
+    qs = rng.standard_normal((64, d)).astype(np.float32)
+    pool = [rng.choice(n, size=min(per_q, n), replace=False) for _ in range(64)]
+    for storage in ("float16", "float32"):
+        g = torch.Generator(device="cuda").manual_seed(1)
+        ix = HipFlatIPIndex({"dimension": d, "metric": "cosine", "storage_dtype": storage})
+        ix.build(torch.randn((n, d), generator=g, device="cuda"), ids)
+        s = ix.online_searcher(8)
+        words = (n + 31) // 32
+        for nq in (1, 8):
+            bits = torch.zeros((nq, words), dtype=torch.int32, device="cuda")
+            state = {"i": 0}
+
+            def request():
+                state["i"] += 1
+                o = (state["i"] * nq) % (64 - nq)
+                return qs[o:o + nq], pool[o:o + nq]
+
+            def none():
+                q, _ = request()
+                with s.lock:
+                    sc, pos = s.search(q, k)
+                    return _lists_from_positions(sc, pos, ix.id_map, k, None)
+
+            def lists():
+                q, ex = request()
+                with s.lock:
+                    sc, pos = s.search(q, k, exclude=ex)
+                    return _lists_from_positions(sc, pos, ix.id_map, k, None)
+
+            def bitmap():
+                q, ex = request()
+                ex = [_sorted_positions(e, n) for e in ex]
+                off = np.zeros(nq + 1, np.int64)
+                np.cumsum([len(e) for e in ex], out=off[1:])
+                kernels.exclusion_bitmap_csr(torch.from_numpy(off).cuda(), torch.from_numpy(np.concatenate(ex)).cuda(),
+                                             n, out=bits)
+                sc, pos = ix.search_tensors(q, k, exclude_bits=bits)
+                return _lists_from_positions(sc.cpu().numpy(), pos.cpu().numpy(), ix.id_map, k, None)
+
+            # the kernel pair alone, on prepared device queries and resident operands: first
+            # that the list form and the bitmap form agree bit for bit, timed after the rounds
+            q = torch.nn.functional.normalize(torch.from_numpy(qs[:nq]).cuda(), dim=1).to(ix.storage_dtype)
+            rows = ix.index[: ix.current_size]
+            ex = [_sorted_positions(e, n) for e in pool[:nq]]
+            off = np.zeros(nq + 1, np.int64)
+            np.cumsum([len(e) for e in ex], out=off[1:])
+            d_off, d_it = torch.from_numpy(off).cuda(), torch.from_numpy(np.concatenate(ex)).cuda()
+            kernels.exclusion_bitmap_csr(d_off, d_it, n, out=bits)
+            a = kernels.flatip_topk_online(q, rows, k, exclude_lists=(d_off, d_it))
+            b = kernels.flatip_topk_online(q, rows, k, exclude_bits=bits)
+            if not (torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])):
+                raise SystemExit(f"exclude leg {storage} nq={nq}: lists and bitmap differ in the online kernel")
+            sides = {"none": none, "lists": lists, "bitmap": bitmap}
+            got = lists()
+            state["i"] -= 1  # the same request again
+            ref = bitmap()
+            agree = {"ids": got[0] == ref[0], "scores": got[1] == ref[1]}
+            if not agree["ids"]:
+                raise SystemExit(f"exclude leg {storage} nq={nq}: the list side and the bitmap side return "
+                                 f"different ids: {got[0][0][:5]} vs {ref[0][0][:5]}")
+            names, rounds = list(sides), []
+            for r in range(3):
+                order = names[r:] + names[:r]
+                res = timed_alternating({name: sides[name] for name in order}, args.calls, args.warmup)
+                rounds.append({"first": order[0], **res})
+            floor = min(r["bitmap"]["p50_ms"] for r in rounds)
+            res = {"rounds": rounds, "bar": {
+                "bitmap_min_p50_ms": floor, "lists_p50_ms": [r["lists"]["p50_ms"] for r in rounds],
+                "none_p50_ms": [r["none"]["p50_ms"] for r in rounds],
+                "lower_in_every_round": all(r["lists"]["p50_ms"] < floor for r in rounds)}}
+            res["sides_agree"] = agree
+            res["kernels"] = event_timed_alternating({
+                "kernel_none": lambda: kernels.flatip_topk_online(q, rows, k),
+                "kernel_lists": lambda: kernels.flatip_topk_online(q, rows, k, exclude_lists=(d_off, d_it)),
+                "kernel_bitmap": lambda: kernels.flatip_topk_online(q, rows, k, exclude_bits=bits),
+            }, min(args.calls, 300), 10)
+            out[f"{storage}_nq{nq}"] = res
+        del s, ix
+        torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--baseline", action="store_true", help="only the API of the commit before the online path")
@@ -458,7 +573,8 @@ def main():
     res = {"tool": "serve_latency", "baseline": bool(args.baseline), "calls": args.calls, "warmup": args.warmup,
            "lib": os.environ.get("RTREC_HIP_LIB", "in-tree"), "device": torch.cuda.get_device_name(0)}
     legs = {"serve_q1_ref": leg_serve_q1_ref, "corpus_1m": leg_corpus_1m, "embed_b1": leg_embed_b1,
-            "serve_e2e": leg_serve_e2e, "tower_kernel": leg_tower_kernel, "mutate": leg_mutate}
+            "serve_e2e": leg_serve_e2e, "tower_kernel": leg_tower_kernel, "mutate": leg_mutate,
+            "exclude": leg_exclude}
     for name in args.legs.split(","):
         if name not in legs:
             ap.error(f"unknown leg {name!r}")
