@@ -10,17 +10,19 @@
 //
 // Block geometry of the in-batch part: a FIXED tile of 32 rows (users, or items
 // in the column pass) whose fragments sit in registers, and a STREAMED span of
-// 256 rows: each wave stages two 32-row tiles through its own LDS slice (all
-// loads of a tile in flight at once, the next tile prefetched into registers
-// while the current one is on the MFMAs).
-// Launch 1 (B/32 × B/256 blocks): per-span partial row log-sum-exp of S = U·Pᵀ/τ
-//   (online max/sum, S never stored), plus the explicit contrastive CE with its
-//   gradients for a strided subset of the block's users.
+// 256 rows: each wave stages 32-row tiles through its own LDS slice (all loads
+// of a tile in flight at once; a wave with two tiles prefetches the second into
+// registers while the first is on the MFMAs).
+// Launch 1 (B/32 × B/256 blocks of 4 waves x 2 tiles): per-span partial row
+//   log-sum-exp of S = U·Pᵀ/τ (online max/sum, S never stored), plus the explicit
+//   contrastive CE with its gradients for a strided subset of the block's users.
 // Launch 2 (2 × B/32 × B/256 blocks): S tiles are recomputed; the accumulator
 //   of an S tile is directly the A operand of the next MFMA (the k order over
 //   the streamed rows follows the accumulator layout), so dU = dS·P (row pass)
 //   and dP = dSᵀ·U (column pass) need no LDS transpose; dS = w/B·(softmax − I).
-//   The 4 waves' partials are summed through LDS, one atomic per element per span.
+//   D <= 128: 8 waves, one tile each (two waves per SIMD, no prefetch buffer);
+//   D = 256: 4 waves, two tiles each (8 tiles would not fit the LDS). The waves'
+//   partials are summed through LDS in wave order, one atomic per element per span.
 // Every MFMA operand is an fp32 value taken as its three bf16 pieces; the
 // k-order of an S chain is that of the 32x32x16 MFMA (lane half h holds
 // k = 16kb + 8h .. +7 of k-block kb), so every fragment is two contiguous float4.
@@ -62,7 +64,7 @@ struct Args {
     bool grad;
 };
 
-constexpr int SPAN = 256;  // streamed rows per block (4 waves x 2 tiles of 32)
+constexpr int SPAN = 256;  // streamed rows per block (launch 1: 4 waves x 2 tiles of 32; launch 2: 8 x 1 or 4 x 2)
 constexpr int LDP = 4;     // LDS row pad (floats): conflict-free ds_read_b128 of 16 rows
 
 // ---- in-batch building blocks (DP = D padded to a multiple of 32) ----------
@@ -140,9 +142,21 @@ __device__ __forceinline__ f32x16 s_tile3(const float* __restrict__ Ss, const Pi
     }
     return acc;
 }
-// dynamic LDS of the in-batch kernels: 4 waves x 32 rows x (DP + LDP) floats
+// dynamic LDS of the in-batch kernels: waves x 32 rows x (DP + LDP) floats
 template <int DP>
-constexpr size_t inb_lds_bytes() { return static_cast<size_t>(4) * 32 * (DP + LDP) * sizeof(float); }
+constexpr size_t inb_lds_bytes(int waves) { return static_cast<size_t>(waves) * 32 * (DP + LDP) * sizeof(float); }
+// launch 2 runs SPAN / 32 = 8 waves of one tile where their slices fit the CU's
+// LDS (DP <= 128: 132 KiB + lse_s), else 4 waves of two tiles
+// (A/B build: -DRT_LOSS_BWD_WAVES=4 is the 4-wave form at every D)
+template <int DP>
+constexpr int bwd_waves() {
+#ifdef RT_LOSS_BWD_WAVES
+    static_assert(RT_LOSS_BWD_WAVES == 4 || RT_LOSS_BWD_WAVES == 8, "the two forms that are built and tested");
+    return DP <= 128 ? RT_LOSS_BWD_WAVES : 4;
+#else
+    return DP <= 128 ? 8 : 4;
+#endif
+}
 
 // ---------------------------------------------------------------- launch 1
 // block (it, js < n_split): in-batch partial row log-sum-exp of users
@@ -331,9 +345,13 @@ __device__ __forceinline__ float combine_lse(const float2* part, int n_split, in
 // blockIdx.z = 0: row pass, fixed 32 users, dU += dS · P over the span's items
 // blockIdx.z = 1: column pass, fixed 32 items, dP += dSᵀ · U over the span's users
 // (dS = wb/B·(softmax(S) − I)); one atomic add per output element per span.
-template <int DP, typename T>
-__global__ __launch_bounds__(256) void loss_bwd_kernel(Args a, float wb_eff, bool add_loss) {
+// NW waves per block, each with SPAN / (32 NW) streamed tiles: tile q of wave w
+// starts at streamed row s0 + 32 (w + NW q).
+template <int DP, typename T, int NW>
+__global__ __launch_bounds__(64 * NW) void loss_bwd_kernel(Args a, float wb_eff, bool add_loss) {
     constexpr int DT = DP / 32;
+    constexpr int NT = SPAN / (32 * NW);
+    static_assert(NT * 32 * NW == SPAN && NT >= 1, "the waves' tiles cover the span");
     extern __shared__ __attribute__((aligned(16))) float sm_b[];
     __shared__ float lse_s[SPAN];  // column pass: the span's streamed users
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 31, h = lane >> 5;
@@ -379,8 +397,10 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(Args a, float wb_eff, boo
             }
         }
     } else {
-        const int64_t i = s0 + tid;
-        lse_s[tid] = i < a.b ? combine_lse(a.part, a.n_split, a.b, i) : 0.f;  // streamed users
+        for (int x = tid; x < SPAN; x += 64 * NW) {  // streamed users
+            const int64_t i = s0 + x;
+            lse_s[x] = i < a.b ? combine_lse(a.part, a.n_split, a.b, i) : 0.f;
+        }
     }
     __syncthreads();
     if (!a.grad || !ib || f0 >= n_fixed || s0 >= n_str) return;
@@ -388,19 +408,19 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(Args a, float wb_eff, boo
     float* Ss = sm_b + w * 32 * (DP + LDP);
     Pieces pf[DP / 16];
     load_fixed3<DP, T>(Fm, f0, n_fixed, D, pf);
-    const int64_t t0 = s0 + 32 * w, t1 = t0 + 128;
+    const int64_t t0 = s0 + 32 * w;
     float4 buf[DP / 8];
     load_rows<DP, T>(Sm, t0, n_str, D, buf);
     f32x16 acc[DT];
 #pragma unroll
     for (int x = 0; x < DT; ++x) acc[x] = f32x16{};
 #pragma unroll 1
-    for (int q = 0; q < 2; ++q) {
-        const int64_t tt = q == 0 ? t0 : t1;
+    for (int q = 0; q < NT; ++q) {
+        const int64_t tt = t0 + 32 * NW * q;
         if (tt >= n_str) break;  // wave-uniform
         store_rows<DP>(Ss, buf);
         wave_lds_sync();
-        if (q == 0 && t1 < n_str) load_rows<DP, T>(Sm, t1, n_str, D, buf);  // prefetch
+        if (q + 1 < NT && tt + 32 * NW < n_str) load_rows<DP, T>(Sm, tt + 32 * NW, n_str, D, buf);  // prefetch
         // st[r]: streamed row tile_row(r,h) x fixed col c
         const f32x16 st = s_tile3<DP>(Ss, pf);
         float ds[16];
@@ -411,7 +431,7 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(Args a, float wb_eff, boo
             const int64_t srow = tt + rr;
             float v = 0.f;
             if (srow < n_str && fcol < n_fixed) {
-                const float lse = row_pass ? lse_fixed : lse_s[32 * w + 128 * q + rr];
+                const float lse = row_pass ? lse_fixed : lse_s[32 * (w + NW * q) + rr];
                 // label: item off + user  (row pass: srow item, fcol user; column pass: the reverse)
                 const bool label = row_pass ? (srow == a.off + fcol) : (fcol == a.off + srow);
                 v = scale * (expf(st[r] * a.inv_tau - lse) - (label ? 1.f : 0.f));
@@ -440,19 +460,21 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(Args a, float wb_eff, boo
         }
         wave_lds_sync();
     }
-    // ---- sum the 4 waves' [32 fixed x DP] partials through LDS, one atomic each ----
+    // ---- sum the waves' [32 fixed x DP] partials through LDS in wave order, one
+    // atomic each (a partial is 32 x DP floats, a wave's slice 32 x (DP + LDP)) ----
     __syncthreads();  // every wave done with its Ss slice
-    float* red = sm_b;  // [4][DT*16][64]
+    float* red = sm_b;  // [NW][DT*16][64]
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
         for (int r = 0; r < 16; ++r) red[(w * DT * 16 + dt * 16 + r) * 64 + lane] = acc[dt][r];
     __syncthreads();
     float* out = row_pass ? a.du : a.dp;
-    for (int p = tid; p < DT * 16 * 64; p += 256) {
+    for (int p = tid; p < DT * 16 * 64; p += 64 * NW) {
         const int v = p >> 6, l = p & 63;
-        const float t = red[v * 64 + l] + red[(DT * 16 + v) * 64 + l] + red[(2 * DT * 16 + v) * 64 + l] +
-                        red[(3 * DT * 16 + v) * 64 + l];
+        float t = red[v * 64 + l];
+#pragma unroll
+        for (int x = 1; x < NW; ++x) t += red[(x * DT * 16 + v) * 64 + l];
         const int dt = v >> 4, r = v & 15;
         const int64_t gi = f0 + tile_row(r, l >> 5);
         const int dd = dt * 32 + (l & 31);
@@ -484,11 +506,12 @@ using namespace rt;
 
 namespace {
 // allow > 64 KiB of dynamic LDS (gfx950 has 160 KiB per CU); set once per kernel
-template <typename K>
-void allow_lds(K kernel, size_t bytes) {
+// (the kernel is a template argument: one flag per instantiation, not per signature)
+template <auto Kernel>
+void allow_lds(size_t bytes) {
     static size_t set = 0;
     if (bytes > set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   static_cast<int>(bytes));
         set = bytes;
     }
@@ -496,13 +519,15 @@ void allow_lds(K kernel, size_t bytes) {
 
 template <int DP, typename T>
 int launch_loss(const loss::Args& a, dim3 grid1, dim3 grid2, float wb_eff, hipStream_t st) {
-    const size_t lds = loss::inb_lds_bytes<DP>();
-    allow_lds(loss::loss_fwd_kernel<DP, T>, lds);
-    hipLaunchKernelGGL((loss::loss_fwd_kernel<DP, T>), grid1, dim3(256), lds, st, a);
+    const size_t lds1 = loss::inb_lds_bytes<DP>(4);
+    allow_lds<loss::loss_fwd_kernel<DP, T>>(lds1);
+    hipLaunchKernelGGL((loss::loss_fwd_kernel<DP, T>), grid1, dim3(256), lds1, st, a);
     const int rc = check_launch("loss_fwd_kernel");
     if (rc) return rc;
-    allow_lds(loss::loss_bwd_kernel<DP, T>, lds);
-    hipLaunchKernelGGL((loss::loss_bwd_kernel<DP, T>), grid2, dim3(256), lds, st, a, wb_eff, true);
+    constexpr int NW = loss::bwd_waves<DP>();
+    const size_t lds2 = loss::inb_lds_bytes<DP>(NW);
+    allow_lds<loss::loss_bwd_kernel<DP, T, NW>>(lds2);
+    hipLaunchKernelGGL((loss::loss_bwd_kernel<DP, T, NW>), grid2, dim3(64 * NW), lds2, st, a, wb_eff, true);
     return check_launch("loss_bwd_kernel");
 }
 

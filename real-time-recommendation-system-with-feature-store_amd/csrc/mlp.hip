@@ -290,6 +290,22 @@ __device__ __forceinline__ void bn_finalize_last(const rt_linear_fwd_args& a, un
 constexpr int FM = 32;  // rows per block
 
 __host__ __device__ __forceinline__ int pad8(int k) { return (k + 31) / 32 * 32; }  // k padded to whole 32-deep iterations
+// The fast-path conditions of linear_bwd_dz_kernel. The kernel tests them per
+// launch group; the host's dz_fast_class tests the SAME functions to pick an
+// instance that has only those paths compiled in.
+// phase A, F.normalize backward: float4 lanes per row a power of two <= 64, no pad columns
+__host__ __device__ __forceinline__ bool dz_norm_fast(int n) {
+    const int l4 = n / 4;
+    return (n % 4) == 0 && l4 <= 64 && (l4 & (l4 - 1)) == 0 && pad8(n) == n;
+}
+// phase A, BatchNorm / plain backward: each thread owns 4 fixed columns
+__host__ __device__ __forceinline__ bool dz_bn_fast(int n, int act, int grad_mode) {
+    return (n % 4) == 0 && (256 % (pad8(n) / 4)) == 0 && act_is_piecewise_linear(act) && grad_mode != 3;
+}
+// dA epilogue (of a full row block): g_prev only, piecewise-linear previous activation
+__host__ __device__ __forceinline__ bool dz_da_fast(const rt_linear_bwd_args& a) {
+    return !a.dsrc && a.g_prev && act_is_piecewise_linear(a.prev_act);
+}
 
 // WPL: the k-loop reads W's split pieces from rt_linear_fwd_args.w_planes
 // (TPW == 1, k % 8 == 0) instead of splitting W fragments in registers
@@ -807,10 +823,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TPW == 1 ? 
 // Block = 32 rows. dz (32 x n) lives in LDS; dA = dz·W reads W[n][k] rows
 // coalesced along k straight from L2 (the reduction runs over n).
 // (3 waves per SIMD: the C2 launches' 576 blocks need 3 co-resident blocks on
-// some CUs; the register cap moves the accumulators from AGPRs to VGPRs, no spill)
+// some CUs; the register cap moves the accumulators from AGPRs to VGPRs. At
+// that cap the all-paths instances spill: `make resource-usage` is the record,
+// DESIGN §5 has the table. The FE instances below spill no VGPR.)
 // WPL: dA reads Wᵀ's split pieces from rt_linear_bwd_args.wt_planes (n % 8 == 0)
 // KS: L.ksplit > 1 (dA columns of a row block split over blocks)
-template <int TPWK, bool WPL, bool KS>  // 32-col dA tiles per wave (k <= 128*TPWK)
+// FE != 0: every argument set takes one fast phase A (1: the F.normalize
+// backward, 2: the BatchNorm-backward float4 pass), the Wᵀ-row loads and the
+// fast dA epilogue (the host checks it, dz_fast_class): the other phase A, the
+// generic passes, the strided W loads, the predicated epilogue and the dsrc
+// store are not compiled in, so their live values do not count against the
+// three-wave register cap
+template <int TPWK, bool WPL, bool KS, int FE>  // 32-col dA tiles per wave (k <= 128*TPWK)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void linear_bwd_dz_kernel(BwdLaunch L) {
 #ifdef RT_FOLD_FIRST
     fold_side(L, 0);
@@ -857,7 +881,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void l
         for (int i = 0; i < TPWK; ++i) {
             const int kk = (tb + w + 4 * i) * 32 + c32;
             const bool on = (tb + w + 4 * i) * 32 < k && kk < k;
-            if (WtT) {
+            if (FE != 0 || WtT) {  // (FE: the host saw a.wt and n % 8 == 0)
                 const int nn = s + 8 * h;
                 float4 v0 = make_float4(0.f, 0.f, 0.f, 0.f), v1 = v0;
                 if (on && nn < n) {
@@ -901,7 +925,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void l
 
     // ---- phase A: dz tile ----
     const int l4 = n / 4;  // grad_mode 0 fast path: float4 lanes per row (a power of two <= 64)
-    if (a.grad_mode == 0 && (n % 4) == 0 && l4 <= 64 && (l4 & (l4 - 1)) == 0 && np == n) {
+    if (FE == 1 || (FE == 0 && a.grad_mode == 0 && dz_norm_fast(n))) {
         // F.normalize backward, every load of the wave's 8 rows issued up front:
         // l4 lanes per row, 64/l4 rows per pass, segmented lane sums for the dots
         const int rpp = 64 / l4, sub = lane / l4, li = lane % l4, c = 4 * li;
@@ -939,7 +963,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void l
             }
             *reinterpret_cast<float4*>(Dz + r * ldz + c) = d;
         }
-    } else if (a.grad_mode == 0) {
+    } else if (FE == 0 && a.grad_mode == 0) {
         for (int rr = w * 8; rr < w * 8 + 8; ++rr) {
             const int64_t gr = row0 + rr;
             if (gr < m) {
@@ -962,7 +986,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void l
                 for (int c = lane; c < np; c += 64) Dz[rr * ldz + c] = 0.f;
             }
         }
-    } else {
+    } else if constexpr (FE != 1) {
         // per-column BN-backward coefficients, then a float4 elementwise pass
         float* cA = Dz + FM * ldz;   // γ·invstd (mode 1/2) or 1
         float* cB = cA + np;         // Σg/m
@@ -973,7 +997,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void l
         const double* gst = a.g_stats ? a.g_stats + static_cast<int64_t>(my_seg) * RT_STAT_SLOTS * 2 * n : nullptr;
         const int vpr = np / 4;
         const bool vec = (n % 4) == 0;
-        const bool fast = vec && (256 % vpr) == 0 && act_is_piecewise_linear(a.act) && a.grad_mode != 3;
+        const bool fast = FE != 0 || dz_bn_fast(n, a.act, a.grad_mode);
         // fast path with one pass over the tile: its g loads are issued before
         // the coefficient loads below, so both share one memory round trip (z
         // follows after the barrier: both sets at once would cost occupancy)
@@ -1050,7 +1074,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void l
                     if (prim && gr < m && c < n) st_act4(a.dz_ws + gr * n + c, d);
                 }
             }
-        } else
+        } else if constexpr (FE == 0) {
         for (int base = tid; base < total; base += 256 * 4) {
             float4 gv[4], zv[4];
 #pragma unroll
@@ -1103,6 +1127,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void l
                         for (int j = 0; j < 4 && c + j < n; ++j) a.dz_ws[off + j] = dzv[j];
                 }
             }
+        }
         }
     }
     RT_PP_MARK(0)
@@ -1167,8 +1192,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void l
     // fast epilogue (the C2 hidden layers): a full row block, g_prev only, a
     // piecewise-linear previous activation — no per-element predicates, 32-bit
     // offsets from one base pointer; its z_prev / BN loads are issued HERE,
-    // ahead of the reduction, so they land during the MFMAs
-    const bool fast = row0 + FM <= m && !a.dsrc && a.g_prev && act_is_piecewise_linear(a.prev_act);
+    // ahead of the reduction. In the all-paths two-tile instance the register
+    // cap makes the compiler wait for them and spill 9 of them before the
+    // loop; the FE instances keep them in registers (DESIGN §5 note n)
+    const bool fast = FE != 0 || (row0 + FM <= m && dz_da_fast(a));
     float zpre[TPWK][16], pmean[TPWK], pinv[TPWK];
 #pragma unroll
     for (int i = 0; i < TPWK; ++i) {
@@ -1177,8 +1204,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void l
         pmean[i] = ld ? a.prev_mean[my_seg * k + kk] : 0.f;
         pinv[i] = ld ? a.prev_invstd[my_seg * k + kk] : 0.f;
         const float* zp = a.src + (row0 + 4 * h) * a.ld_src + kk;
+        // (one branch around the 16 loads, not one per load)
+        if (ld) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) zpre[i][r] = ld ? zp[((r & 3) + 8 * (r >> 2)) * a.ld_src] : 0.f;
+            for (int r = 0; r < 16; ++r) zpre[i][r] = zp[((r & 3) + 8 * (r >> 2)) * a.ld_src];
+        } else {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) zpre[i][r] = 0.f;
+        }
     }
     if constexpr (WPL) {
         if constexpr (TPWK != 1) load_p(0, pn);
@@ -1248,7 +1281,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void l
                 s2 += gv * xh;
             }
             if (!want_stats || !col_ok) s1 = s2 = 0.f;
-        } else
+        } else if constexpr (FE == 0) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int64_t gr = row0 + (r & 3) + 8 * (r >> 2) + 4 * h;
@@ -1268,6 +1301,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void l
                     }
                 }
             }
+        }
         }
         if (want_stats) {
             s1 += __shfl_xor(s1, 32, 64);
@@ -1749,11 +1783,12 @@ __global__ __launch_bounds__(DW_NT) void linear_bwd_dw_joint_kernel(DwJointLaunc
 using namespace rt;
 
 // allow > 64 KiB of dynamic LDS (gfx950 has 160 KiB per CU); set once per kernel
-template <typename K>
-static void allow_lds(K kernel, size_t bytes) {
+// (the kernel is a template argument: one flag per instantiation, not per signature)
+template <auto Kernel>
+static void allow_lds(size_t bytes) {
     static size_t set = 0;
     if (bytes > set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                             static_cast<int>(bytes));
         set = bytes;
     }
@@ -1823,7 +1858,7 @@ extern "C" int rt_linear_fwd_f32_multi(const rt_linear_fwd_args* args, int n_arg
     const dim3 grid(total);
 #define RT_FWD(T, V, P)                                                                           \
     do {                                                                                          \
-        allow_lds(mlp::linear_fwd_kernel<T, V, P>, lds);                                          \
+        allow_lds<mlp::linear_fwd_kernel<T, V, P>>(lds);                                          \
         hipLaunchKernelGGL((mlp::linear_fwd_kernel<T, V, P>), grid, dim3(256), lds, st, L);       \
     } while (0)
     if (kvec && tpw == 1 && wpl) {
@@ -1858,6 +1893,21 @@ static bool all_dz_fusable(const rt_linear_bwd_args* args, int n_args) {
     return true;
 }
 
+// the fast-paths-only class (the dz kernel's FE) of an argument set: every block
+// takes one fast phase A and the fast dA epilogue (the kernel's own conditions,
+// which its FE instances drop): full row blocks, g_prev without dsrc,
+// piecewise-linear activations, Wᵀ given. 1: F.normalize backward, 2: BatchNorm
+// backward, 0: none (the instance that carries every path)
+static int dz_fast_class(const rt_linear_bwd_args& a) {
+#if defined(RT_DZ_NO_FE) || defined(RT_NO_WT_ROWS)  // A/B variants
+    return 0;
+#endif
+    if (!a.wt || (a.n % 8) != 0) return 0;  // dA reads W through Wᵀ's rows
+    if ((a.m % mlp::FM) != 0 || !mlp::dz_da_fast(a)) return 0;  // every row block full
+    if (a.grad_mode == 0) return mlp::dz_norm_fast(a.n) ? 1 : 0;
+    return ((a.grad_mode == 1 || a.grad_mode == 2) && mlp::dz_bn_fast(a.n, a.act, a.grad_mode)) ? 2 : 0;
+}
+
 static int validate_bwd(const rt_linear_bwd_args* args) {
     if (!args) return RT_ERR_INVALID;
     const rt_linear_bwd_args& a = *args;
@@ -1888,11 +1938,14 @@ extern "C" int rt_linear_bwd_dz_f32_multi(const rt_linear_bwd_args* args, int n_
     size_t lds = 0;
     unsigned blocks[2] = {0u, 0u};
     bool wpl = true;  // every argument set with a dA brings Wᵀ's planes
+    int fe = -1;      // the fast-paths-only class all argument sets share, or 0
     for (int g = 0; g < n_args; ++g) {
         const int v = validate_bwd(&args[g]);
         if (v) return v;
         const rt_linear_bwd_args& a = args[g];
         const bool need_da = a.g_prev || a.dsrc;
+        const int fc = dz_fast_class(a);
+        fe = (fe < 0 || fe == fc) ? fc : 0;
         wpl = wpl && (!need_da || a.wt_planes != nullptr);
         const int t = !need_da ? 1 : a.k <= 128 ? 1 : a.k <= 256 ? 2 : 4;
         tpwk = t > tpwk ? t : tpwk;
@@ -1926,18 +1979,28 @@ extern "C" int rt_linear_bwd_dz_f32_multi(const rt_linear_bwd_args* args, int n_
     if (ks == 2) tpwk = 1;
     const dim3 grid(total * ks);
     hipStream_t st = as_stream(stream);
-#define RT_DZ(T, P, K)                                                                        \
-    do {                                                                                      \
-        allow_lds(mlp::linear_bwd_dz_kernel<T, P, K>, lds);                                   \
-        hipLaunchKernelGGL((mlp::linear_bwd_dz_kernel<T, P, K>), grid, dim3(256), lds, st, L); \
+#define RT_DZ(T, P, K, F)                                                                        \
+    do {                                                                                         \
+        allow_lds<mlp::linear_bwd_dz_kernel<T, P, K, F>>(lds);                                   \
+        hipLaunchKernelGGL((mlp::linear_bwd_dz_kernel<T, P, K, F>), grid, dim3(256), lds, st, L); \
     } while (0)
     if (ks > 1) {
-        if (wpl) RT_DZ(1, true, true); else RT_DZ(1, false, true);
+        if (wpl) RT_DZ(1, true, true, 0); else RT_DZ(1, false, true, 0);
     } else {
         switch (tpwk) {
-            case 1: if (wpl) RT_DZ(1, true, false); else RT_DZ(1, false, false); break;
-            case 2: if (wpl) RT_DZ(2, true, false); else RT_DZ(2, false, false); break;
-            default: RT_DZ(4, false, false); break;
+            case 1:
+                if (wpl) RT_DZ(1, true, false, 0);
+                else if (fe == 1) RT_DZ(1, false, false, 1);
+                // (no <1, false, false, 2>: built, it spills 3 VGPRs where the all-paths instance spills none)
+                else RT_DZ(1, false, false, 0);
+                break;
+            case 2:
+                if (wpl) RT_DZ(2, true, false, 0);
+                else if (fe == 1) RT_DZ(2, false, false, 1);
+                else if (fe == 2) RT_DZ(2, false, false, 2);
+                else RT_DZ(2, false, false, 0);
+                break;
+            default: RT_DZ(4, false, false, 0); break;
         }
     }
 #undef RT_DZ
