@@ -718,6 +718,49 @@ int rt_rank_metrics(const int64_t* preds, int64_t n_rows, int list_len, const in
 int rt_rank_metrics_reduce(const double* per_row, const int32_t* valid, int64_t n_rows, int n_cols,
                            const uint32_t* coverage_bits, int64_t num_items, double* out, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Beyond-accuracy list metrics (src/evaluation/metrics.py:402-478,
+ * scripts/evaluate_model.py:309-338): intra-list diversity and novelty of
+ * device-resident rankings, every k in one pass.
+ *
+ * rt_list_metrics: per row r of preds [n_rows, list_len] int64 (-1 = no
+ *   item, the "present" rule of rt_rank_metrics) and per k of k_values (HOST
+ *   array of n_k ascending positive ints, n_k <= RT_METRICS_MAX_K), over the
+ *   first n = min(k, len(list)) entries of the row's list:
+ *   diversity (emb != NULL): mean over pairs i < j of 1 - ê_i·ê_j with
+ *     ê = e / (‖e‖ + 1e-8), computed in fp64 on the stored values as
+ *     1 - (‖Σ ê_i‖² - Σ ‖ê_i‖²) / (n(n-1)) (no K×K matrix). emb [n_emb, d]
+ *     of emb_dtype (rt_dtype) with a row stride of ld_emb >= d elements;
+ *     fp32: 1 <= d <= 1024, fp16 / bf16: d % 8 == 0, d <= 1024
+ *     (RT_ERR_UNSUPPORTED otherwise). 16-byte loads when d, ld_emb and the
+ *     base pointer allow, element loads otherwise. Every id is checked
+ *     against n_emb before its row is read; an id >= n_emb is not read, is
+ *     counted in oob_count (optional, caller-zeroed) and is left out of the
+ *     row's diversity list. div fp64 [n_rows][n_k]; div_valid int32
+ *     [n_rows][n_k] = 1 where n >= 2 (else 0 and div = 0).
+ *   novelty (info != NULL): info fp64 [n_info] holds each item's
+ *     self-information -log2(pop/total + 1e-10); ids >= n_info take
+ *     default_info (an item the popularity table does not hold: pop = 1).
+ *     nov_sum fp64 [n_rows][n_k] = Σ info over the first n entries, nov_cnt
+ *     int32 [n_rows][n_k] = n.
+ *   emb and info are each optional (not both NULL); a NULL operand's outputs
+ *   are not written. Every argument is validated before any device work;
+ *   n_rows == 0 returns RT_OK. No floating-point atomics: two calls on the
+ *   same inputs return the same bits.
+ *
+ * rt_list_metrics_reduce: out fp64 [4][n_k] = the mean of div over the rows
+ *   valid at k (0 when none), the number of those rows, Σ nov_sum / Σ nov_cnt
+ *   (the reference's flat mean over entries; 0 when none), Σ nov_cnt. A NULL
+ *   pair (div, div_valid) or (nov_sum, nov_cnt) gives zeros. Fixed summation
+ *   order (deterministic).
+ * ------------------------------------------------------------------------ */
+int rt_list_metrics(const int64_t* preds, int64_t n_rows, int list_len, const void* emb, int emb_dtype,
+                    int64_t n_emb, int d, int64_t ld_emb, const double* info, int64_t n_info, double default_info,
+                    const int32_t* k_values, int n_k, double* div, int32_t* div_valid, double* nov_sum,
+                    int32_t* nov_cnt, int32_t* oob_count, void* stream);
+int rt_list_metrics_reduce(const double* div, const int32_t* div_valid, const double* nov_sum,
+                           const int32_t* nov_cnt, int64_t n_rows, int n_k, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

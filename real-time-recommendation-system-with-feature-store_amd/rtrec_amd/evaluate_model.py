@@ -6,8 +6,11 @@ user / movie feature tables), load the checkpoint (architecture inferred from
 its weight shapes), masked top-max(k) recommendations for every test user,
 ``Evaluator.evaluate``, JSON results. Every step after loading runs on the
 MI355X (``generate_recommendations`` → rt_exclusion_bitmap + rt_flatip_topk,
-metrics → rt_rank_metrics). Diversity / novelty (metrics.py:402-527) are
-outside the hot-path scope and not computed. Without ``ml-1m/ratings.dat``
+metrics → rt_rank_metrics). ``diversity@10`` / ``novelty@10``
+(evaluate_model.py:309-338, metrics.py:402-478) come from ``beyond_accuracy``:
+the same device ids, the model's item embeddings and a ``bincount`` of the
+training interactions go to rt_list_metrics; the ranking is copied to the host
+once, for the dict the Evaluator takes. Without ``ml-1m/ratings.dat``
 (not shipped with the reference) the seeded ML-1M-shaped stream is used.
 
     python -m rtrec_amd.evaluate_model --checkpoint models/checkpoints/two_tower_best.pth
@@ -53,8 +56,31 @@ def prepare_evaluation_data(data):
     return train_items, test_ground_truth, uf, mf
 
 
+def beyond_accuracy(model, ids, movie_features, train_movie_idx, k: int = 10) -> dict:
+    """evaluate_model.py:309-331 on the device: ``diversity@k`` of the ranking
+    ``ids`` [U, top_k] (device int64, -1 = no item) over the model's own item
+    embeddings, and ``novelty@k`` against the popularity of the training
+    interactions (one count per ``train_movie_idx`` entry, the reference's
+    ``value_counts``). Neither the ids nor the embeddings visit the host."""
+    import torch
+
+    from .evaluation import list_metrics_tensors, self_information
+    dev = ids.device
+    mf = torch.as_tensor(np.asarray(movie_features, np.float32)) if not isinstance(movie_features, torch.Tensor) \
+        else movie_features
+    with torch.no_grad():
+        item_emb = model.get_item_embeddings({"numerical": mf.to(dev), "categorical": {}})
+    idx = torch.as_tensor(np.asarray(train_movie_idx, np.int64)) if not isinstance(train_movie_idx, torch.Tensor) \
+        else train_movie_idx
+    counts = torch.bincount(idx.to(dev).to(torch.int64), minlength=int(mf.shape[0]))
+    info, default = self_information(counts)
+    res = list_metrics_tensors(ids, [int(k)], item_embeddings=item_emb.detach().contiguous(), item_info=info,
+                               default_info=default)
+    return {f"diversity@{k}": res.diversity[int(k)], f"novelty@{k}": res.novelty[int(k)]}
+
+
 def run(args) -> dict:
-    from .evaluation import Evaluator, generate_recommendations, load_model
+    from .evaluation import Evaluator, generate_recommendations, load_model, recommendations_from_ids
     from .train_movielens import load_data
     k_values = [int(k) for k in args.k_values.split(",")]
     data, source = load_data(argparse.Namespace(data_path=args.data_path, synthetic=args.synthetic))
@@ -63,12 +89,15 @@ def run(args) -> dict:
     model = load_model(args.checkpoint, user_dim=uf.shape[1], item_dim=mf.shape[1], device=device)
     test_users = list(gt.keys())
     t0 = time.time()
-    recs = generate_recommendations(model, test_users, train_items, uf, mf, top_k=max(k_values),
-                                    batch_size=args.batch_size, device=device)
+    _, ids = generate_recommendations(model, test_users, train_items, uf, mf, top_k=max(k_values),
+                                      batch_size=args.batch_size, device=device, return_tensors=True)
+    recs = recommendations_from_ids(ids, test_users)
     t_recs = time.time() - t0
     evaluator = Evaluator(k_values=k_values, num_items=mf.shape[0])
     metrics = evaluator.evaluate(recs, gt, exclude_items=train_items)
     results = metrics.to_dict()
+    # diversity / novelty of the same device ids (k fixed at 10, evaluate_model.py:320-328)
+    results.update(beyond_accuracy(model, ids, mf, data.train_interactions["movie_idx"].to_numpy(), k=10))
     results.update({"num_test_users": len(test_users), "num_items": int(mf.shape[0]), "checkpoint": args.checkpoint,
                     "data": source, "recommendation_seconds": t_recs})
     out = Path(args.output)
@@ -81,6 +110,8 @@ def main(argv: Optional[List[str]] = None) -> int:
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(levelname)s %(name)s: %(message)s")
     res = run(build_parser().parse_args(argv))
     print("\n" + str(res["metrics"]))
+    print(f"Diversity@10: {res['results']['diversity@10']:.4f}")
+    print(f"Novelty@10:   {res['results']['novelty@10']:.4f}")
     return 0
 
 

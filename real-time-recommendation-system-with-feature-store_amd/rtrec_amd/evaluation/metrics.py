@@ -15,6 +15,16 @@ Contract differences, stated: a prediction list may not repeat a ground-truth
 item (the top-K kernels never emit duplicates; the reference would count such
 a repeat once in recall but twice in NDCG), and ids must be >= 0 (-1 pads a
 ragged list). Both raise ``ValueError`` in the dict path.
+
+Beyond accuracy (metrics.py:402-478): ``compute_diversity`` and
+``compute_novelty`` keep the reference's signatures (plus ``device``);
+``list_metrics_tensors`` is their device-resident form for several k at once
+and ``self_information`` builds the novelty table. Both come from
+``rt_list_metrics`` (one wave per list, fp64, the pair sum through
+‖Σ ê‖² − Σ ‖ê‖² instead of the K×K similarity matrix) and
+``rt_list_metrics_reduce``. Contract differences, stated: negative ids raise
+``ValueError`` (numpy would index from the end), and a float64 embedding array
+is rounded to fp32 first (the kernel reads fp32 / fp16 / bf16 tables).
 """
 from __future__ import annotations
 
@@ -186,6 +196,122 @@ class Evaluator:
         ids = list(item_ids)
         predictions = {u: [ids[i] for i in recs[u]] for u in test_users}
         return self.evaluate(predictions, test_ground_truth)
+
+
+@dataclass
+class ListMetrics:
+    """Result of ``list_metrics_tensors``: per-k summaries on the host, per-row
+    diversity on the device."""
+    diversity: Dict[int, float] = field(default_factory=dict)
+    novelty: Dict[int, float] = field(default_factory=dict)
+    per_row_diversity: Optional[torch.Tensor] = None   # fp64 [n_rows, n_k], 0 where not valid
+    diversity_valid: Optional[torch.Tensor] = None     # int32 [n_rows, n_k]: the row has >= 2 items at this k
+    diversity_rows: Dict[int, int] = field(default_factory=dict)    # rows averaged per k
+    novelty_entries: Dict[int, int] = field(default_factory=dict)   # list entries averaged per k
+
+
+def self_information(counts, total: Optional[float] = None):
+    """The novelty table of ``compute_novelty`` (metrics.py:467-476): (info fp64
+    [n_info], default) with ``info[i] = -log2(pop_i / total + 1e-10)`` and
+    ``default`` the value of an item the popularity table does not hold (pop 1).
+    ``counts`` is the reference's ``{item: count}`` dict (a host table comes
+    back) or a per-item count tensor such as a ``bincount`` (a zero count means
+    absent; the table stays on the tensor's device). ``total`` defaults to the
+    sum of the counts held; a zero total raises ``ZeroDivisionError`` as the
+    reference's division does."""
+    if isinstance(counts, dict):
+        keys = np.fromiter((int(i) for i in counts.keys()), np.int64, len(counts))
+        vals = np.fromiter((float(v) for v in counts.values()), np.float64, len(counts))
+        if keys.size and keys.min() < 0:
+            raise ValueError("item ids must be >= 0")
+        tot = float(sum(counts.values())) if total is None else float(total)
+        if tot == 0.0:
+            raise ZeroDivisionError("division by zero: the item popularity table sums to 0")
+        default = float(-np.log2(1.0 / tot + 1e-10))
+        info = np.full(int(keys.max()) + 1 if keys.size else 0, default, np.float64)
+        info[keys] = -np.log2(vals / tot + 1e-10)
+        return torch.from_numpy(info), default
+    c = torch.as_tensor(counts)
+    if c.dim() != 1:
+        raise ValueError("a count tensor must be 1-D, one count per item")
+    c = c.to(torch.float64)
+    tot = float(c.sum().item()) if total is None else float(total)
+    if tot == 0.0:
+        raise ZeroDivisionError("division by zero: the item popularity table sums to 0")
+    pop = torch.where(c > 0, c, torch.ones_like(c))
+    return -torch.log2(pop / tot + 1e-10), float(-np.log2(1.0 / tot + 1e-10))
+
+
+def list_metrics_tensors(preds: torch.Tensor, k_values: Sequence[int],
+                         item_embeddings: Optional[torch.Tensor] = None, item_info: Optional[torch.Tensor] = None,
+                         default_info: Optional[float] = None) -> ListMetrics:
+    """compute_diversity / compute_novelty on device-resident rankings [n, L]
+    (-1 = no item) for every k of ``k_values`` in one pass. ``item_embeddings``
+    [num_items, d] fp32 / fp16 / bf16 and ``item_info`` / ``default_info`` (from
+    ``self_information``) are each optional; a metric without its operand is
+    left out of the result."""
+    if item_info is not None and default_info is None:
+        raise ValueError("item_info needs default_info (self_information returns both)")
+    ks = sorted(int(k) for k in k_values)
+    div, valid, _, _, summary = kernels.list_metrics(preds, ks, emb=item_embeddings, info=item_info,
+                                                     default_info=0.0 if default_info is None else default_info)
+    s = summary.cpu().numpy()
+    out = ListMetrics(per_row_diversity=div, diversity_valid=valid)
+    for i, k in enumerate(ks):
+        if item_embeddings is not None:
+            out.diversity[k] = float(s[0, i])
+            out.diversity_rows[k] = int(s[1, i])
+        if item_info is not None:
+            out.novelty[k] = float(s[2, i])
+            out.novelty_entries[k] = int(s[3, i])
+    return out
+
+
+def _embedding_table(item_embeddings, dev) -> torch.Tensor:
+    if isinstance(item_embeddings, torch.Tensor):
+        t = item_embeddings.detach()
+        if t.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            t = t.to(torch.float32)
+        return t if t.device.type == "cuda" else t.to(dev)
+    return torch.from_numpy(np.ascontiguousarray(item_embeddings, dtype=np.float32)).to(dev)
+
+
+def _list_device(device, *tensors) -> torch.device:
+    for t in tensors:
+        if isinstance(t, torch.Tensor) and t.device.type == "cuda":
+            return t.device  # a device tensor is used where it lies
+    return _device(device)
+
+
+def compute_diversity(recommendations: Dict[int, List[int]], item_embeddings, k: int = 10, device=None) -> float:
+    """metrics.py:402-446: mean over users with at least two items in their first
+    ``k`` of the mean pairwise cosine distance ``1 - ê_i·ê_j``, ``ê = e / (‖e‖ +
+    1e-8)``; 0.0 when no user qualifies. ``item_embeddings`` is a numpy array
+    or a tensor (a device tensor is used in place). Ids past the table raise
+    ``IndexError`` as numpy does; negative ids raise ``ValueError``."""
+    dev = _list_device(device, item_embeddings)
+    lists = [list(x)[:int(k)] for x in recommendations.values()]
+    if not lists:
+        return 0.0
+    res = list_metrics_tensors(_pack_predictions(lists, dev), [int(k)],
+                               item_embeddings=_embedding_table(item_embeddings, dev))
+    return res.diversity[int(k)]
+
+
+def compute_novelty(recommendations: Dict[int, List[int]], item_popularity: Dict[int, int], k: int = 10,
+                    device=None) -> float:
+    """metrics.py:449-478: flat mean over every entry of every user's first ``k``
+    of ``-log2(pop / total + 1e-10)``, ``pop`` the item's count (1 for an item
+    ``item_popularity`` does not hold) and ``total`` the sum of the counts; 0.0
+    without entries. An all-zero or empty table with non-empty lists raises
+    ``ZeroDivisionError``."""
+    dev = _list_device(device)
+    lists = [list(x)[:int(k)] for x in recommendations.values()]
+    if not any(len(x) for x in lists):
+        return 0.0
+    info, default = self_information(dict(item_popularity))
+    res = list_metrics_tensors(_pack_predictions(lists, dev), [int(k)], item_info=info.to(dev), default_info=default)
+    return res.novelty[int(k)]
 
 
 def _single(predicted: List[int], ground_truth: Set[int], k: int):

@@ -76,6 +76,13 @@ def _pad_like_reference(ids_row: np.ndarray, scores_row: np.ndarray, n_items: in
     return [int(x) for x in np.argsort(row)[::-1][:top_k]]
 
 
+def recommendations_from_ids(ids: torch.Tensor, users: Sequence[int]) -> Dict[int, List[int]]:
+    """Dict[user_idx, List[movie_idx]] from device ids [U, top_k] (row r belongs to
+    ``users[r]``; -1 = no item): the one host copy of a ranking."""
+    host = ids.cpu().numpy()
+    return {int(u): [int(x) for x in host[r] if x >= 0] for r, u in enumerate(users)}
+
+
 def generate_recommendations(model: TwoTowerModel, test_users: list, train_items: Dict[int, list],
                              user_features: np.ndarray, movie_features: np.ndarray, top_k: int = 100,
                              batch_size: int = 256, device: Optional[str] = None,
@@ -98,9 +105,9 @@ def generate_recommendations(model: TwoTowerModel, test_users: list, train_items
                                     t_items, top_k=top_k, batch_size=batch_size)
     if return_tensors:
         return scores, ids
-    host = ids.cpu().numpy()
     if not pad_excluded:
-        return {u: [int(x) for x in host[r] if x >= 0] for r, u in enumerate(users)}
+        return recommendations_from_ids(ids, users)
+    host = ids.cpu().numpy()
     n_items = mf.shape[0]
     host_s = scores.cpu().numpy()
     out = {}

@@ -597,6 +597,68 @@ def rank_metrics(preds: torch.Tensor, gt_offsets: torch.Tensor, gt_items: torch.
     return per_row, valid, summary
 
 
+def list_metrics(preds: torch.Tensor, k_values, emb: Optional[torch.Tensor] = None,
+                 info: Optional[torch.Tensor] = None, default_info: float = 0.0):
+    """Intra-list diversity and novelty of device-resident rankings
+    (src/evaluation/metrics.py:402-478) for every k in one pass
+    (rt_list_metrics + rt_list_metrics_reduce). ``preds`` int64 [n, L] (-1 = no
+    item); ``emb`` [n_emb, d] fp32 / fp16 / bf16 (a row stride is kept) and
+    ``info`` fp64 [n_info] self-information (ids past it take ``default_info``)
+    are each optional. Returns (div fp64 [n, n_k], div_valid int32 [n, n_k],
+    nov_sum fp64 [n, n_k], nov_cnt int32 [n, n_k], summary fp64 [4, n_k] =
+    diversity mean over valid rows, valid rows, novelty mean over entries,
+    entries); a metric whose operand is None returns None tensors and zeros in
+    the summary. Raises IndexError when a list holds an id >= n_emb (the kernel
+    does not read it; costs a device sync)."""
+    native.require_device(preds, emb, info, what="list_metrics")
+    if emb is None and info is None:
+        raise ValueError("list_metrics needs an embedding table, a self-information table, or both")
+    if preds.dim() != 2:
+        raise ValueError("preds must be [n_rows, list_len]")
+    preds = preds.contiguous().to(torch.int64)
+    ks = [int(k) for k in k_values]
+    if not ks or len(ks) > native.RT_METRICS_MAX_K or sorted(set(ks)) != ks or ks[0] <= 0:
+        raise ValueError(f"k_values must be 1..{native.RT_METRICS_MAX_K} ascending positive ints")
+    n, L = preds.shape
+    nk = len(ks)
+    dev = preds.device
+    div = valid = nov_sum = nov_cnt = oob = None
+    dt, n_emb, d, ld = 0, 0, 0, 0
+    if emb is not None:
+        if emb.dim() != 2:
+            raise ValueError("emb must be [n_emb, d]")
+        dt = native.dtype_code(emb.dtype)
+        n_emb, d = emb.shape
+        if d < 1 or d > 1024 or (dt != native.RT_F32 and d % 8):
+            raise ValueError(f"list_metrics: d = {d} unsupported for {emb.dtype} "
+                             "(fp32: 1..1024; fp16 / bf16: a multiple of 8 up to 1024)")
+        if n_emb > 1 and emb.stride(1) == 1 and emb.stride(0) >= d:
+            ld = emb.stride(0)  # a row-strided view (a slice of the index's stored rows) is read in place
+        else:
+            emb, ld = emb.contiguous(), d
+        div = torch.empty((n, nk), dtype=torch.float64, device=dev)
+        valid = torch.empty((n, nk), dtype=torch.int32, device=dev)
+        oob = torch.zeros(1, dtype=torch.int32, device=dev)
+    if info is not None:
+        if info.dim() != 1 or info.dtype != torch.float64:
+            raise TypeError("info must be a 1-D float64 tensor")
+        info = info.contiguous()
+        nov_sum = torch.empty((n, nk), dtype=torch.float64, device=dev)
+        nov_cnt = torch.empty((n, nk), dtype=torch.int32, device=dev)
+    karr = (ctypes.c_int32 * nk)(*ks)
+    st = stream_of(preds)
+    gather_bytes = float(n) * L * d * (emb.element_size() if emb is not None else 0)
+    with TIMER.region("list_metrics", bytes_=gather_bytes + 8.0 * n * L):
+        call("rt_list_metrics", ptr(preds), n, L, ptr(emb), dt, n_emb, d, ld, ptr(info),
+             info.numel() if info is not None else 0, float(default_info), karr, nk, ptr(div), ptr(valid),
+             ptr(nov_sum), ptr(nov_cnt), ptr(oob), st)
+        summary = torch.empty((4, nk), dtype=torch.float64, device=dev)
+        call("rt_list_metrics_reduce", ptr(div), ptr(valid), ptr(nov_sum), ptr(nov_cnt), n, nk, ptr(summary), st)
+    if oob is not None and int(oob.item()) != 0:
+        raise IndexError(f"{int(oob.item())} ids out of range for an embedding table of {n_emb} rows")
+    return div, valid, nov_sum, nov_cnt, summary
+
+
 def sample_negatives(pos_offsets: torch.Tensor, pos_items: torch.Tensor, users: torch.Tensor, num_items: int,
                      num_neg: int, seed: int, seed_offset: Optional[torch.Tensor] = None,
                      out: Optional[torch.Tensor] = None) -> torch.Tensor:

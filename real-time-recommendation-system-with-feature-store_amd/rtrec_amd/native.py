@@ -169,6 +169,9 @@ SIGNATURES = {
     "rt_rank_metrics": (c_int, [vp, c_i64, c_int, vp, vp, vp, c_i64, vp, vp, vp, c_i64, vp, c_int, c_i64, vp, vp,
                                 vp, vp]),
     "rt_rank_metrics_reduce": (c_int, [vp, vp, c_i64, c_int, vp, c_i64, vp, vp]),
+    "rt_list_metrics": (c_int, [vp, c_i64, c_int, vp, c_int, c_i64, c_int, c_i64, vp, c_i64, ctypes.c_double, vp,
+                                c_int, vp, vp, vp, vp, vp, vp]),
+    "rt_list_metrics_reduce": (c_int, [vp, vp, vp, vp, c_i64, c_int, vp, vp]),
 }
 
 RT_METRICS_MAX_K = 16

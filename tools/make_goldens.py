@@ -414,6 +414,45 @@ def gen_reference_r3(ref: Path, out: Path):
     _save(out, "ckpt_ref_moments", **moments)
 
 
+def gen_reference_r4(ref: Path, out: Path):
+    """Beyond-accuracy fixture: the reference compute_diversity / compute_novelty
+    (src/evaluation/metrics.py:402-478) on ragged lists over a spread and a
+    tightly clustered embedding table, at k = 2, 10, 100. The float64 values
+    (the reference fed float64 copies of the fp32 tables) are the yardstick; its
+    values on the fp32 tables themselves are recorded for the record only (its
+    float32 arithmetic moves them by up to ~1e-7)."""
+    sys.path.insert(0, str(HERE / "loguru_stub"))
+    sys.path.insert(0, str(ref))
+    from src.evaluation.metrics import compute_diversity, compute_novelty  # noqa: E402
+
+    print("reference compute_diversity / compute_novelty")
+    rng = np.random.default_rng(77)
+    n_items, d, n_lists, width = 300, 64, 40, 100
+    table = rng.standard_normal((n_items, d))
+    table *= (rng.uniform(0.1, 3.0, (n_items, 1)) / np.linalg.norm(table, axis=1, keepdims=True))
+    table = table.astype(np.float32)
+    common = rng.standard_normal(d)
+    clustered = (0.05 * table + (common / np.linalg.norm(common))[None, :]).astype(np.float32)
+    lengths = rng.integers(3, width + 1, n_lists)
+    lengths[:4] = [1, 2, 0, width]
+    lists = np.full((n_lists, width), -1, np.int64)
+    for r, n in enumerate(lengths):
+        lists[r, :n] = rng.choice(n_items, int(n), replace=False)
+    held = np.array([i for i in range(n_items) if i % 7 != 6], np.int64)  # every seventh item is left out
+    counts = rng.integers(1, 5000, held.size).astype(np.int64)
+    recs = {r: [int(x) for x in lists[r] if x >= 0] for r in range(n_lists)}
+    pop = {int(i): int(c) for i, c in zip(held, counts)}
+    ks = np.array([2, 10, 100], np.int64)
+    res = {}
+    for name, t in (("table", table), ("clustered", clustered)):
+        res[f"div64_{name}"] = np.array([compute_diversity(recs, t.astype(np.float64), k=int(k)) for k in ks],
+                                        np.float64)
+        res[f"div32_{name}"] = np.array([compute_diversity(recs, t, k=int(k)) for k in ks], np.float64)
+    nov = np.array([compute_novelty(recs, pop, k=int(k)) for k in ks], np.float64)
+    _save(out, "beyond_accuracy", table=table, clustered=clustered, lists=lists, pop_items=held, pop_counts=counts,
+          k_values=ks, novelty=nov, **res)
+
+
 def _dyadic_unit(rng, n, d, nnz=16):
     """Unit-norm rows with `nnz` entries of ±1/4 (nnz=16): the renorm is exactly
     the identity and every inner product is an exact multiple of 1/16."""
@@ -480,7 +519,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref", default="/root/reference")
     ap.add_argument("--out", default=str(HERE.parent / "tests" / "golden"))
-    ap.add_argument("--only", choices=["reference", "dyadic", "r2", "r3"], default=None)
+    ap.add_argument("--only", choices=["reference", "dyadic", "r2", "r3", "r4"], default=None)
     a = ap.parse_args()
     out = Path(a.out)
     if a.only in (None, "dyadic"):
@@ -499,6 +538,10 @@ def main():
         ref = Path(a.ref)
         if (ref / "src" / "models" / "two_tower.py").exists():
             gen_reference_r3(ref, out)
+    if a.only in (None, "reference", "r4"):
+        ref = Path(a.ref)
+        if (ref / "src" / "models" / "two_tower.py").exists():
+            gen_reference_r4(ref, out)
 
 
 if __name__ == "__main__":
