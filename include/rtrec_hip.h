@@ -194,6 +194,84 @@ int rt_flatip_topk_online_lists(const void* queries, int64_t nq, const void* ite
                                 float* out_scores, int64_t* out_ids, void* workspace, size_t workspace_bytes,
                                 void* stream);
 
+/* ------------------------------------------------------------------------
+ * IVF-Flat (faiss.index_factory(d, "IVF1024,Flat") with index.nprobe = 20,
+ * the reference's default index: src/serving/retrieval.py:60-62, 101-133;
+ * searched at :141-197).
+ *
+ * rt_ivf_topk: top-k over the union of the probed lists (the scan that
+ *   faiss.IndexIVFFlat.search runs after its coarse quantiser, :171).
+ *   queries [nq, d] and rows [nx, d], both `dtype`, rows 16-byte aligned; d and
+ *   dtype limits of rt_flatip_topk_online (f32: d % 4 == 0, f16/bf16: d % 8 ==
+ *   0, d <= 256); 1 <= k <= RT_IVF_MAX_K; 1 <= nprobe <= RT_IVF_MAX_NPROBE;
+ *   nq <= 65,535 per call; nx < 2^31 - 1.
+ *   rows are stored list-contiguous: list l is the stored rows
+ *   [list_offsets[l], list_offsets[l + 1]) (int64 [nlist + 1], device);
+ *   row_pos[i] (int32 [nx], device) is the ORIGINAL corpus position of stored
+ *   row i. probes (int64 [nq, nprobe], device): list ids, exactly what
+ *   rt_flatip_topk / rt_flatip_topk_online write as out_ids over the
+ *   centroids; an entry of -1 or outside [0, nlist) is skipped; a list named
+ *   twice in a probe row may repeat its rows in the result, nothing worse.
+ *   max_list_rows (host): an upper bound of the longest list; with nq and
+ *   nprobe it fixes the grid, so the call makes no host read, is
+ *   stream-ordered and can be captured in a graph. A list longer than
+ *   max_list_rows is the caller's error: its rows past the bound are not
+ *   scanned; nothing outside the list or the corpus is ever read, whatever
+ *   the offsets hold, and a row whose row_pos is outside [0, nx) is dropped.
+ *   exclude_bits: optional uint32 [nq, exclude_words], indexed by ORIGINAL
+ *   position (the convention of rt_flatip_topk); exclude_words >=
+ *   ceil(nx / 32).
+ *   Result rows: the contract of rt_flatip_topk over the union of the probed
+ *   lists — the first k in (score desc, original position asc) order,
+ *   out_ids = original position, unfilled slots (-FLT_MAX, -1); fp32 scores
+ *   are the sequential fmaf chain (bit-identical to the oracle), f16/bf16
+ *   scores the same chain over the widened elements. With every list probed
+ *   the result is rt_flatip_topk's over the corpus in original order, bit
+ *   for bit.
+ *   Status, before any device work: RT_ERR_INVALID for a NULL operand
+ *   (rows / row_pos may be NULL when nx == 0), k <= 0, nprobe <= 0, nlist <=
+ *   0, a negative size, an unknown dtype, misaligned queries / rows /
+ *   workspace (8 bytes), exclude_words too small; RT_ERR_UNSUPPORTED for
+ *   k > RT_IVF_MAX_K, nprobe > RT_IVF_MAX_NPROBE, nq > 65,535, a refused
+ *   d / dtype pair, nx >= 2^31 - 1; RT_ERR_WORKSPACE. nq == 0: RT_OK.
+ * rt_ivf_topk_plan: host only. out = {chunks per list, rows per chunk, scan
+ *   blocks}: a probed list is scanned by `chunks` blocks of `rows per chunk`
+ *   rows (a multiple of 256; chunks x rows >= max_list_rows), blocks = nq x
+ *   nprobe x chunks, and nprobe x chunks <= 512 (the finish's lists per query).
+ *   The smallest chunk that rule allows: at nq = 1 the blocks are all the
+ *   parallelism a call has.
+ * rt_ivf_topk_workspace_bytes: the partial lists [nq][k][nprobe x chunks] of
+ *   8-byte composite keys (256 for a refused shape).
+ * rt_ivf_topk_tuning: process-wide floor of the chunk, in 256-row tiles
+ *   (0 = the default, 1), for measurements; changes the plan, never a result.
+ *
+ * rt_segment_mean_f32: the centroid update of one Lloyd step (the mean that
+ *   faiss.Clustering.train computes per centroid inside index.train, :131).
+ *   rows [n, d] of `dtype` (d / dtype limits as above, 16-byte aligned)
+ *   grouped by segment; offsets int64 [n_seg + 1] (device): segment s is the
+ *   rows [offsets[s], offsets[s + 1]), clamped to [0, n]. out[s] (fp32
+ *   [n_seg, d]) = the mean of the segment's rows, accumulated in fp64 in an
+ *   order that depends on the segment's length and d only (no atomics: the
+ *   same input gives the same bits), rounded once to fp32; an empty segment
+ *   copies prev[s] (fp32 [n_seg, d]); normalize != 0 rescales every non-empty
+ *   result to unit L2 norm in fp64 before the rounding (spherical k-means for
+ *   the cosine metric; a zero mean stays zero).
+ *   Status: RT_ERR_INVALID for a NULL offsets / prev / out (rows may be NULL
+ *   when n == 0), negative sizes, d <= 0, an unknown dtype, misaligned rows;
+ *   RT_ERR_UNSUPPORTED for a refused d / dtype pair. n_seg == 0: RT_OK.
+ * ------------------------------------------------------------------------ */
+#define RT_IVF_MAX_K 128
+#define RT_IVF_MAX_NPROBE 128
+int rt_ivf_topk_tuning(int min_chunk_tiles);
+int rt_ivf_topk_plan(int64_t nq, int nprobe, int64_t max_list_rows, int64_t* out);
+size_t rt_ivf_topk_workspace_bytes(int64_t nq, int nprobe, int64_t max_list_rows, int k);
+int rt_ivf_topk(const void* queries, int64_t nq, const void* rows, int64_t nx, int d, int dtype,
+                const int64_t* list_offsets, int64_t nlist, const int32_t* row_pos, const int64_t* probes,
+                int nprobe, int64_t max_list_rows, int k, const uint32_t* exclude_bits, int64_t exclude_words,
+                float* out_scores, int64_t* out_ids, void* workspace, size_t workspace_bytes, void* stream);
+int rt_segment_mean_f32(const void* rows, int64_t n, int d, int dtype, const int64_t* offsets, int64_t n_seg,
+                        const float* prev, int normalize, float* out, void* stream);
+
 /* Corpus-sharded search with ONE corpus-wide threshold per query (several
  * GPUs, each holding a row shard of the corpus that faiss.IndexFlatIP.search
  * would scan whole, src/serving/retrieval.py:141-197): every rank samples its

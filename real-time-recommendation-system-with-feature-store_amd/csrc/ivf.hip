@@ -1,0 +1,408 @@
+// IVF-Flat: the probed-list scan (rt_ivf_topk) and the centroid update of one
+// Lloyd step (rt_segment_mean_f32). Serves the reference's default index,
+// faiss.index_factory(d, "IVF1024,Flat") searched with nprobe = 20
+// (src/serving/retrieval.py:60-62, 101-133, 141-197).
+//
+// rt_ivf_topk, two launches:
+//
+// 1. ivf_scan: grid (probe x chunk, query). The corpus is stored
+//    list-contiguous; block (p, c) of query q reads probes[q][p], clamps chunk c
+//    of that list to [off[l], off[l + 1]) and to [0, nx), and leaves at once
+//    (its partial list all "none") when nothing is left. Otherwise it is the
+//    online scan (topk_online.h) for ONE query: a wave walks 64-row groups of
+//    256-row tiles, one lane per row, 128 B of every row per step through
+//    registers into the padded LDS stage, the query in LDS as fp32, every score
+//    one lane's chain acc = fmaf(q[j], x[j], acc), j ascending: the chain of
+//    oracle/flatip.c, so scores are bit-identical to the Flat index's. What
+//    differs from the online scan is the id: a candidate carries the ORIGINAL
+//    corpus position row_pos[row], the exclusion bitmap is indexed by it, and
+//    the composite key (score key << 32 | ~position) holds the tie rule — the
+//    storage order does not reach the result. Rows therefore do NOT arrive in
+//    id order, and the filter threshold after a compaction is the lowest score
+//    kept (an equal later score may still win on its position), never the
+//    "strictly above" of compact_stream's tie case.
+// 2. flatip_online_finish (topk_online.h, unchanged): one block per query over
+//    the nprobe x chunks <= 512 sorted partial lists.
+//
+// The grid depends on host arguments only (nq, nprobe, max_list_rows): no host
+// read, stream-ordered, capturable.
+#include "topk_online.h"
+
+namespace rt {
+namespace topk {
+namespace ivf {
+
+namespace on = rt::topk::online;
+
+constexpr int kMaxProbe = 128;                // RT_IVF_MAX_NPROBE
+constexpr int kMaxLists = on::kMaxBlocks;     // partial lists per query the finish takes (one thread each)
+constexpr int64_t kMaxNq = 65535;             // grid.y
+static_assert(kMaxProbe <= kMaxLists, "ivf: one partial list per probe at least");
+
+struct Plan {
+    int chunks;              // per probed list
+    int64_t rows_per_chunk;  // a multiple of the scan's 256-row tile
+};
+
+// Smallest chunks (>= min_tiles tiles) that keep nprobe x chunks within the
+// finish's 512 lists: at nq = 1 the blocks of a call are all the parallelism
+// there is (20 probes of ~1,000 rows = 80 blocks of one tile, not 20).
+inline Plan make_plan(int nprobe, int64_t max_list_rows, int min_tiles) {
+    const int64_t tile = on::kTileRows;
+    const int64_t mlr = max_list_rows > 0 ? max_list_rows : 1;
+    const int64_t cap = kMaxLists / (nprobe > 0 ? nprobe : 1);  // >= 4
+    int64_t tiles = (mlr + tile - 1) / tile;
+    int64_t tpc = (tiles + cap - 1) / cap;  // tiles per chunk
+    if (tpc < min_tiles) tpc = min_tiles;
+    Plan p;
+    p.rows_per_chunk = tpc * tile;
+    p.chunks = static_cast<int>((mlr + p.rows_per_chunk - 1) / p.rows_per_chunk);
+    return p;
+}
+
+// wave: compact one candidate buffer; thr = the lowest score kept
+__device__ __forceinline__ void compact_keep_ties(Cand* buf, int& n, int k, int limit, uint32_t* hist, float& thr) {
+    const int lane = threadIdx.x & 63;
+    float unused = 0.f;
+    v4::compact_stream(buf, n, k, limit, hist, unused);
+    wave_lds_sync();
+    float lo = INFINITY;
+    for (int i = lane; i < n; i += 64) lo = fminf(lo, buf[i].s);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) lo = fminf(lo, __shfl_xor(lo, o, 64));
+    thr = lo;
+}
+
+template <typename T>
+__global__ __launch_bounds__(on::kThreads, 2) void ivf_scan(
+    const T* __restrict__ Q, const char* __restrict__ X, int64_t nx, int d, int k,
+    const int64_t* __restrict__ list_offsets, int64_t nlist, const int32_t* __restrict__ row_pos,
+    const int64_t* __restrict__ probes, int nprobe, int chunks, int64_t rows_per_chunk,
+    const uint32_t* __restrict__ excl, int64_t excl_words, uint64_t* __restrict__ partials) {
+    constexpr int EPU = 16 / static_cast<int>(sizeof(T));
+    constexpr int kThreads = on::kThreads, kTileRows = on::kTileRows, kStepUnits = on::kStepUnits;
+    constexpr int kRowStride = on::kRowStride, kRoom = on::kRoom;
+    using L = on::Lds<1>;
+    __shared__ __attribute__((aligned(16))) char lds[L::kBytes];
+    __shared__ int cnt;
+    __shared__ float thr;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lists = nprobe * chunks;
+    const int lb = blockIdx.x, q = blockIdx.y;
+    const int p = lb / chunks, c = lb - p * chunks;
+    uint64_t* const out = partials + static_cast<int64_t>(q) * k * lists + lb;  // [q][rank][lb]
+
+    // the chunk, clamped to the list and to the corpus
+    int64_t row_begin = 0, row_end = 0;
+    const int64_t l = probes[static_cast<int64_t>(q) * nprobe + p];
+    if (l >= 0 && l < nlist) {
+        int64_t lo = list_offsets[l], hi = list_offsets[l + 1];
+        lo = lo < 0 ? 0 : lo;
+        hi = hi > nx ? nx : hi;
+        if (lo < hi) {
+            const int64_t len = hi - lo, first = static_cast<int64_t>(c) * rows_per_chunk;
+            if (first < len) {
+                row_begin = lo + first;
+                row_end = (first + rows_per_chunk) < len ? (row_begin + rows_per_chunk) : hi;
+            }
+        }
+    }
+    if (row_end <= row_begin) {  // block-uniform
+        for (int r = threadIdx.x; r < k; r += kThreads) out[static_cast<int64_t>(r) * lists] = 0ull;
+        return;
+    }
+
+    char* const stage = lds + wave * on::kStageBytes;
+    Cand* const cand = reinterpret_cast<Cand*>(lds + L::kStage);
+    float* const qs = reinterpret_cast<float*>(lds + L::kStage + L::kCand);
+    uint32_t* const hist = reinterpret_cast<uint32_t*>(lds + L::kStage + L::kCand + L::kQuery) + wave * 256;
+    const int units = d / EPU;
+    const int64_t row_bytes = static_cast<int64_t>(units) * 16;
+    const int steps = (units + kStepUnits - 1) / kStepUnits;
+    const int tiles = static_cast<int>((row_end - row_begin + kTileRows - 1) / kTileRows);
+
+    for (int e = threadIdx.x; e < d; e += kThreads) qs[e] = to_f32(Q[static_cast<int64_t>(q) * d + e]);
+    if (threadIdx.x == 0) {
+        cnt = 0;
+        thr = -INFINITY;
+    }
+
+    // step (tile t, column step cs) of this wave: slot i of lane l is unit
+    // cs * 8 + (f & 7) of group row f >> 3, f = 64 i + l (the online scan's)
+    uint4 R[kStepUnits];
+    auto load_step = [&](int t, int cs) {
+        const int64_t g0 = row_begin + static_cast<int64_t>(t) * kTileRows + wave * 64;
+#pragma unroll
+        for (int i = 0; i < kStepUnits; ++i) {
+            const int f = i * 64 + lane;
+            const int u = cs * kStepUnits + (f & 7);
+            const int64_t row = g0 + (f >> 3);
+            R[i] = make_uint4(0u, 0u, 0u, 0u);
+            if (t < tiles && u < units && row < row_end)
+                R[i] = *reinterpret_cast<const uint4*>(X + row * row_bytes + static_cast<int64_t>(u) * 16);
+        }
+    };
+    load_step(0, 0);
+    __syncthreads();
+
+    int over = 0;  // decided through the barrier that ends a tile: block-uniform
+    for (int t = 0; t < tiles; ++t) {
+        if (over) {
+            if (wave == 0) {
+                int n = cnt;
+                float th = thr;
+                compact_keep_ties(cand, n, k, kRoom, hist, th);
+                if (lane == 0) {
+                    cnt = n;
+                    thr = th;
+                }
+            }
+            __syncthreads();
+        }
+        const float th = thr;
+        const int64_t row = row_begin + static_cast<int64_t>(t) * kTileRows + wave * 64 + lane;
+        // original position of this lane's row: in flight under the scores
+        const int32_t pos = row < row_end ? row_pos[row] : -1;
+
+        float acc = 0.f;
+        for (int cs = 0; cs < steps; ++cs) {
+#pragma unroll
+            for (int i = 0; i < kStepUnits; ++i) {
+                const int f = i * 64 + lane;
+                *reinterpret_cast<uint4*>(stage + (f >> 3) * kRowStride + (f & 7) * 16) = R[i];
+            }
+            if (cs + 1 < steps) load_step(t, cs + 1);
+            else load_step(t + 1, 0);
+            wave_lds_sync();
+            const int nu = (units - cs * kStepUnits) < kStepUnits ? (units - cs * kStepUnits) : kStepUnits;
+#pragma unroll
+            for (int u = 0; u < kStepUnits; ++u) {
+                if (u >= nu) break;  // wave-uniform
+                const uint4 xv = *reinterpret_cast<const uint4*>(stage + lane * kRowStride + u * 16);
+                float x[EPU];
+                on::widen(xv, x, T());
+                const int j0 = (cs * kStepUnits + u) * EPU;
+#pragma unroll
+                for (int h = 0; h < EPU / 4; ++h) {
+                    const float4 qv = *reinterpret_cast<const float4*>(qs + j0 + 4 * h);
+                    acc = __builtin_fmaf(qv.x, x[4 * h], acc);
+                    acc = __builtin_fmaf(qv.y, x[4 * h + 1], acc);
+                    acc = __builtin_fmaf(qv.z, x[4 * h + 2], acc);
+                    acc = __builtin_fmaf(qv.w, x[4 * h + 3], acc);
+                }
+            }
+            wave_lds_sync();  // the stage is rewritten by the next step
+        }
+
+        // ---- selection: at most one append per row ----
+        // a position outside [0, nx) (a corrupt row_pos) is dropped: it has no bit in
+        // the bitmap and no row in the caller's corpus
+        bool pass = pos >= 0 && static_cast<int64_t>(pos) < nx && acc >= th;
+        if (excl && pass)
+            pass = ((excl[static_cast<int64_t>(q) * excl_words + (pos >> 5)] >> (pos & 31)) & 1u) == 0u;
+        int mine_over = 0;
+        const uint64_t bm = __ballot(pass);
+        if (bm) {
+            int base = 0;
+            if (lane == 0) base = atomicAdd(&cnt, __popcll(bm));
+            base = __shfl(base, 0, 64);
+            mine_over = (base + __popcll(bm)) > kRoom ? 1 : 0;
+            const int at = base + static_cast<int>(__builtin_amdgcn_mbcnt_hi(
+                                      static_cast<uint32_t>(bm >> 32),
+                                      __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(bm), 0u)));
+            // at < kCap by the append budget; the test only guards a row_pos that
+            // repeats positions (equal keys, which no compaction can tell apart)
+            if (pass && at < on::kCap) cand[at] = Cand{acc, static_cast<uint32_t>(pos)};
+        }
+        over = __syncthreads_or(mine_over);
+    }
+
+    // ---- the block's list: the k best, sorted, as composite keys ----
+    if (wave != 0) return;
+    int n = cnt;
+    if (n > v4::kFinishCap) {
+        float th = 0.f;
+        v4::compact_stream(cand, n, k, v4::kFinishCap, hist, th);
+    }
+    wave_lds_sync();
+    float s[2];
+    uint32_t id[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int r = lane * 2 + j;
+        const Cand cd = r < n ? cand[r] : Cand{-INFINITY, kEmptyId};
+        s[j] = cd.s;
+        id[j] = cd.i;
+    }
+    wave_sort_regs2(s, id);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int r = lane * 2 + j;
+        if (r < k) out[static_cast<int64_t>(r) * lists] = id[j] != kEmptyId ? v4::ckey(Cand{s[j], id[j]}) : 0ull;
+    }
+}
+
+// ---- rt_segment_mean_f32 ----
+// One block per segment. Thread (g, u) sums 16-byte unit u of the rows g, g + G,
+// g + 2G, ... of the segment in fp64 (G = 256 / units row groups: consecutive
+// threads read consecutive 16 bytes), then element e is the sum of its G
+// partials in ascending g: the order depends on the segment's length and d
+// only. No atomics.
+constexpr int kMeanThreads = 256;
+
+template <typename T>
+__global__ __launch_bounds__(kMeanThreads) void segment_mean(const char* __restrict__ X, int64_t n, int d,
+                                                             const int64_t* __restrict__ offsets,
+                                                             const float* __restrict__ prev, int normalize,
+                                                             float* __restrict__ out) {
+    constexpr int EPU = 16 / static_cast<int>(sizeof(T));
+    __shared__ double part[kMeanThreads * EPU];  // [g][u][e]
+    __shared__ double mean[256];
+    const int64_t s = blockIdx.x;
+    int64_t lo = offsets[s], hi = offsets[s + 1];
+    lo = lo < 0 ? 0 : lo;
+    hi = hi > n ? n : hi;
+    float* const o = out + s * d;
+    if (hi <= lo) {  // block-uniform
+        for (int e = threadIdx.x; e < d; e += kMeanThreads) o[e] = prev[s * d + e];
+        return;
+    }
+    const int units = d / EPU;            // <= 64
+    const int G = kMeanThreads / units;   // >= 4
+    const int g = threadIdx.x / units, u = threadIdx.x - g * units;
+    double acc[EPU];
+#pragma unroll
+    for (int e = 0; e < EPU; ++e) acc[e] = 0.0;
+    if (g < G) {
+        for (int64_t r = lo + g; r < hi; r += G) {
+            const uint4 v = *reinterpret_cast<const uint4*>(X + (r * units + u) * 16);
+            float x[EPU];
+            on::widen(v, x, T());
+#pragma unroll
+            for (int e = 0; e < EPU; ++e) acc[e] += static_cast<double>(x[e]);
+        }
+#pragma unroll
+        for (int e = 0; e < EPU; ++e) part[(g * units + u) * EPU + e] = acc[e];
+    }
+    __syncthreads();
+    const double inv = 1.0 / static_cast<double>(hi - lo);
+    for (int e = threadIdx.x; e < d; e += kMeanThreads) {
+        double t = 0.0;
+        for (int gg = 0; gg < G; ++gg) t += part[gg * d + e];  // (gg * units + e / EPU) * EPU + e % EPU
+        mean[e] = t * inv;
+    }
+    __syncthreads();
+    double scale = 1.0;
+    if (normalize) {
+        double ss = 0.0;
+        for (int e = 0; e < d; ++e) ss += mean[e] * mean[e];  // LDS broadcast reads, the same order in every thread
+        if (ss > 0.0) scale = 1.0 / sqrt(ss);
+    }
+    for (int e = threadIdx.x; e < d; e += kMeanThreads) o[e] = static_cast<float>(mean[e] * scale);
+}
+
+}  // namespace ivf
+}  // namespace topk
+}  // namespace rt
+
+using namespace rt;
+namespace iv = rt::topk::ivf;
+namespace ivon = rt::topk::online;
+
+static_assert(RT_IVF_MAX_NPROBE == iv::kMaxProbe && RT_IVF_MAX_K == ivon::kMaxK, "rtrec_hip.h restates the kernel's limits");
+
+static int g_ivf_min_tiles = 1;
+
+static bool ivf_shape_ok(int d, int dtype) {
+    return dtype == RT_F32 ? (d % 4 == 0 && d <= 256) : (d % 8 == 0 && d <= 256);
+}
+
+extern "C" int rt_ivf_topk_tuning(int min_chunk_tiles) {
+    if (min_chunk_tiles < 0 || min_chunk_tiles > 4096) return RT_ERR_INVALID;
+    g_ivf_min_tiles = min_chunk_tiles ? min_chunk_tiles : 1;
+    return RT_OK;
+}
+
+extern "C" int rt_ivf_topk_plan(int64_t nq, int nprobe, int64_t max_list_rows, int64_t* out) {
+    if (nq <= 0 || nprobe <= 0 || max_list_rows < 0 || !out) return RT_ERR_INVALID;
+    if (nprobe > iv::kMaxProbe || nq > iv::kMaxNq || max_list_rows >= 0xFFFFFFFFll) return RT_ERR_UNSUPPORTED;
+    const iv::Plan p = iv::make_plan(nprobe, max_list_rows, g_ivf_min_tiles);
+    out[0] = p.chunks;
+    out[1] = p.rows_per_chunk;
+    out[2] = nq * nprobe * p.chunks;
+    return RT_OK;
+}
+
+extern "C" size_t rt_ivf_topk_workspace_bytes(int64_t nq, int nprobe, int64_t max_list_rows, int k) {
+    int64_t plan[3];
+    if (k <= 0 || k > ivon::kMaxK || rt_ivf_topk_plan(nq, nprobe, max_list_rows, plan) != RT_OK) return 256;
+    const size_t need = static_cast<size_t>(plan[2]) * k * sizeof(uint64_t);
+    return need < 256 ? 256 : need;
+}
+
+extern "C" int rt_ivf_topk(const void* queries, int64_t nq, const void* rows, int64_t nx, int d, int dtype,
+                           const int64_t* list_offsets, int64_t nlist, const int32_t* row_pos,
+                           const int64_t* probes, int nprobe, int64_t max_list_rows, int k,
+                           const uint32_t* exclude_bits, int64_t exclude_words, float* out_scores,
+                           int64_t* out_ids, void* workspace, size_t workspace_bytes, void* stream) {
+    if (nq < 0 || nx < 0 || d <= 0 || k <= 0 || nlist <= 0 || nprobe <= 0 || max_list_rows < 0) return RT_ERR_INVALID;
+    if (nq == 0) return RT_OK;
+    if (!queries || !out_scores || !out_ids || !list_offsets || !probes || (nx > 0 && (!rows || !row_pos)))
+        return RT_ERR_INVALID;
+    if (k > ivon::kMaxK || nprobe > iv::kMaxProbe || nq > iv::kMaxNq) return RT_ERR_UNSUPPORTED;
+    if (dtype != RT_F32 && dtype != RT_F16 && dtype != RT_BF16) return RT_ERR_INVALID;
+    if (!ivf_shape_ok(d, dtype)) return RT_ERR_UNSUPPORTED;
+    if (nx >= 0x7FFFFFFFll || max_list_rows >= 0xFFFFFFFFll) return RT_ERR_UNSUPPORTED;  // positions are int32
+    if ((reinterpret_cast<uintptr_t>(queries) | reinterpret_cast<uintptr_t>(rows)) & 15) return RT_ERR_INVALID;
+    if (exclude_bits && exclude_words < (nx + 31) / 32) return RT_ERR_INVALID;
+    if (!workspace || workspace_bytes < rt_ivf_topk_workspace_bytes(nq, nprobe, max_list_rows, k))
+        return RT_ERR_WORKSPACE;
+    if (reinterpret_cast<uintptr_t>(workspace) & 7) return RT_ERR_INVALID;
+    hipStream_t st = as_stream(stream);
+    const iv::Plan p = iv::make_plan(nprobe, max_list_rows, g_ivf_min_tiles);
+    const int lists = nprobe * p.chunks;
+    uint64_t* partials = static_cast<uint64_t*>(workspace);
+    const dim3 grid(static_cast<unsigned>(lists), static_cast<unsigned>(nq)), block(ivon::kThreads);
+    const char* x = static_cast<const char*>(rows);
+#define RT_IVF_LAUNCH(T)                                                                                      \
+    hipLaunchKernelGGL((iv::ivf_scan<T>), grid, block, 0, st, static_cast<const T*>(queries), x, nx, d, k,    \
+                       list_offsets, nlist, row_pos, probes, nprobe, p.chunks, p.rows_per_chunk, exclude_bits, \
+                       exclude_words, partials)
+    switch (dtype) {
+        case RT_F32: RT_IVF_LAUNCH(float); break;
+        case RT_F16: RT_IVF_LAUNCH(__half); break;
+        default: RT_IVF_LAUNCH(__hip_bfloat16); break;
+    }
+#undef RT_IVF_LAUNCH
+    int rc = check_launch("ivf_scan");
+    if (rc) return rc;
+    hipLaunchKernelGGL(ivon::flatip_online_finish, dim3(static_cast<unsigned>(nq)), dim3(ivon::kMaxBlocks), 0, st,
+                       partials, lists, k, out_scores, out_ids, static_cast<int64_t>(0));
+    return check_launch("flatip_online_finish");
+}
+
+extern "C" int rt_segment_mean_f32(const void* rows, int64_t n, int d, int dtype, const int64_t* offsets,
+                                   int64_t n_seg, const float* prev, int normalize, float* out, void* stream) {
+    if (n < 0 || d <= 0 || n_seg < 0) return RT_ERR_INVALID;
+    if (n_seg == 0) return RT_OK;
+    if (!offsets || !prev || !out || (n > 0 && !rows)) return RT_ERR_INVALID;
+    if (dtype != RT_F32 && dtype != RT_F16 && dtype != RT_BF16) return RT_ERR_INVALID;
+    if (!ivf_shape_ok(d, dtype) || n_seg > 0x7FFFFFFFll) return RT_ERR_UNSUPPORTED;
+    if (reinterpret_cast<uintptr_t>(rows) & 15) return RT_ERR_INVALID;
+    hipStream_t st = as_stream(stream);
+    const dim3 grid(static_cast<unsigned>(n_seg)), block(iv::kMeanThreads);
+    const char* x = static_cast<const char*>(rows);
+    switch (dtype) {
+        case RT_F32:
+            hipLaunchKernelGGL((iv::segment_mean<float>), grid, block, 0, st, x, n, d, offsets, prev, normalize, out);
+            break;
+        case RT_F16:
+            hipLaunchKernelGGL((iv::segment_mean<__half>), grid, block, 0, st, x, n, d, offsets, prev, normalize, out);
+            break;
+        default:
+            hipLaunchKernelGGL((iv::segment_mean<__hip_bfloat16>), grid, block, 0, st, x, n, d, offsets, prev,
+                               normalize, out);
+            break;
+    }
+    return check_launch("segment_mean");
+}

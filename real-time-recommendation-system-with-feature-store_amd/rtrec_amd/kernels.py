@@ -525,6 +525,110 @@ def topk_merge(scores: torch.Tensor, ids: torch.Tensor, k_out: int
     return os_, oi
 
 
+# ---------------------------------------------------------------------------
+# IVF-Flat (faiss "IVF<nlist>,Flat" + nprobe, src/serving/retrieval.py:60-62,101-133)
+# ---------------------------------------------------------------------------
+
+IVF_MAX_K = 128        # RT_IVF_MAX_K
+IVF_MAX_NPROBE = 128   # RT_IVF_MAX_NPROBE
+IVF_QUERY_CHUNK = 32768  # queries per rt_ivf_topk call (the kernel's grid takes 65,535)
+
+
+def ivf_topk_plan(nq: int, nprobe: int, max_list_rows: int) -> Tuple[int, int, int]:
+    """Host-only plan of the probed-list scan (rt_ivf_topk_plan): ``(chunks per
+    list, rows per chunk, scan blocks)``. No device work."""
+    out = (ctypes.c_int64 * 3)()
+    call("rt_ivf_topk_plan", int(nq), int(nprobe), int(max_list_rows), ctypes.cast(out, ctypes.c_void_p))
+    return int(out[0]), int(out[1]), int(out[2])
+
+
+def ivf_topk_tuning(min_chunk_tiles: int = 0) -> None:
+    """Floor of the scan's chunk in 256-row tiles (0 = default); for measurements."""
+    call("rt_ivf_topk_tuning", int(min_chunk_tiles))
+
+
+def ivf_topk(queries: torch.Tensor, rows: torch.Tensor, list_offsets: torch.Tensor, row_pos: torch.Tensor,
+             probes: torch.Tensor, max_list_rows: int, k: int, exclude_bits: Optional[torch.Tensor] = None,
+             out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+             workspace_buf: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Top-k over the union of the probed lists (rt_ivf_topk): (scores [nq, k] f32,
+    original positions [nq, k] int64) in (score desc, position asc) order,
+    (-FLT_MAX, -1) pads. ``rows`` [nx, d] are stored list-contiguous, list l =
+    stored rows ``[list_offsets[l], list_offsets[l + 1])``; ``row_pos`` int32 [nx]
+    = original position of each stored row; ``probes`` int64 [nq, nprobe] list
+    ids (-1: skipped); ``exclude_bits`` is indexed by original position.
+    Batches above 32,768 queries run in chunks."""
+    native.require_device(queries, rows, list_offsets, row_pos, probes, exclude_bits, what="ivf_topk")
+    if queries.dim() != 2 or rows.dim() != 2 or queries.shape[1] != rows.shape[1]:
+        raise ValueError(f"shape mismatch: queries {tuple(queries.shape)} rows {tuple(rows.shape)}")
+    if queries.dtype != rows.dtype:
+        raise TypeError("queries and rows must share a dtype")
+    if not 1 <= k <= IVF_MAX_K:
+        raise ValueError(f"k={k}: ivf_topk returns 1..{IVF_MAX_K} results per query")
+    if not (queries.is_contiguous() and rows.is_contiguous() and probes.is_contiguous()
+            and list_offsets.is_contiguous() and row_pos.is_contiguous()):
+        raise ValueError("ivf_topk expects contiguous operands")
+    nq, d = queries.shape
+    nx = rows.shape[0]
+    if list_offsets.dtype != torch.int64 or list_offsets.dim() != 1 or list_offsets.numel() < 2:
+        raise ValueError("list_offsets must be int64 [nlist + 1]")
+    if row_pos.dtype != torch.int32 or row_pos.numel() != nx:
+        raise ValueError("row_pos must be int32 [nx]")
+    if probes.dtype != torch.int64 or probes.dim() != 2 or probes.shape[0] != nq:
+        raise ValueError("probes must be int64 [nq, nprobe]")
+    nprobe = probes.shape[1]
+    if not 1 <= nprobe <= IVF_MAX_NPROBE:
+        raise ValueError(f"nprobe={nprobe}: 1..{IVF_MAX_NPROBE}")
+    nlist = list_offsets.numel() - 1
+    dt = native.dtype_code(queries.dtype)
+    if out is None:
+        scores = torch.empty((nq, k), dtype=torch.float32, device=queries.device)
+        ids = torch.empty((nq, k), dtype=torch.int64, device=queries.device)
+    else:
+        scores, ids = out
+    words = 0
+    if exclude_bits is not None:
+        if exclude_bits.dtype not in (torch.int32, torch.uint32) or exclude_bits.shape[0] != nq \
+                or not exclude_bits.is_contiguous():
+            raise ValueError("exclude_bits must be contiguous int32/uint32 [nq, words]")
+        words = exclude_bits.shape[1]
+    for a in range(0, nq, IVF_QUERY_CHUNK):
+        b = min(nq, a + IVF_QUERY_CHUNK)
+        ws = workspace_buf
+        if ws is None:
+            ws = workspace(queries.device,
+                           native.lib().rt_ivf_topk_workspace_bytes(b - a, nprobe, int(max_list_rows), k), "ivf_topk")
+        call("rt_ivf_topk", ptr(queries[a:b]), b - a, ptr(rows) if nx else None, nx, d, dt, ptr(list_offsets), nlist,
+             ptr(row_pos) if nx else None, ptr(probes[a:b]), nprobe, int(max_list_rows), k,
+             ptr(exclude_bits[a:b]) if exclude_bits is not None else None, words, ptr(scores[a:b]), ptr(ids[a:b]),
+             ptr(ws), ws.numel(), stream_of(queries))
+    return scores, ids
+
+
+def segment_mean(rows: torch.Tensor, offsets: torch.Tensor, prev: torch.Tensor, normalize: bool = False,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp32 [n_seg, d] means of the row segments ``[offsets[s], offsets[s + 1])`` of
+    ``rows`` [n, d] (rt_segment_mean_f32: fp64 accumulation in a fixed order, no
+    atomics); an empty segment copies ``prev[s]``; ``normalize`` rescales the
+    non-empty results to unit L2 norm."""
+    native.require_device(rows, offsets, prev, out, what="segment_mean")
+    if rows.dim() != 2 or not rows.is_contiguous():
+        raise ValueError("segment_mean expects contiguous [n, d] rows")
+    n, d = rows.shape
+    if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.numel() < 1 or not offsets.is_contiguous():
+        raise ValueError("offsets must be contiguous int64 [n_seg + 1]")
+    n_seg = offsets.numel() - 1
+    if prev.dtype != torch.float32 or tuple(prev.shape) != (n_seg, d) or not prev.is_contiguous():
+        raise ValueError(f"prev must be contiguous fp32 [{n_seg}, {d}]")
+    if out is None:
+        out = torch.empty((n_seg, d), dtype=torch.float32, device=rows.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (n_seg, d) or not out.is_contiguous():
+        raise ValueError(f"out must be contiguous fp32 [{n_seg}, {d}]")
+    call("rt_segment_mean_f32", ptr(rows) if n else None, n, d, native.dtype_code(rows.dtype), ptr(offsets), n_seg,
+         ptr(prev), 1 if normalize else 0, ptr(out), stream_of(rows))
+    return out
+
+
 def exclusion_bitmap(n_queries: int, n_items: int, excluded, device) -> torch.Tensor:
     """int32 bitmap [nq, ceil(n_items/32)] (bit j of row q set ⇒ item j skipped for
     query q) from per-query excluded item lists — the train-item mask of

@@ -126,6 +126,12 @@ SIGNATURES = {
                                       c_size, vp]),
     "rt_flatip_topk_online_lists": (c_int, [vp, c_i64, vp, c_i64, c_int, c_int, c_int,
                                             ctypes.POINTER(ExclusionLists), c_int, c_i64, vp, vp, vp, c_size, vp]),
+    "rt_ivf_topk_tuning": (c_int, [c_int]),
+    "rt_ivf_topk_plan": (c_int, [c_i64, c_int, c_i64, vp]),
+    "rt_ivf_topk_workspace_bytes": (c_size, [c_i64, c_int, c_i64, c_int]),
+    "rt_ivf_topk": (c_int, [vp, c_i64, vp, c_i64, c_int, c_int, vp, c_i64, vp, vp, c_int, c_i64, c_int, vp, c_i64,
+                            vp, vp, vp, c_size, vp]),
+    "rt_segment_mean_f32": (c_int, [vp, c_i64, c_int, c_int, vp, c_i64, vp, c_int, vp, vp]),
     "rt_topk_merge": (c_int, [vp, vp, c_i64, c_int, c_int, c_int, vp, vp, vp]),
     "rt_flatip_topk_tuning": (c_int, [c_int, c_int, c_int]),
     "rt_flatip_topk_shard_workspace_bytes": (c_size, [c_i64, c_i64, c_int, c_int, c_int]),

@@ -616,6 +616,10 @@ class OnlineSearcher:
         self._device_chain(nq, k, [self._list_source()] if lists else None)
         self._download(nq, k)
 
+    def _graph_key(self, nq: int, k: int, lists: bool) -> tuple:
+        """What one captured graph serves."""
+        return (nq, k, True) if lists else (nq, k)
+
     def _revalidate(self) -> bool:
         """Under ``lock``: pick up the index's rows again when ``build`` / ``add`` /
         ``load`` moved or grew them (the graphs hold stale pointers: dropped).
@@ -671,7 +675,7 @@ class OnlineSearcher:
                 s, p = idx.search_tensors(t, k, exclude_bits=bits)
                 return s.cpu().numpy(), p.cpu().numpy()
             self._h_q[:nq].copy_(t)
-            key = (nq, k, True) if lists else (nq, k)
+            key = self._graph_key(nq, k, lists)
             stream = torch.cuda.current_stream(self._d_s.device)
             if os.environ.get("RTREC_ONLINE_GRAPH", "1") == "0":
                 self._sequence(nq, k, lists)
@@ -1104,11 +1108,434 @@ def _lists_from_positions(scores: np.ndarray, pos: np.ndarray, id_map: Dict[int,
     return batch_ids, batch_scores
 
 
+_IVF_FACTORY = "IVF1024,Flat"   # the reference's default (retrieval.py:60)
+IVF_MIN_ITEMS = 1024            # below it the reference builds Flat (retrieval.py:90-93)
+_ASSIGN_CHUNK = 1 << 20         # rows per nearest-centroid call
+
+
+def _parse_ivf_factory(factory: str) -> int:
+    """``"IVF<nlist>,Flat"`` -> nlist; anything else raises."""
+    s = str(factory)
+    head, _, tail = s.partition(",")
+    if not head.startswith("IVF") or tail != "Flat" or not head[3:].isdigit() or int(head[3:]) < 1:
+        raise ValueError(f"index_factory {factory!r}: HipIVFFlatIndex serves 'IVF<nlist>,Flat' "
+                         "(every other factory: HipFlatIPIndex, exact)")
+    return int(head[3:])
+
+
+class HipIVFFlatIndex(IndexBase):
+    """IVF-Flat index resident in HBM: the reference's DEFAULT configuration,
+    ``faiss.index_factory(d, "IVF1024,Flat")`` searched with ``nprobe = 20``
+    (retrieval.py:60-62, 101-133). k-means lists over the corpus, a coarse
+    search over the centroids, then an exact scan of the probed lists only
+    (``rt_ivf_topk``): a search reads about nprobe / nlist of the rows.
+
+    Scores are the Flat index's, bit for bit (the same sequential fmaf chain),
+    and results keep its order — (score desc, original position asc), -1 pads —
+    so a search with ``nprobe == nlist`` IS the Flat search, and one with fewer
+    probes is the Flat search restricted to the probed lists. Faiss's own
+    k-means cannot be reproduced bit for bit (random subsampling and
+    initialisation); this one is deterministic: the same data and ``seed`` give
+    the same index, bit for bit.
+
+    Config keys: ``dimension``; ``metric`` ("cosine" or "inner_product"; the L2
+    metric raises — use :class:`HipFlatIPIndex`); ``index_factory``
+    (``"IVF<nlist>,Flat"``, default ``"IVF1024,Flat"``; anything else raises);
+    ``nprobe`` (default 20, clamped to nlist at search; a plain attribute that
+    may be changed between searches, as with Faiss; at most 128 lists are
+    probed per search); ``storage_dtype``, ``device``; ``train_iters`` (10);
+    ``max_points_per_centroid`` (256: training subsamples to that many rows per
+    list); ``seed`` (1234); ``online_max_batch`` (as :class:`HipFlatIPIndex`:
+    small calls go through the resident :class:`OnlineIVFSearcher`).
+    ``mutable: True`` raises; ``update`` and ``remove`` only warn, as the
+    reference's do. k <= 128 per search (2k <= 128 with ``filter_ids``).
+
+    Below 1,024 items, or below nlist, ``build`` logs the reference's message
+    and everything is delegated to an inner :class:`HipFlatIPIndex`.
+
+    Measured ("IVF-Flat"; 1M x 128, k = 100, nlist = 1024,
+    resident searchers alternating call by call): at nprobe = 20 the call is
+    1.31x the exact online search's for one float16 query (slower: four chained
+    launches against two, both latency-bound), 0.87x for 8 float16 queries,
+    0.89x / 0.81x for 1 / 8 float32 queries; recall@100 0.998. Recommended from
+    about 1M rows for float32 storage or 8-query calls and, extrapolated, from
+    1.5-2M rows for single float16 queries; below that ``HipFlatIPIndex`` with
+    ``online_max_batch`` is as fast and exact.
+    """
+
+    def __init__(self, config: Optional[Dict[str, Any]] = None):
+        self.config = dict(config or {})
+        self.dimension = self.config.get("dimension", 128)
+        self.metric = self.config.get("metric", "cosine")
+        if self.metric not in ("cosine", "inner_product"):
+            raise ValueError(f"metric {self.metric!r}: HipIVFFlatIndex serves 'cosine' and 'inner_product'; "
+                             "the L2 metric (IndexFlatL2) is HipFlatIPIndex")
+        if self.config.get("mutable", False):
+            raise ValueError("HipIVFFlatIndex is not mutable: in-place list mutation is not built "
+                             "(HipFlatIPIndex takes mutable=True)")
+        self.index_factory = self.config.get("index_factory", _IVF_FACTORY)
+        self.nlist = _parse_ivf_factory(self.index_factory)
+        self.nprobe = int(self.config.get("nprobe", 20))
+        self.storage_dtype = _STORAGE[self.config.get("storage_dtype", "float32")]
+        step = 4 if self.storage_dtype == torch.float32 else 8
+        if not (0 < self.dimension <= MAX_DIM) or self.dimension % step:
+            raise ValueError(f"dimension {self.dimension} unsupported: the MI355X index serves d % {step} == 0, "
+                             f"d <= {MAX_DIM}")
+        self.train_iters = int(self.config.get("train_iters", 10))
+        self.max_points_per_centroid = int(self.config.get("max_points_per_centroid", 256))
+        self.seed = int(self.config.get("seed", 1234))
+        self.online_max_batch = int(self.config.get("online_max_batch", 0) or 0)
+        if not 0 <= self.online_max_batch <= OnlineSearcher.MAX_BATCH:
+            raise ValueError(f"online_max_batch={self.online_max_batch}: 0 (off) or 1..{OnlineSearcher.MAX_BATCH}")
+        dev = self.config.get("device")
+        self.device = torch.device(dev) if dev is not None else None
+        self._l2 = False
+        self.mutable = False
+        self._flat: Optional[HipFlatIPIndex] = None   # the Flat fallback of a small corpus
+        self.index: Optional[torch.Tensor] = None     # [n, d] storage dtype, list-contiguous
+        self.centroids: Optional[torch.Tensor] = None     # [nlist, d] fp32
+        self.list_offsets: Optional[torch.Tensor] = None  # [nlist + 1] int64
+        self.row_pos: Optional[torch.Tensor] = None       # [n] int32: original position of a stored row
+        self.assign: Optional[torch.Tensor] = None        # [n] int64: list of an original position
+        self.max_list_rows = 0
+        self.id_map: Dict[int, str] = {}
+        self.reverse_id_map: Dict[str, int] = {}
+        self._ids: List[str] = []
+        self.current_size = 0
+        self._generation = 0
+        self._online: Optional["OnlineSearcher"] = None
+
+    # -- helpers -----------------------------------------------------------
+    _dev = HipFlatIPIndex._dev
+    _prepare = HipFlatIPIndex._prepare
+
+    def _flat_config(self) -> Dict[str, Any]:
+        cfg = {k: v for k, v in self.config.items()
+               if k in ("dimension", "metric", "storage_dtype", "device", "online_max_batch")}
+        cfg["index_factory"] = "Flat"
+        return cfg
+
+    def _assign_rows(self, rows: torch.Tensor, centroids: torch.Tensor) -> torch.Tensor:
+        """Nearest centroid of every fp32 row by inner product, the lowest centroid
+        id winning ties (rt_flatip_topk, k = 1: rows as queries, centroids as items)."""
+        out = torch.empty(rows.shape[0], dtype=torch.int64, device=rows.device)
+        for a in range(0, rows.shape[0], _ASSIGN_CHUNK):
+            _, ids = kernels.flatip_topk(rows[a:a + _ASSIGN_CHUNK], centroids, 1)
+            out[a:a + _ASSIGN_CHUNK] = ids.view(-1)
+        return out
+
+    def _group(self, assign: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(order, offsets, counts): the stable sort of the assignments (original order
+        kept within a list) and the lists' CSR offsets."""
+        order = torch.sort(assign, stable=True).indices
+        counts = torch.bincount(assign, minlength=self.nlist)
+        offsets = torch.zeros(self.nlist + 1, dtype=torch.int64, device=assign.device)
+        offsets[1:] = torch.cumsum(counts, 0)
+        return order, offsets, counts
+
+    def _train(self, rows: torch.Tensor) -> torch.Tensor:
+        """``train_iters`` Lloyd steps over all rows, or over a seeded subsample of
+        ``max_points_per_centroid x nlist`` of them in ascending position order;
+        the initial centroids are the rows at the first nlist entries of the
+        same permutation. An empty list keeps its centroid."""
+        n = rows.shape[0]
+        perm = torch.randperm(n, generator=torch.Generator().manual_seed(self.seed))
+        centroids = rows[perm[: self.nlist].to(rows.device)].contiguous()
+        n_train = self.max_points_per_centroid * self.nlist
+        train = rows
+        if n > n_train:
+            sub = torch.sort(perm[:n_train]).values.to(rows.device)
+            train = kernels.gather_rows(rows, sub)
+        for _ in range(self.train_iters):
+            order, offsets, _ = self._group(self._assign_rows(train, centroids))
+            grouped = kernels.gather_rows(train, order)
+            centroids = kernels.segment_mean(grouped, offsets, centroids, normalize=self.metric == "cosine")
+        return centroids
+
+    def _regroup(self, src: torch.Tensor, src_index: Optional[torch.Tensor], assign: torch.Tensor):
+        """Store the rows list-contiguous: stored row i is ``src[src_index[order[i]]]``
+        (``src_index`` None: ``src`` is in original order) — one gather."""
+        order, offsets, counts = self._group(assign)
+        self.index = kernels.gather_rows(src, order if src_index is None else src_index[order])
+        self.row_pos = order.to(torch.int32)
+        self.list_offsets = offsets
+        self.assign = assign
+        self.max_list_rows = int(counts.max().item()) if assign.numel() else 0
+        self.current_size = int(assign.numel())
+
+    def _set_ids(self, ids: List[str], n: int):
+        self.id_map, self.reverse_id_map = {}, {}
+        for i, item_id in enumerate(ids):
+            self.id_map[i] = item_id
+            self.reverse_id_map[item_id] = i
+        self._ids = list(ids) + [None] * max(0, n - len(ids))
+
+    def _sync_flat(self):
+        """Mirror the inner Flat index's public state (the fallback of a small corpus)."""
+        f = self._flat
+        self.id_map, self.reverse_id_map, self._ids = f.id_map, f.reverse_id_map, f._ids
+        self.current_size = f.current_size
+        self.index = f.index
+        self._generation += 1
+
+    # -- IndexBase ---------------------------------------------------------
+    def build(self, embeddings: Array, ids: List[str]):
+        """retrieval.py:70-139: normalise (cosine), train the coarse quantiser
+        (``index.train``), add every row to its list (``index.add``)."""
+        start = time.time()
+        n = len(embeddings)
+        self._online = None
+        if n < IVF_MIN_ITEMS or n < self.nlist:
+            logger.info("Dataset too small (%d) for IVF, using Flat index", n)
+            self._flat = HipFlatIPIndex(self._flat_config())
+            self._flat.build(embeddings, ids)
+            self.centroids = self.list_offsets = self.row_pos = self.assign = None
+            self._sync_flat()
+            return
+        self._flat = None
+        rows = self._prepare(embeddings)
+        self.centroids = self._train(rows)
+        assign = self._assign_rows(rows, self.centroids)
+        self._regroup(rows.to(self.storage_dtype), None, assign)
+        self._set_ids(ids, n)
+        self._generation += 1
+        logger.info("Index built in %.2f seconds", time.time() - start)
+
+    def online_searcher(self, max_batch: int = 8, max_exclude: int = 8192) -> "OnlineSearcher":
+        """The resident searcher for calls of at most ``max_batch`` (1..8) queries and
+        k <= 128: an :class:`OnlineIVFSearcher` (the Flat fallback: an
+        :class:`OnlineSearcher` over the inner Flat index)."""
+        if self._flat is not None:
+            return self._flat.online_searcher(max_batch, max_exclude)
+        return OnlineIVFSearcher(self, max_batch)
+
+    def _n_probe(self, nprobe: Optional[int] = None) -> int:
+        np_ = min(int(self.nprobe if nprobe is None else nprobe), self.nlist)
+        if not 1 <= np_ <= kernels.IVF_MAX_NPROBE:
+            raise ValueError(f"nprobe={np_}: the MI355X IVF index probes 1..{kernels.IVF_MAX_NPROBE} lists per search")
+        return np_
+
+    def search_tensors(self, query_embeddings: Array, k: int, exclude_bits: Optional[torch.Tensor] = None,
+                       nprobe: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Device-level search: (scores [nq, k], original positions [nq, k]) with
+        (-FLT_MAX, -1) padding, like the Flat index. The coarse search runs on the
+        fp32 queries, before the storage cast."""
+        if self.index is None:
+            raise ValueError("Index not built yet")
+        if self._flat is not None:
+            return self._flat.search_tensors(query_embeddings, k, exclude_bits=exclude_bits)
+        if not 1 <= k <= kernels.IVF_MAX_K:
+            raise ValueError(f"k={k}: the MI355X IVF index returns 1..{kernels.IVF_MAX_K} results per query")
+        np_ = self._n_probe(nprobe)
+        q32 = self._prepare(query_embeddings)
+        if q32.shape[0] <= kernels.ONLINE_MAX_NQ:
+            _, probes = kernels.flatip_topk_online(q32, self.centroids, np_)
+        else:
+            _, probes = kernels.flatip_topk(q32, self.centroids, np_)
+        return kernels.ivf_topk(q32.to(self.storage_dtype), self.index, self.list_offsets, self.row_pos, probes,
+                                self.max_list_rows, k, exclude_bits=exclude_bits)
+
+    def search(self, query_embeddings: Array, k: int = 10, filter_ids: Optional[List[str]] = None,
+               exclude_ids=None) -> Tuple[List[List[str]], List[List[float]]]:
+        """retrieval.py:141-197, as :meth:`HipFlatIPIndex.search`: the 2k over-fetch
+        for ``filter_ids``, exact ``exclude_ids`` in the search (over the probed
+        lists). A call with ``exclude_ids`` takes the bitmap path."""
+        if self.index is None:
+            raise ValueError("Index not built yet")
+        if self._flat is not None:
+            return self._flat.search(query_embeddings, k, filter_ids, exclude_ids=exclude_ids)
+        k_search = min(k * 2, self.current_size) if filter_ids else k
+        nq = 1 if np.ndim(query_embeddings) == 1 else len(query_embeddings)
+        if k_search <= 0:
+            return [[] for _ in range(nq)], [[] for _ in range(nq)]
+        if exclude_ids is None and self.online_max_batch and k_search <= OnlineSearcher.MAX_K \
+                and 1 <= nq <= self.online_max_batch:
+            if self._online is None:
+                self._online = self.online_searcher(self.online_max_batch)
+            with self._online.lock:
+                scores, pos = self._online.search(query_embeddings, k_search)
+                return _lists_from_positions(scores, pos, self.id_map, k, filter_ids)
+        bits = None
+        if exclude_ids is not None:
+            excl = _exclude_positions(self.reverse_id_map, exclude_ids, nq)
+            bits = kernels.exclusion_bitmap(nq, self.current_size, excl, self._dev())
+        scores, pos = self.search_tensors(query_embeddings, k_search, exclude_bits=bits)
+        return _lists_from_positions(scores.cpu().numpy(), pos.cpu().numpy(), self.id_map, k, filter_ids)
+
+    def add(self, embeddings: Array, ids: List[str]):
+        """retrieval.py:199-226. The new rows are assigned to the existing centroids
+        (no retraining), then every list is regrouped by a stable sort of all
+        assignments and one gather: O(n) per call in the size of the index, not
+        in the size of the batch — batch the additions."""
+        if self.index is None:
+            raise ValueError("Index not built yet")
+        if self._flat is not None:
+            self._flat.add(embeddings, ids)
+            self._sync_flat()
+            return
+        rows = self._prepare(embeddings)
+        n_old, m = self.current_size, rows.shape[0]
+        dev = rows.device
+        inv = torch.empty(n_old, dtype=torch.int64, device=dev)
+        inv[self.row_pos.long()] = torch.arange(n_old, dtype=torch.int64, device=dev)
+        src_index = torch.cat([inv, torch.arange(n_old, n_old + m, dtype=torch.int64, device=dev)])
+        assign = torch.cat([self.assign, self._assign_rows(rows, self.centroids)])
+        src = torch.cat([self.index, rows.to(self.storage_dtype)])
+        with (self._online.lock if self._online is not None else contextlib.nullcontext()):
+            self._regroup(src, src_index, assign)
+            for i, item_id in enumerate(ids):
+                self.id_map[n_old + i] = item_id
+                self.reverse_id_map[item_id] = n_old + i
+            self._ids.extend(list(ids) + [None] * max(0, m - len(ids)))
+            self._generation += 1
+        logger.info("Added %d items to index. Total size: %d", m, self.current_size)
+
+    def update(self, embeddings: Array, ids: List[str]):
+        """retrieval.py:228-237: a no-op with a warning, like the reference."""
+        logger.warning("IVF index doesn't support direct updates. Consider periodic rebuilds.")
+
+    def remove(self, ids: List[str]):
+        """retrieval.py:239-246: a no-op with a warning, like the reference."""
+        logger.warning("IVF index doesn't support removal. Consider periodic rebuilds.")
+        return None
+
+    def vectors(self) -> np.ndarray:
+        """The stored rows in original order (fp32)."""
+        if self._flat is not None:
+            return self._flat.vectors()
+        if self.index is None:
+            return np.zeros((0, self.dimension), np.float32)
+        out = torch.empty_like(self.index)
+        out[self.row_pos.long()] = self.index
+        return out.float().cpu().numpy()
+
+    def save(self, path: str):
+        """``<path>.faiss`` (the rows in original order, IndexFlatIP layout) and
+        ``<path>.pkl`` (id maps) as the Flat index writes them, plus
+        ``<path>.ivf.npz``: centroids, assignments, config and seed."""
+        if self.index is None:
+            raise ValueError("No index to save")
+        path = Path(path)
+        if self._flat is not None:
+            self._flat.save(str(path))
+            ivf = path.with_suffix(".ivf.npz")
+            if ivf.exists():
+                ivf.unlink()   # a stale file of an earlier IVF save under this name
+            return
+        path.parent.mkdir(parents=True, exist_ok=True)
+        write_flat_index(path.with_suffix(".faiss"), self.vectors(), True)
+        with open(path.with_suffix(".pkl"), "wb") as f:
+            pickle.dump({"id_map": self.id_map, "reverse_id_map": self.reverse_id_map,
+                         "current_size": self.current_size, "config": self.config}, f)
+        cfg = {k: v for k, v in self.config.items() if isinstance(v, (str, int, float, bool, type(None)))}
+        np.savez(path.with_suffix(".ivf.npz"), centroids=self.centroids.cpu().numpy(),
+                 assign=self.assign.cpu().numpy(), config=np.array(json.dumps(cfg)), seed=np.int64(self.seed),
+                 nlist=np.int64(self.nlist))
+        logger.info("Saved index to %s", path)
+
+    def load(self, path: str):
+        """retrieval.py:275-299. A loaded index answers bit-identically: the rows are
+        regrouped by the saved assignments, nothing is trained again."""
+        path = Path(path)
+        self._online = None
+        ivf = path.with_suffix(".ivf.npz")
+        if not ivf.exists():   # saved by the Flat fallback (or by HipFlatIPIndex)
+            self._flat = HipFlatIPIndex(self._flat_config())
+            self._flat.load(str(path))
+            self.dimension, self.metric = self._flat.dimension, self._flat.metric
+            self.centroids = self.list_offsets = self.row_pos = self.assign = None
+            self._sync_flat()
+            return
+        vecs, _ip = read_flat_index(path.with_suffix(".faiss"))
+        with open(path.with_suffix(".pkl"), "rb") as f:
+            data = pickle.load(f)  # files this index wrote
+        with np.load(ivf) as z:
+            centroids, assign = z["centroids"], z["assign"]
+            self.seed, self.nlist = int(z["seed"]), int(z["nlist"])
+        self._flat = None
+        self.id_map, self.reverse_id_map = data["id_map"], data["reverse_id_map"]
+        self.config = dict(data.get("config", self.config))
+        self.metric = self.config.get("metric", self.metric)
+        self.dimension = vecs.shape[1]
+        self.index_factory = f"IVF{self.nlist},Flat"
+        dev = self._dev()
+        self.centroids = torch.from_numpy(centroids).to(dev)
+        self._regroup(torch.from_numpy(vecs).to(dev).to(self.storage_dtype), None, torch.from_numpy(assign).to(dev))
+        self._ids = [self.id_map.get(i) for i in range(self.current_size)]
+        self._generation += 1
+        logger.info("Loaded index from %s with %d items", path, self.current_size)
+
+
+class OnlineIVFSearcher(OnlineSearcher):
+    """:class:`OnlineSearcher` over one :class:`HipIVFFlatIndex`
+    (``index.online_searcher(max_batch)``): the same pinned buffers, one graph
+    replay and one synchronise per call; the captured chain is ``l2_renorm``
+    (cosine) -> coarse ``rt_flatip_topk_online`` over the fp32 centroids with
+    k = nprobe -> storage-dtype cast -> ``rt_ivf_topk`` — the arithmetic of
+    ``HipIVFFlatIndex.search_tensors`` in the same order. One graph per
+    (nq, k, nprobe): ``index.nprobe`` is read at every call. Generation
+    invalidation as the base class (``build`` / ``add`` / ``load``).
+
+    Exclusion lists are not read by the probed-list scan yet: a call with
+    ``exclude`` takes the bitmap path through ``search_tensors`` and returns
+    fresh arrays, as the base class's oversize-list fallback does."""
+
+    def __init__(self, index: "HipIVFFlatIndex", max_batch: int = 8):
+        if not isinstance(index, HipIVFFlatIndex) or index._flat is not None or index.index is None:
+            raise ValueError("OnlineIVFSearcher serves a built HipIVFFlatIndex that holds lists "
+                             "(a small corpus falls back to Flat: index.online_searcher() returns its searcher)")
+        super().__init__(index, max_batch, 0)
+        dev, mb = index._dev(), self.max_batch
+        # workspace sizing: both searches write [mb][<= 128][<= 512 lists] 8-byte keys at most —
+        # the base class's bound; the coarse search gets a workspace of its own
+        self._ws_coarse = torch.empty(mb * self.MAX_K * 512 * 8, dtype=torch.uint8, device=dev)
+        self._d_cs = torch.empty(mb * kernels.IVF_MAX_NPROBE, dtype=torch.float32, device=dev)
+        self._d_probes = torch.empty(mb * kernels.IVF_MAX_NPROBE, dtype=torch.int64, device=dev)
+        self._nprobe = 0
+        self._lists = None
+
+    def _stage_lists(self, nq: int, exclude) -> bool:
+        return False   # every call with lists: the bitmap path
+
+    def _graph_key(self, nq: int, k: int, lists: bool) -> tuple:
+        return (nq, k, self._nprobe)
+
+    def _revalidate(self) -> bool:
+        idx = self.index
+        self._nprobe = idx._n_probe() if idx._flat is None else 0   # read at every call
+        if self._generation == idx._generation:
+            return False
+        self._graphs.clear()
+        if idx._flat is not None or idx.dimension != self._h_q.shape[1] or idx.storage_dtype != self._d_q.dtype:
+            raise ValueError("the index changed its dimension, storage dtype or fell back to Flat since this "
+                             "searcher was made: obtain a new one (index.online_searcher)")
+        self._rows = idx.index
+        self._lists = (idx.list_offsets, idx.row_pos, idx.centroids, idx.max_list_rows)
+        self._generation = idx._generation
+        return True
+
+    def _device_chain(self, nq: int, k: int, sources=None):
+        n, np_ = nq * k, self._nprobe
+        offsets, row_pos, centroids, max_list_rows = self._lists
+        q32 = self._d_q32[:nq]
+        if self.index.metric == "cosine":
+            kernels.l2_renorm_(q32)
+        probes = self._d_probes[:nq * np_].view(nq, np_)
+        kernels.flatip_topk_online(q32, centroids, np_, out=(self._d_cs[:nq * np_].view(nq, np_), probes),
+                                   workspace_buf=self._ws_coarse)
+        q = self._d_q[:nq]
+        if q.data_ptr() != q32.data_ptr():
+            q.copy_(q32)
+        kernels.ivf_topk(q, self._rows, offsets, row_pos, probes, max_list_rows, k,
+                         out=(self._d_s[:n].view(nq, k), self._d_p[:n].view(nq, k)), workspace_buf=self._ws)
+
+
 # Backwards-compatible name: configs with index_type "faiss" get the exact
 # HBM-resident index (Faiss-CPU is not part of the MI355X build).
 FaissIndex = HipFlatIPIndex
 
-_INDEX_TYPES = {"hip_flat": HipFlatIPIndex, "faiss": HipFlatIPIndex, "hip_flat_sharded": HipShardedFlatIPIndex}
+_INDEX_TYPES = {"hip_flat": HipFlatIPIndex, "faiss": HipFlatIPIndex, "hip_flat_sharded": HipShardedFlatIPIndex,
+                "hip_ivf": HipIVFFlatIndex}
 
 
 def register_index(name: str, cls):

@@ -1,0 +1,177 @@
+#!/usr/bin/env python
+"""Per-request latency of the IVF-Flat index against the exact Flat index.
+
+One process, one clustered corpus of ``--rows`` x 128 (default 1,000,000;
+unit-norm rows around 4,096 Gaussian centres, queries = perturbed corpus
+rows), float16 and float32 storage, nq in {1, 8}, k = 100, "IVF1024,Flat",
+nprobe in {1, 8, 20, 64}. The yardstick is the Flat ``OnlineSearcher`` on the
+same box in the same process: its calls and the ``OnlineIVFSearcher``'s
+alternate call by call (host clock around calls that end in a synchronise).
+
+Per case: p50 / p99 of both calls and their ratio, the hipEvent time of the
+coarse and the scan launches alone, the bytes the scan touches (rows of the
+probed lists, averaged over the queries) and recall@k of the IVF result
+against the Flat result on the same queries. The build time of each index is
+reported once. ``--chunk-tiles`` adds the scan alone at other chunk floors
+(rt_ivf_topk_tuning) — the measurement behind the plan's rule.
+
+Prints one JSON line per case and a closing summary line; run it under a time
+limit, e.g. ``timeout 900 python tools/ivf_latency.py > profiles/ivf_latency.txt``.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (REPO, os.path.join(REPO, "real-time-recommendation-system-with-feature-store_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import torch  # noqa: E402
+
+from rtrec_amd import kernels  # noqa: E402
+from rtrec_amd.serving.retrieval import HipFlatIPIndex, HipIVFFlatIndex  # noqa: E402
+
+
+def pct(samples_ms):
+    a = np.sort(np.asarray(samples_ms, np.float64))
+    return {"p50_ms": round(float(a[len(a) // 2]), 5), "p99_ms": round(float(a[min(len(a) - 1, int(len(a) * 0.99))]), 5)}
+
+
+def timed_alternating(fns, calls, warmup):
+    for _ in range(warmup):
+        for f in fns.values():
+            f()
+    out = {name: [] for name in fns}
+    for _ in range(calls):
+        for name, f in fns.items():
+            t0 = time.perf_counter()
+            f()
+            out[name].append((time.perf_counter() - t0) * 1e3)
+    return {name: pct(v) for name, v in out.items()}
+
+
+def event_timed(fns, calls, warmup):
+    for _ in range(warmup):
+        for f in fns.values():
+            f()
+    torch.cuda.synchronize()
+    evs = {name: [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(calls)]
+           for name in fns}
+    for i in range(calls):
+        for name, f in fns.items():
+            a, b = evs[name][i]
+            a.record()
+            f()
+            b.record()
+    torch.cuda.synchronize()
+    return {name: pct([a.elapsed_time(b) for a, b in evs[name]])["p50_ms"] for name in fns}
+
+
+def corpus(n, d, n_centres, n_queries, dev):
+    """Clustered unit-norm rows, generated on the device (fp32), and queries on the host."""
+    g = torch.Generator(device=dev).manual_seed(0)
+    centres = torch.nn.functional.normalize(torch.randn(n_centres, d, generator=g, device=dev), dim=1)
+    which = torch.randint(0, n_centres, (n,), generator=g, device=dev)
+    rows = centres[which] + 0.7 * torch.randn(n, d, generator=g, device=dev) / d ** 0.5
+    rows = torch.nn.functional.normalize(rows, dim=1)
+    pick = torch.randint(0, n, (n_queries,), generator=g, device=dev)
+    q = torch.nn.functional.normalize(rows[pick] + 0.05 * torch.randn(n_queries, d, generator=g, device=dev), dim=1)
+    return rows, q.cpu().numpy()
+
+
+def recall(got, want):
+    return float(np.mean([len(set(g[g >= 0]) & set(w[w >= 0])) / max(1, (w >= 0).sum()) for g, w in zip(got, want)]))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, default=1_000_000)
+    ap.add_argument("--dim", type=int, default=128)
+    ap.add_argument("--nlist", type=int, default=1024)
+    ap.add_argument("--k", type=int, default=100)
+    ap.add_argument("--calls", type=int, default=300)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--storage", default="float16,float32")
+    ap.add_argument("--nprobe", default="1,8,20,64")
+    ap.add_argument("--nq", default="1,8")
+    ap.add_argument("--chunk-tiles", default="", help="comma list of chunk floors (256-row tiles) for the scan alone")
+    ap.add_argument("--train-iters", type=int, default=10)
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    n, d, k = args.rows, args.dim, args.k
+    rows, queries = corpus(n, d, 4096, 64, dev)
+    ids = []   # positions only: the id maps are not what is measured
+    summary = {"rows": n, "dim": d, "k": k, "nlist": args.nlist, "cases": []}
+    for storage in args.storage.split(","):
+        flat = HipFlatIPIndex({"dimension": d, "metric": "cosine", "storage_dtype": storage})
+        t0 = time.perf_counter()
+        flat.build(rows, ids)
+        torch.cuda.synchronize()
+        t_flat = time.perf_counter() - t0
+        ivf = HipIVFFlatIndex({"dimension": d, "metric": "cosine", "storage_dtype": storage, "nprobe": 20,
+                               "index_factory": f"IVF{args.nlist},Flat", "train_iters": args.train_iters})
+        t0 = time.perf_counter()
+        ivf.build(rows, ids)
+        torch.cuda.synchronize()
+        t_ivf = time.perf_counter() - t0
+        lens = torch.diff(ivf.list_offsets).cpu().numpy()
+        print(json.dumps({"leg": "build", "storage": storage, "flat_build_s": round(t_flat, 3),
+                          "ivf_build_s": round(t_ivf, 3), "max_list_rows": int(lens.max()),
+                          "min_list_rows": int(lens.min()), "empty_lists": int((lens == 0).sum())}), flush=True)
+        s_flat, s_ivf = flat.online_searcher(8), ivf.online_searcher(8)
+        esz = 2 if storage == "float16" else 4
+        for nq in [int(x) for x in args.nq.split(",")]:
+            batches = [queries[i * nq:(i + 1) * nq] for i in range(len(queries) // nq)]
+            want = np.concatenate([s_flat.search(b, k)[1].copy() for b in batches])
+            for nprobe in [int(x) for x in args.nprobe.split(",")]:
+                ivf.nprobe = nprobe
+                got = np.concatenate([s_ivf.search(b, k)[1].copy() for b in batches])
+                state = {"i": 0}
+
+                def call(s):
+                    def f():
+                        state["i"] += 1
+                        s.search(batches[state["i"] % len(batches)], k)
+                    return f
+                host = timed_alternating({"flat": call(s_flat), "ivf": call(s_ivf)}, args.calls, args.warmup)
+                # the launches alone
+                q32 = torch.from_numpy(np.ascontiguousarray(batches[0])).to(dev)
+                qs = q32.to(ivf.storage_dtype)
+                _, probes = kernels.flatip_topk_online(q32, ivf.centroids, nprobe)
+                probed_rows = float(lens[probes.cpu().numpy()].sum(axis=1).mean())
+                launches = {
+                    "flat_online": lambda: kernels.flatip_topk_online(qs, flat.index[: flat.current_size], k),
+                    "ivf_coarse": lambda: kernels.flatip_topk_online(q32, ivf.centroids, nprobe),
+                    "ivf_scan": lambda: kernels.ivf_topk(qs, ivf.index, ivf.list_offsets, ivf.row_pos, probes,
+                                                         ivf.max_list_rows, k),
+                }
+                ev = event_timed(launches, args.calls, args.warmup)
+                case = {"leg": "search", "storage": storage, "nq": nq, "nprobe": nprobe,
+                        "flat": host["flat"], "ivf": host["ivf"],
+                        "ivf_over_flat_p50": round(host["ivf"]["p50_ms"] / host["flat"]["p50_ms"], 3),
+                        "event_p50_ms": ev, "plan": kernels.ivf_topk_plan(nq, nprobe, ivf.max_list_rows),
+                        "scan_bytes_per_query": int(probed_rows * d * esz),
+                        "flat_bytes": int(n * d * esz),
+                        f"recall_at_{k}": round(recall(got, want), 4)}
+                if args.chunk_tiles:
+                    sweep = {}
+                    for tiles in [int(x) for x in args.chunk_tiles.split(",")]:
+                        kernels.ivf_topk_tuning(tiles)
+                        sweep[str(tiles)] = event_timed({"s": launches["ivf_scan"]}, args.calls, args.warmup)["s"]
+                    kernels.ivf_topk_tuning(0)
+                    case["scan_event_p50_ms_by_chunk_tiles"] = sweep
+                print(json.dumps(case), flush=True)
+                summary["cases"].append({key: case[key] for key in ("storage", "nq", "nprobe", "ivf_over_flat_p50",
+                                                                     f"recall_at_{k}")})
+        del s_flat, s_ivf, flat, ivf
+        torch.cuda.empty_cache()
+    print(json.dumps(summary), flush=True)
+
+
+if __name__ == "__main__":
+    main()
