@@ -8,19 +8,20 @@
 // 1. ivf_scan: grid (probe x chunk, query). The corpus is stored
 //    list-contiguous; block (p, c) of query q reads probes[q][p], clamps chunk c
 //    of that list to [off[l], off[l + 1]) and to [0, nx), and leaves at once
-//    (its partial list all "none") when nothing is left. Otherwise it is the
-//    online scan (topk_online.h) for ONE query: a wave walks 64-row groups of
-//    256-row tiles, one lane per row, 128 B of every row per step through
-//    registers into the padded LDS stage, the query in LDS as fp32, every score
-//    one lane's chain acc = fmaf(q[j], x[j], acc), j ascending: the chain of
-//    oracle/flatip.c, so scores are bit-identical to the Flat index's. What
-//    differs from the online scan is the id: a candidate carries the ORIGINAL
-//    corpus position row_pos[row], the exclusion bitmap is indexed by it, and
-//    the composite key (score key << 32 | ~position) holds the tie rule — the
-//    storage order does not reach the result. Rows therefore do NOT arrive in
-//    id order, and the filter threshold after a compaction is the lowest score
-//    kept (an equal later score may still win on its position), never the
-//    "strictly above" of compact_stream's tie case.
+//    (its partial list all "none") when nothing is left. Over that row window it
+//    runs the online scan's row stream for ONE query — online::score_tile,
+//    online::append and online::write_block_list (topk_online.h) are the same
+//    code, so scores are bit-identical to the Flat index's. What differs:
+//      * the id: a candidate carries the ORIGINAL corpus position row_pos[row],
+//        the exclusion bitmap is indexed by it, and the composite key (score
+//        key << 32 | ~position) holds the tie rule — the storage order does
+//        not reach the result;
+//      * the compaction: rows therefore do NOT arrive in id order, and the
+//        filter threshold after a compaction is the lowest score kept (an
+//        equal later score may still win on its position), never the
+//        "strictly above" of compact_stream's tie case;
+//      * the append is guarded: a row_pos that repeats positions gives equal
+//        keys, of which a compaction may keep more than its limit.
 // 2. flatip_online_finish (topk_online.h, unchanged): one block per query over
 //    the nprobe x chunks <= 512 sorted partial lists.
 //
@@ -81,7 +82,6 @@ __global__ __launch_bounds__(on::kThreads, 2) void ivf_scan(
     const uint32_t* __restrict__ excl, int64_t excl_words, uint64_t* __restrict__ partials) {
     constexpr int EPU = 16 / static_cast<int>(sizeof(T));
     constexpr int kThreads = on::kThreads, kTileRows = on::kTileRows, kStepUnits = on::kStepUnits;
-    constexpr int kRowStride = on::kRowStride, kRoom = on::kRoom;
     using L = on::Lds<1>;
     __shared__ __attribute__((aligned(16))) char lds[L::kBytes];
     __shared__ int cnt;
@@ -93,7 +93,9 @@ __global__ __launch_bounds__(on::kThreads, 2) void ivf_scan(
     uint64_t* const out = partials + static_cast<int64_t>(q) * k * lists + lb;  // [q][rank][lb]
 
     // the chunk, clamped to the list and to the corpus
-    int64_t row_begin = 0, row_end = 0;
+    on::RowWindow w;
+    w.X = X;
+    w.row_begin = w.row_end = 0;
     const int64_t l = probes[static_cast<int64_t>(q) * nprobe + p];
     if (l >= 0 && l < nlist) {
         int64_t lo = list_offsets[l], hi = list_offsets[l + 1];
@@ -102,12 +104,12 @@ __global__ __launch_bounds__(on::kThreads, 2) void ivf_scan(
         if (lo < hi) {
             const int64_t len = hi - lo, first = static_cast<int64_t>(c) * rows_per_chunk;
             if (first < len) {
-                row_begin = lo + first;
-                row_end = (first + rows_per_chunk) < len ? (row_begin + rows_per_chunk) : hi;
+                w.row_begin = lo + first;
+                w.row_end = (first + rows_per_chunk) < len ? (w.row_begin + rows_per_chunk) : hi;
             }
         }
     }
-    if (row_end <= row_begin) {  // block-uniform
+    if (w.row_end <= w.row_begin) {  // block-uniform
         for (int r = threadIdx.x; r < k; r += kThreads) out[static_cast<int64_t>(r) * lists] = 0ull;
         return;
     }
@@ -116,10 +118,10 @@ __global__ __launch_bounds__(on::kThreads, 2) void ivf_scan(
     Cand* const cand = reinterpret_cast<Cand*>(lds + L::kStage);
     float* const qs = reinterpret_cast<float*>(lds + L::kStage + L::kCand);
     uint32_t* const hist = reinterpret_cast<uint32_t*>(lds + L::kStage + L::kCand + L::kQuery) + wave * 256;
-    const int units = d / EPU;
-    const int64_t row_bytes = static_cast<int64_t>(units) * 16;
-    const int steps = (units + kStepUnits - 1) / kStepUnits;
-    const int tiles = static_cast<int>((row_end - row_begin + kTileRows - 1) / kTileRows);
+    w.units = d / EPU;
+    w.row_bytes = static_cast<int64_t>(w.units) * 16;
+    w.steps = (w.units + kStepUnits - 1) / kStepUnits;
+    w.tiles = static_cast<int>((w.row_end - w.row_begin + kTileRows - 1) / kTileRows);
 
     for (int e = threadIdx.x; e < d; e += kThreads) qs[e] = to_f32(Q[static_cast<int64_t>(q) * d + e]);
     if (threadIdx.x == 0) {
@@ -127,31 +129,17 @@ __global__ __launch_bounds__(on::kThreads, 2) void ivf_scan(
         thr = -INFINITY;
     }
 
-    // step (tile t, column step cs) of this wave: slot i of lane l is unit
-    // cs * 8 + (f & 7) of group row f >> 3, f = 64 i + l (the online scan's)
     uint4 R[kStepUnits];
-    auto load_step = [&](int t, int cs) {
-        const int64_t g0 = row_begin + static_cast<int64_t>(t) * kTileRows + wave * 64;
-#pragma unroll
-        for (int i = 0; i < kStepUnits; ++i) {
-            const int f = i * 64 + lane;
-            const int u = cs * kStepUnits + (f & 7);
-            const int64_t row = g0 + (f >> 3);
-            R[i] = make_uint4(0u, 0u, 0u, 0u);
-            if (t < tiles && u < units && row < row_end)
-                R[i] = *reinterpret_cast<const uint4*>(X + row * row_bytes + static_cast<int64_t>(u) * 16);
-        }
-    };
-    load_step(0, 0);
+    on::load_step(R, w, 0, 0);
     __syncthreads();
 
-    int over = 0;  // decided through the barrier that ends a tile: block-uniform
-    for (int t = 0; t < tiles; ++t) {
+    int over = 0;  // decided through the barrier that ends a tile: block-uniform (flatip_online_scan)
+    for (int t = 0; t < w.tiles; ++t) {
         if (over) {
             if (wave == 0) {
                 int n = cnt;
                 float th = thr;
-                compact_keep_ties(cand, n, k, kRoom, hist, th);
+                compact_keep_ties(cand, n, k, on::kRoom, hist, th);
                 if (lane == 0) {
                     cnt = n;
                     thr = th;
@@ -160,86 +148,23 @@ __global__ __launch_bounds__(on::kThreads, 2) void ivf_scan(
             __syncthreads();
         }
         const float th = thr;
-        const int64_t row = row_begin + static_cast<int64_t>(t) * kTileRows + wave * 64 + lane;
+        const int64_t row = w.row_begin + static_cast<int64_t>(t) * kTileRows + wave * 64 + lane;
         // original position of this lane's row: in flight under the scores
-        const int32_t pos = row < row_end ? row_pos[row] : -1;
+        const int32_t pos = row < w.row_end ? row_pos[row] : -1;
 
-        float acc = 0.f;
-        for (int cs = 0; cs < steps; ++cs) {
-#pragma unroll
-            for (int i = 0; i < kStepUnits; ++i) {
-                const int f = i * 64 + lane;
-                *reinterpret_cast<uint4*>(stage + (f >> 3) * kRowStride + (f & 7) * 16) = R[i];
-            }
-            if (cs + 1 < steps) load_step(t, cs + 1);
-            else load_step(t + 1, 0);
-            wave_lds_sync();
-            const int nu = (units - cs * kStepUnits) < kStepUnits ? (units - cs * kStepUnits) : kStepUnits;
-#pragma unroll
-            for (int u = 0; u < kStepUnits; ++u) {
-                if (u >= nu) break;  // wave-uniform
-                const uint4 xv = *reinterpret_cast<const uint4*>(stage + lane * kRowStride + u * 16);
-                float x[EPU];
-                on::widen(xv, x, T());
-                const int j0 = (cs * kStepUnits + u) * EPU;
-#pragma unroll
-                for (int h = 0; h < EPU / 4; ++h) {
-                    const float4 qv = *reinterpret_cast<const float4*>(qs + j0 + 4 * h);
-                    acc = __builtin_fmaf(qv.x, x[4 * h], acc);
-                    acc = __builtin_fmaf(qv.y, x[4 * h + 1], acc);
-                    acc = __builtin_fmaf(qv.z, x[4 * h + 2], acc);
-                    acc = __builtin_fmaf(qv.w, x[4 * h + 3], acc);
-                }
-            }
-            wave_lds_sync();  // the stage is rewritten by the next step
-        }
+        float acc[1];
+        on::score_tile<T, 1>(R, w, t, stage, qs, d, acc);
 
         // ---- selection: at most one append per row ----
         // a position outside [0, nx) (a corrupt row_pos) is dropped: it has no bit in
         // the bitmap and no row in the caller's corpus
-        bool pass = pos >= 0 && static_cast<int64_t>(pos) < nx && acc >= th;
+        bool pass = pos >= 0 && static_cast<int64_t>(pos) < nx && acc[0] >= th;
         if (excl && pass)
             pass = ((excl[static_cast<int64_t>(q) * excl_words + (pos >> 5)] >> (pos & 31)) & 1u) == 0u;
-        int mine_over = 0;
-        const uint64_t bm = __ballot(pass);
-        if (bm) {
-            int base = 0;
-            if (lane == 0) base = atomicAdd(&cnt, __popcll(bm));
-            base = __shfl(base, 0, 64);
-            mine_over = (base + __popcll(bm)) > kRoom ? 1 : 0;
-            const int at = base + static_cast<int>(__builtin_amdgcn_mbcnt_hi(
-                                      static_cast<uint32_t>(bm >> 32),
-                                      __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(bm), 0u)));
-            // at < kCap by the append budget; the test only guards a row_pos that
-            // repeats positions (equal keys, which no compaction can tell apart)
-            if (pass && at < on::kCap) cand[at] = Cand{acc, static_cast<uint32_t>(pos)};
-        }
-        over = __syncthreads_or(mine_over);
+        over = __syncthreads_or(on::append<true>(pass, &cnt, cand, acc[0], static_cast<uint32_t>(pos)));
     }
 
-    // ---- the block's list: the k best, sorted, as composite keys ----
-    if (wave != 0) return;
-    int n = cnt;
-    if (n > v4::kFinishCap) {
-        float th = 0.f;
-        v4::compact_stream(cand, n, k, v4::kFinishCap, hist, th);
-    }
-    wave_lds_sync();
-    float s[2];
-    uint32_t id[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int r = lane * 2 + j;
-        const Cand cd = r < n ? cand[r] : Cand{-INFINITY, kEmptyId};
-        s[j] = cd.s;
-        id[j] = cd.i;
-    }
-    wave_sort_regs2(s, id);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int r = lane * 2 + j;
-        if (r < k) out[static_cast<int64_t>(r) * lists] = id[j] != kEmptyId ? v4::ckey(Cand{s[j], id[j]}) : 0ull;
-    }
+    if (wave == 0) on::write_block_list(cand, cnt, k, hist, out, lists);
 }
 
 // ---- rt_segment_mean_f32 ----
@@ -313,10 +238,6 @@ static_assert(RT_IVF_MAX_NPROBE == iv::kMaxProbe && RT_IVF_MAX_K == ivon::kMaxK,
 
 static int g_ivf_min_tiles = 1;
 
-static bool ivf_shape_ok(int d, int dtype) {
-    return dtype == RT_F32 ? (d % 4 == 0 && d <= 256) : (d % 8 == 0 && d <= 256);
-}
-
 extern "C" int rt_ivf_topk_tuning(int min_chunk_tiles) {
     if (min_chunk_tiles < 0 || min_chunk_tiles > 4096) return RT_ERR_INVALID;
     g_ivf_min_tiles = min_chunk_tiles ? min_chunk_tiles : 1;
@@ -351,7 +272,7 @@ extern "C" int rt_ivf_topk(const void* queries, int64_t nq, const void* rows, in
         return RT_ERR_INVALID;
     if (k > ivon::kMaxK || nprobe > iv::kMaxProbe || nq > iv::kMaxNq) return RT_ERR_UNSUPPORTED;
     if (dtype != RT_F32 && dtype != RT_F16 && dtype != RT_BF16) return RT_ERR_INVALID;
-    if (!ivf_shape_ok(d, dtype)) return RT_ERR_UNSUPPORTED;
+    if (!ivon::shape_ok(d, dtype)) return RT_ERR_UNSUPPORTED;
     if (nx >= 0x7FFFFFFFll || max_list_rows >= 0xFFFFFFFFll) return RT_ERR_UNSUPPORTED;  // positions are int32
     if ((reinterpret_cast<uintptr_t>(queries) | reinterpret_cast<uintptr_t>(rows)) & 15) return RT_ERR_INVALID;
     if (exclude_bits && exclude_words < (nx + 31) / 32) return RT_ERR_INVALID;
@@ -376,9 +297,7 @@ extern "C" int rt_ivf_topk(const void* queries, int64_t nq, const void* rows, in
 #undef RT_IVF_LAUNCH
     int rc = check_launch("ivf_scan");
     if (rc) return rc;
-    hipLaunchKernelGGL(ivon::flatip_online_finish, dim3(static_cast<unsigned>(nq)), dim3(ivon::kMaxBlocks), 0, st,
-                       partials, lists, k, out_scores, out_ids, static_cast<int64_t>(0));
-    return check_launch("flatip_online_finish");
+    return ivon::launch_finish(partials, lists, k, out_scores, out_ids, 0, nq, st);
 }
 
 extern "C" int rt_segment_mean_f32(const void* rows, int64_t n, int d, int dtype, const int64_t* offsets,
@@ -387,7 +306,7 @@ extern "C" int rt_segment_mean_f32(const void* rows, int64_t n, int d, int dtype
     if (n_seg == 0) return RT_OK;
     if (!offsets || !prev || !out || (n > 0 && !rows)) return RT_ERR_INVALID;
     if (dtype != RT_F32 && dtype != RT_F16 && dtype != RT_BF16) return RT_ERR_INVALID;
-    if (!ivf_shape_ok(d, dtype) || n_seg > 0x7FFFFFFFll) return RT_ERR_UNSUPPORTED;
+    if (!ivon::shape_ok(d, dtype) || n_seg > 0x7FFFFFFFll) return RT_ERR_UNSUPPORTED;
     if (reinterpret_cast<uintptr_t>(rows) & 15) return RT_ERR_INVALID;
     hipStream_t st = as_stream(stream);
     const dim3 grid(static_cast<unsigned>(n_seg)), block(iv::kMeanThreads);

@@ -55,6 +55,12 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// rank of this lane among the set bits of a ballot: the set bits below it
+__device__ __forceinline__ int ballot_rank(uint64_t bm) {
+    return static_cast<int>(__builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(bm >> 32),
+                                                      __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(bm), 0u)));
+}
+
 // order LDS traffic of one wave: DS ops of a wave complete in order; this also
 // stops the compiler from hoisting reads above earlier writes by other lanes
 __device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }

@@ -173,9 +173,7 @@ __global__ __launch_bounds__(256) void topk_merge_select_kernel(const float* __r
                 const uint64_t kb = key[e] & pmask;
                 const bool take = ((vmask >> e) & 1u) && (pass == 0 ? kb > prefix : kb == prefix);
                 const uint64_t bm = __ballot(take);
-                const int pos = m + static_cast<int>(__builtin_amdgcn_mbcnt_hi(
-                                        static_cast<uint32_t>(bm >> 32),
-                                        __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(bm), 0u)));
+                const int pos = m + ballot_rank(bm);
                 if (take && pos < v4::kFinishCap)
                     keep[pos] = Cand{v2::okey_inv(static_cast<uint32_t>(key[e] >> 32)), ~static_cast<uint32_t>(key[e])};
                 m += __popcll(bm);

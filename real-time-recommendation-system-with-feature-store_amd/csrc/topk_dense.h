@@ -191,9 +191,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void d
         while (__ballot(pm != 0ull)) {
             const bool has = pm != 0ull;
             const uint64_t bm = __ballot(has);
-            const int pos = m + static_cast<int>(__builtin_amdgcn_mbcnt_hi(
-                                    static_cast<uint32_t>(bm >> 32),
-                                    __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(bm), 0u)));
+            const int pos = m + ballot_rank(bm);
             if (has) {
                 const int e = __builtin_ctzll(pm);
                 pm &= pm - 1ull;

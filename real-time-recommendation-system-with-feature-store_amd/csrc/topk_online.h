@@ -246,6 +246,122 @@ __device__ __forceinline__ void widen(const uint4& v, float (&x)[8], __hip_bfloa
     }
 }
 
+// ---- the row stream both scans share (flatip_online_scan; ivf_scan, ivf.hip) ----
+// A block's row window: the stored rows [row_begin, row_end) of X, `units`
+// 16-byte units each, walked in `tiles` 256-row tiles of `steps` column steps.
+struct RowWindow {
+    const char* X;
+    int64_t row_begin, row_end, row_bytes;
+    int units, steps, tiles;
+};
+
+// step (tile t, column step c) of this wave: slot i of lane l is unit
+// c * 8 + (f & 7) of group row f >> 3, f = 64 i + l
+__device__ __forceinline__ void load_step(uint4 (&R)[kStepUnits], const RowWindow& w, int t, int c) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t g0 = w.row_begin + static_cast<int64_t>(t) * kTileRows + wave * 64;
+#pragma unroll
+    for (int i = 0; i < kStepUnits; ++i) {
+        const int f = i * 64 + lane;
+        const int u = c * kStepUnits + (f & 7);
+        const int64_t row = g0 + (f >> 3);
+        R[i] = make_uint4(0u, 0u, 0u, 0u);
+        if (t < w.tiles && u < w.units && row < w.row_end)
+            R[i] = *reinterpret_cast<const uint4*>(w.X + row * w.row_bytes + static_cast<int64_t>(u) * 16);
+    }
+}
+
+// Staged score chain: acc[qi] = the score of query qi (fp32 in LDS at
+// qs + qi * d) against this lane's row of tile t — the wave's 64-row group,
+// lane = row. R holds the tile's first step on entry (load_step) and the next
+// tile's first step on return: every step is loaded one ahead of its compute.
+template <typename T, int NQ>
+__device__ __forceinline__ void score_tile(uint4 (&R)[kStepUnits], const RowWindow& w, int t, char* stage,
+                                           const float* qs, int d, float (&acc)[NQ]) {
+    constexpr int EPU = 16 / static_cast<int>(sizeof(T));  // elements per 16-byte unit
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int qi = 0; qi < NQ; ++qi) acc[qi] = 0.f;
+    for (int c = 0; c < w.steps; ++c) {
+#pragma unroll
+        for (int i = 0; i < kStepUnits; ++i) {
+            const int f = i * 64 + lane;
+            *reinterpret_cast<uint4*>(stage + (f >> 3) * kRowStride + (f & 7) * 16) = R[i];
+        }
+        if (c + 1 < w.steps) load_step(R, w, t, c + 1);
+        else load_step(R, w, t + 1, 0);
+        wave_lds_sync();
+        const int nu = (w.units - c * kStepUnits) < kStepUnits ? (w.units - c * kStepUnits) : kStepUnits;
+#pragma unroll
+        for (int u = 0; u < kStepUnits; ++u) {
+            if (u >= nu) break;  // wave-uniform
+            const uint4 xv = *reinterpret_cast<const uint4*>(stage + lane * kRowStride + u * 16);
+            float x[EPU];
+            widen(xv, x, T());
+            const int j0 = (c * kStepUnits + u) * EPU;
+#pragma unroll
+            for (int qi = 0; qi < NQ; ++qi) {
+#pragma unroll
+                for (int h = 0; h < EPU / 4; ++h) {
+                    const float4 qv = *reinterpret_cast<const float4*>(qs + qi * d + j0 + 4 * h);
+                    acc[qi] = __builtin_fmaf(qv.x, x[4 * h], acc[qi]);
+                    acc[qi] = __builtin_fmaf(qv.y, x[4 * h + 1], acc[qi]);
+                    acc[qi] = __builtin_fmaf(qv.z, x[4 * h + 2], acc[qi]);
+                    acc[qi] = __builtin_fmaf(qv.w, x[4 * h + 3], acc[qi]);
+                }
+            }
+        }
+        wave_lds_sync();  // the stage is rewritten by the next step
+    }
+}
+
+// Append (s, id) of the lanes with `pass` to one query's candidate buffer: one
+// LDS atomic per wave, positions by ballot rank. `pass` comes from registers
+// and LDS only — a per-lane global load between the scores and the ballot
+// would be waited for with every load before it drained, the next tile's
+// prefetch included. Returns whether this append took the buffer above kRoom.
+// The position is < kCap by the append budget; GUARD tests it all the same,
+// for a caller whose ids may repeat (equal keys, which no compaction can tell
+// apart, so a compaction may leave more than kRoom).
+template <bool GUARD>
+__device__ __forceinline__ int append(bool pass, int* cnt, Cand* buf, float s, uint32_t id) {
+    const uint64_t bm = __ballot(pass);
+    if (!bm) return 0;
+    int base = 0;
+    if ((threadIdx.x & 63) == 0) base = atomicAdd(cnt, __popcll(bm));
+    base = __shfl(base, 0, 64);
+    const int at = base + ballot_rank(bm);
+    if (pass && (!GUARD || at < kCap)) buf[at] = Cand{s, id};
+    return (base + __popcll(bm)) > kRoom ? 1 : 0;
+}
+
+// wave: the block's list of one query — the k best of buf[0, n), sorted, as
+// composite keys to out[rank * stride], 0 for none
+__device__ __forceinline__ void write_block_list(Cand* buf, int n, int k, uint32_t* hist, uint64_t* out,
+                                                 int64_t stride) {
+    const int lane = threadIdx.x & 63;
+    if (n > v4::kFinishCap) {
+        float th = 0.f;
+        v4::compact_stream(buf, n, k, v4::kFinishCap, hist, th);
+    }
+    wave_lds_sync();
+    float s[2];
+    uint32_t id[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int r = lane * 2 + j;
+        const Cand cd = r < n ? buf[r] : Cand{-INFINITY, kEmptyId};
+        s[j] = cd.s;
+        id[j] = cd.i;
+    }
+    wave_sort_regs2(s, id);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int r = lane * 2 + j;
+        if (r < k) out[r * stride] = id[j] != kEmptyId ? v4::ckey(Cand{s[j], id[j]}) : 0ull;
+    }
+}
+
 // LISTS: the exclusions are `la`'s CSR lists (excl is not read); otherwise the
 // optional dense bitmap `excl`.
 template <typename T, int NQ, bool LISTS>
@@ -253,7 +369,7 @@ __global__ __launch_bounds__(kThreads, 2) void flatip_online_scan(
     const T* __restrict__ Q, int nq, const char* __restrict__ X, int64_t nx, int d, int k,
     const uint32_t* __restrict__ excl, int64_t excl_words, int64_t rows_per_block, int blocks,
     uint64_t* __restrict__ partials, const ListArgs<LISTS> la) {
-    constexpr int EPU = 16 / static_cast<int>(sizeof(T));  // elements per 16-byte unit
+    constexpr int EPU = 16 / static_cast<int>(sizeof(T));
     __shared__ __attribute__((aligned(16))) char lds[Lds<NQ, LISTS>::kBytes];
     __shared__ int cnt[kMaxNq];
     __shared__ float thr[kMaxNq];
@@ -264,12 +380,14 @@ __global__ __launch_bounds__(kThreads, 2) void flatip_online_scan(
                            (threadIdx.x >> 6) * 256;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int b = blockIdx.x;
-    const int64_t row_begin = static_cast<int64_t>(b) * rows_per_block;
-    const int64_t row_end = (row_begin + rows_per_block) < nx ? (row_begin + rows_per_block) : nx;
-    const int units = d / EPU;                // 16-byte units per row
-    const int64_t row_bytes = static_cast<int64_t>(units) * 16;
-    const int steps = (units + kStepUnits - 1) / kStepUnits;
-    const int tiles = static_cast<int>((row_end - row_begin + kTileRows - 1) / kTileRows);
+    RowWindow w;
+    w.X = X;
+    w.row_begin = static_cast<int64_t>(b) * rows_per_block;
+    w.row_end = (w.row_begin + rows_per_block) < nx ? (w.row_begin + rows_per_block) : nx;
+    w.units = d / EPU;
+    w.row_bytes = static_cast<int64_t>(w.units) * 16;
+    w.steps = (w.units + kStepUnits - 1) / kStepUnits;
+    w.tiles = static_cast<int>((w.row_end - w.row_begin + kTileRows - 1) / kTileRows);
 
     // queries as fp32 (padding queries: zeros), counters, thresholds
     for (int e = threadIdx.x; e < NQ * d; e += kThreads) {
@@ -281,22 +399,8 @@ __global__ __launch_bounds__(kThreads, 2) void flatip_online_scan(
         thr[threadIdx.x] = -INFINITY;
     }
 
-    // step (tile t, column step c) of this wave: slot i of lane l is unit
-    // c * 8 + (f & 7) of group row f >> 3, f = 64 i + l
     uint4 R[kStepUnits];
-    auto load_step = [&](int t, int c) {
-        const int64_t g0 = row_begin + static_cast<int64_t>(t) * kTileRows + wave * 64;
-#pragma unroll
-        for (int i = 0; i < kStepUnits; ++i) {
-            const int f = i * 64 + lane;
-            const int u = c * kStepUnits + (f & 7);
-            const int64_t row = g0 + (f >> 3);
-            R[i] = make_uint4(0u, 0u, 0u, 0u);
-            if (t < tiles && u < units && row < row_end)
-                R[i] = *reinterpret_cast<const uint4*>(X + row * row_bytes + static_cast<int64_t>(u) * 16);
-        }
-    };
-    load_step(0, 0);
+    load_step(R, w, 0, 0);
     ListState ls{};
     if constexpr (LISTS) {
         // while the first step is in flight: the cursors and tile 0's window
@@ -306,21 +410,21 @@ __global__ __launch_bounds__(kThreads, 2) void flatip_online_scan(
         ls.end = ls.cur + P;
         ls.next = reinterpret_cast<int32_t*>(ls.end + P);
         ls.win = reinterpret_cast<uint32_t*>(ls.next + P);
-        lists_begin<NQ>(la, ls, nq, row_begin);
+        lists_begin<NQ>(la, ls, nq, w.row_begin);
         wave_lds_sync();
-        lists_window<NQ>(la, ls, nq, 0, row_begin, row_end);
+        lists_window<NQ>(la, ls, nq, 0, w.row_begin, w.row_end);
     }
     __syncthreads();
 
     // `over`: some buffer holds more than kRoom entries. The decision is taken
     // THROUGH the barrier that ends a tile (__syncthreads_or over what every
-    // wave's own atomicAdd returned: the last append to a query saw base + n =
+    // wave's own append returned: the last append to a query saw base + n =
     // its final count), never by reading cnt, which waves already in the next
     // tile's selection may be raising: so the branch below, which holds a
     // barrier, is block-uniform, and the check sees every append of the tiles
     // before and none of this one.
     int over = 0;
-    for (int t = 0; t < tiles; ++t) {
+    for (int t = 0; t < w.tiles; ++t) {
         if (over) {
             for (int qi = wave; qi < NQ; qi += kWavesS) {
                 int n = cnt[qi];
@@ -339,110 +443,43 @@ __global__ __launch_bounds__(kThreads, 2) void flatip_online_scan(
 #pragma unroll
         for (int qi = 0; qi < NQ; ++qi) th[qi] = thr[qi];
 
-        // ---- scores of this wave's 64 rows: lane = row ----
         float acc[NQ];
-#pragma unroll
-        for (int qi = 0; qi < NQ; ++qi) acc[qi] = 0.f;
-        for (int c = 0; c < steps; ++c) {
-#pragma unroll
-            for (int i = 0; i < kStepUnits; ++i) {
-                const int f = i * 64 + lane;
-                *reinterpret_cast<uint4*>(stage + (f >> 3) * kRowStride + (f & 7) * 16) = R[i];
-            }
-            if (c + 1 < steps) load_step(t, c + 1);
-            else load_step(t + 1, 0);
-            wave_lds_sync();
-            const int nu = (units - c * kStepUnits) < kStepUnits ? (units - c * kStepUnits) : kStepUnits;
-#pragma unroll
-            for (int u = 0; u < kStepUnits; ++u) {
-                if (u >= nu) break;  // wave-uniform
-                const uint4 xv = *reinterpret_cast<const uint4*>(stage + lane * kRowStride + u * 16);
-                float x[EPU];
-                widen(xv, x, T());
-                const int j0 = (c * kStepUnits + u) * EPU;
-#pragma unroll
-                for (int qi = 0; qi < NQ; ++qi) {
-#pragma unroll
-                    for (int h = 0; h < EPU / 4; ++h) {
-                        const float4 qv = *reinterpret_cast<const float4*>(qs + qi * d + j0 + 4 * h);
-                        acc[qi] = __builtin_fmaf(qv.x, x[4 * h], acc[qi]);
-                        acc[qi] = __builtin_fmaf(qv.y, x[4 * h + 1], acc[qi]);
-                        acc[qi] = __builtin_fmaf(qv.z, x[4 * h + 2], acc[qi]);
-                        acc[qi] = __builtin_fmaf(qv.w, x[4 * h + 3], acc[qi]);
-                    }
-                }
-            }
-            wave_lds_sync();  // the stage is rewritten by the next step
-        }
+        score_tile<T, NQ>(R, w, t, stage, qs, d, acc);
 
         // ---- selection: appends of at most one entry per row and query ----
-        const int64_t row = row_begin + static_cast<int64_t>(t) * kTileRows + wave * 64 + lane;
-        const bool valid = row < row_end;
+        const int64_t row = w.row_begin + static_cast<int64_t>(t) * kTileRows + wave * 64 + lane;
+        const bool valid = row < w.row_end;
         int mine_over = 0;
 #pragma unroll
         for (int qi = 0; qi < NQ; ++qi) {
             if (qi < nq) {
-                // with exclude_bits this per-lane load is waited for with every
-                // load before it drained, the next tile's prefetch included: a
-                // call with exclusions loses the one-step-ahead streaming
                 bool pass = valid && acc[qi] >= th[qi];
                 if constexpr (LISTS) {
                     // bit wave * 64 + lane of the query's window: one wave-uniform
-                    // 8-byte LDS read, no global load between the scores and the ballot
+                    // 8-byte LDS read
                     const uint64_t wbits = *reinterpret_cast<const uint64_t*>(
                         ls.win + ((t & 1) * NQ + qi) * kWinWords + wave * 2);
                     pass = pass && ((wbits >> lane) & 1ull) == 0ull;
                 } else if (excl && pass)
+                    // the per-lane global load `append` warns of: a call with
+                    // exclude_bits loses the one-step-ahead streaming
                     pass = ((excl[qi * excl_words + (row >> 5)] >> (row & 31)) & 1u) == 0u;
-                const uint64_t bm = __ballot(pass);
-                if (bm) {
-                    int base = 0;
-                    if (lane == 0) base = atomicAdd(&cnt[qi], __popcll(bm));
-                    base = __shfl(base, 0, 64);
-                    mine_over |= (base + __popcll(bm)) > kRoom ? 1 : 0;
-                    const int pos = base + static_cast<int>(__builtin_amdgcn_mbcnt_hi(
-                                               static_cast<uint32_t>(bm >> 32),
-                                               __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(bm), 0u)));
-                    if (pass) cand[qi * kCap + pos] = Cand{acc[qi], static_cast<uint32_t>(row)};
-                }
+                mine_over |= append<false>(pass, &cnt[qi], cand + qi * kCap, acc[qi], static_cast<uint32_t>(row));
             }
         }
         if constexpr (LISTS) {
             // the next tile's window, into the buffer whose last readers (tile t - 1's
             // selection) are behind the barrier that ended that tile; the barrier
             // below publishes it
-            if (t + 1 < tiles) lists_window<NQ>(la, ls, nq, t + 1, row_begin, row_end);
+            if (t + 1 < w.tiles) lists_window<NQ>(la, ls, nq, t + 1, w.row_begin, w.row_end);
         }
         over = __syncthreads_or(mine_over);
     }
 
-    // ---- the block's list per query: the k best, sorted, as composite keys ----
-    for (int qi = wave; qi < nq; qi += kWavesS) {
-        int n = cnt[qi];
-        Cand* buf = cand + qi * kCap;
-        if (n > v4::kFinishCap) {
-            float th = 0.f;
-            v4::compact_stream(buf, n, k, v4::kFinishCap, hist, th);
-        }
-        wave_lds_sync();
-        float s[2];
-        uint32_t id[2];
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int r = lane * 2 + j;
-            const Cand cd = r < n ? buf[r] : Cand{-INFINITY, kEmptyId};
-            s[j] = cd.s;
-            id[j] = cd.i;
-        }
-        wave_sort_regs2(s, id);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int r = lane * 2 + j;
-            if (r < k)
-                partials[(static_cast<int64_t>(qi) * k + r) * blocks + b] =
-                    id[j] != kEmptyId ? v4::ckey(Cand{s[j], id[j]}) : 0ull;
-        }
-    }
+    // ---- the block's list per query: partials[query][rank][block] ----
+    for (int qi = wave; qi < nq; qi += kWavesS)
+        write_block_list(cand + qi * kCap, cnt[qi], k, hist, partials + (static_cast<int64_t>(qi) * k) * blocks + b,
+                         blocks);
 }
 
 // ---- finish ----
@@ -471,9 +508,7 @@ __device__ __forceinline__ void pool_select(uint64_t* pool, int& n, int k, uint3
             take = (key & pmask) >= prefix;
         }
         const uint64_t bm = __ballot(take);
-        const int pos = m + static_cast<int>(__builtin_amdgcn_mbcnt_hi(
-                                static_cast<uint32_t>(bm >> 32),
-                                __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(bm), 0u)));
+        const int pos = m + ballot_rank(bm);
         wave_lds_sync();
         if (take) pool[pos] = key;  // pos <= i: every lane read its entry before any lane writes
         m += __popcll(bm);
@@ -512,9 +547,7 @@ static __global__ __launch_bounds__(kMaxBlocks) void flatip_online_finish(const 
             int base = 0;
             if (lane == 0) base = atomicAdd(&pn, __popcll(bm));
             base = __shfl(base, 0, 64);
-            const int pos = base + static_cast<int>(__builtin_amdgcn_mbcnt_hi(
-                                       static_cast<uint32_t>(bm >> 32),
-                                       __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(bm), 0u)));
+            const int pos = base + ballot_rank(bm);
             if (take) pool[pos] = cur;
         }
         // no list has an entry at this rank at or above the bound: none has one
@@ -552,6 +585,19 @@ static __global__ __launch_bounds__(kMaxBlocks) void flatip_online_finish(const 
     wave_lds_sync();
     v4::finish_sort<2>(keep, n, k, out_s + static_cast<int64_t>(q) * k, out_i + static_cast<int64_t>(q) * k,
                        id_offset);
+}
+
+// one block per query over the `lists` sorted partial lists of a scan (0: none, every slot a pad)
+inline int launch_finish(const uint64_t* partials, int lists, int k, float* out_s, int64_t* out_i, int64_t id_offset,
+                         int64_t nq, hipStream_t st) {
+    hipLaunchKernelGGL(flatip_online_finish, dim3(static_cast<unsigned>(nq)), dim3(kMaxBlocks), 0, st, partials, lists,
+                       k, out_s, out_i, id_offset);
+    return check_launch("flatip_online_finish");
+}
+
+// rows the staged chain takes: whole 16-byte units, d <= 256 (the queries' LDS)
+inline bool shape_ok(int d, int dtype) {
+    return dtype == RT_F32 ? (d % 4 == 0 && d <= 256) : (d % 8 == 0 && d <= 256);
 }
 
 struct OnlinePlan {

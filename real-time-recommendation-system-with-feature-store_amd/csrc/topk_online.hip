@@ -8,14 +8,10 @@ namespace on = rt::topk::online;
 
 static_assert(RT_ONLINE_MAX_NQ == on::kMaxNq && RT_ONLINE_MAX_K == on::kMaxK, "rtrec_hip.h restates the kernel's limits");
 
-static bool online_shape_ok(int d, int dtype) {
-    return dtype == RT_F32 ? (d % 4 == 0 && d <= 256) : (d % 8 == 0 && d <= 256);
-}
-
 extern "C" int rt_flatip_topk_online_plan(int64_t nq, int64_t nx, int d, int dtype, int k, int64_t* out) {
     if (nq <= 0 || nx < 0 || d <= 0 || k <= 0 || !out) return RT_ERR_INVALID;
     if (dtype != RT_F32 && dtype != RT_F16 && dtype != RT_BF16) return RT_ERR_INVALID;
-    if (nq > on::kMaxNq || k > on::kMaxK || !online_shape_ok(d, dtype)) return RT_ERR_UNSUPPORTED;
+    if (nq > on::kMaxNq || k > on::kMaxK || !on::shape_ok(d, dtype)) return RT_ERR_UNSUPPORTED;
     const on::OnlinePlan p = on::make_plan(nx);
     out[0] = p.blocks;
     out[1] = p.rows_per_block;
@@ -41,7 +37,7 @@ static int online_search(const void* queries, int64_t nq, const void* items, int
     if (!queries || !out_scores || !out_ids || (nx > 0 && !items)) return RT_ERR_INVALID;
     if (nq > on::kMaxNq || k > on::kMaxK) return RT_ERR_UNSUPPORTED;
     if (dtype != RT_F32 && dtype != RT_F16 && dtype != RT_BF16) return RT_ERR_INVALID;
-    if (!online_shape_ok(d, dtype)) return RT_ERR_UNSUPPORTED;
+    if (!on::shape_ok(d, dtype)) return RT_ERR_UNSUPPORTED;
     if (nx >= 0xFFFFFFFFll || (id_offset + nx) >= 0xFFFFFFFFll || id_offset < 0) return RT_ERR_UNSUPPORTED;
     if ((reinterpret_cast<uintptr_t>(queries) | reinterpret_cast<uintptr_t>(items)) & 15) return RT_ERR_INVALID;
     if (exclude_bits && exclude_words < (nx + 31) / 32) return RT_ERR_INVALID;
@@ -71,9 +67,7 @@ static int online_search(const void* queries, int64_t nq, const void* items, int
         if (rc) return rc;
         blocks = p.blocks;
     }
-    hipLaunchKernelGGL(on::flatip_online_finish, dim3(static_cast<unsigned>(nq)), dim3(on::kMaxBlocks), 0, st,
-                       partials, blocks, k, out_scores, out_ids, id_offset);
-    return check_launch("flatip_online_finish");
+    return on::launch_finish(partials, blocks, k, out_scores, out_ids, id_offset, nq, st);
 }
 
 extern "C" int rt_flatip_topk_online(const void* queries, int64_t nq, const void* items, int64_t nx, int d,

@@ -138,8 +138,7 @@ __device__ __forceinline__ int compact_query_body(Cand* __restrict__ buf, int n0
 #pragma unroll
         for (int e = 0; e < kE; ++e) {
             const uint64_t m = __ballot(keep[e]);
-            const int pos = base + __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32),
-                                                             __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), 0u));
+            const int pos = base + ballot_rank(m);
             if (keep[e]) buf[(pos & 1) * kHalf + (pos >> 1)] = Cand{s[e], id[e]};
             base += __popcll(m);
         }

@@ -252,9 +252,7 @@ __device__ __forceinline__ void compact_stream(Cand* __restrict__ buf, int& n, i
             take = (ckey(c) & pmask) >= prefix;
         }
         const uint64_t bm = __ballot(take);
-        const int pos = m + static_cast<int>(__builtin_amdgcn_mbcnt_hi(
-                                static_cast<uint32_t>(bm >> 32),
-                                __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(bm), 0u)));
+        const int pos = m + ballot_rank(bm);
         if (take) buf[pos] = c;  // pos <= i: every lane read its entry before any lane writes
         m += __popcll(bm);
     }
@@ -1043,9 +1041,7 @@ __global__ __launch_bounds__(256) void flatip_topk_v4_finish(const Cand* __restr
         for (int e = 0; e < kFinishRegs; ++e) {
             const bool take = e * 64 + lane < total && (key[e] & pmask) >= prefix;
             const uint64_t bm = __ballot(take);
-            const int pos = m + static_cast<int>(__builtin_amdgcn_mbcnt_hi(
-                                    static_cast<uint32_t>(bm >> 32),
-                                    __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(bm), 0u)));
+            const int pos = m + ballot_rank(bm);
             if (take && pos < kFinishCap)
                 keep[pos] = Cand{v2::okey_inv(static_cast<uint32_t>(key[e] >> 32)), ~static_cast<uint32_t>(key[e])};
             m += __popcll(bm);
@@ -1075,9 +1071,7 @@ __global__ __launch_bounds__(256) void flatip_topk_v4_finish(const Cand* __restr
                 take = (ckey(c) & pmask) >= prefix;
             }
             const uint64_t bm = __ballot(take);
-            const int pos = m + static_cast<int>(__builtin_amdgcn_mbcnt_hi(
-                                    static_cast<uint32_t>(bm >> 32),
-                                    __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(bm), 0u)));
+            const int pos = m + ballot_rank(bm);
             if (take && pos < kFinishCap) keep[pos] = c;
             m += __popcll(bm);
         }

@@ -143,6 +143,29 @@ def l2_renorm_(x: torch.Tensor) -> torch.Tensor:
     return x
 
 
+def _exclude_words(exclude_bits: Optional[torch.Tensor], nq: int, contiguous: bool) -> int:
+    """Words per row of an exclusion bitmap int32/uint32 ``[nq, words]`` (None: 0);
+    ``contiguous``: the caller passes the tensor on as it is."""
+    if exclude_bits is None:
+        return 0
+    ok = exclude_bits.dtype in (torch.int32, torch.uint32) and exclude_bits.shape[0] == nq
+    if contiguous and not (ok and exclude_bits.is_contiguous()):
+        raise ValueError("exclude_bits must be contiguous int32/uint32 [nq, words]")
+    if not ok:
+        raise ValueError("exclude_bits must be int32/uint32 [nq, words]")
+    return exclude_bits.shape[1]
+
+
+def _topk_out(out: Optional[Tuple[torch.Tensor, torch.Tensor]], nq: int, k: int, device
+              ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The caller's ``out`` pair, or fresh (scores fp32, ids int64) ``[nq, k]``."""
+    if out is not None:
+        scores, ids = out
+        return scores, ids
+    return (torch.empty((nq, k), dtype=torch.float32, device=device),
+            torch.empty((nq, k), dtype=torch.int64, device=device))
+
+
 def flatip_topk(queries: torch.Tensor, items: torch.Tensor, k: int,
                 exclude_bits: Optional[torch.Tensor] = None, id_offset: int = 0,
                 out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
@@ -163,19 +186,12 @@ def flatip_topk(queries: torch.Tensor, items: torch.Tensor, k: int,
     nq, d = queries.shape
     nx = items.shape[0]
     dt = native.dtype_code(queries.dtype)
-    if out is None:
-        scores = torch.empty((nq, k), dtype=torch.float32, device=queries.device)
-        ids = torch.empty((nq, k), dtype=torch.int64, device=queries.device)
-    else:
-        scores, ids = out
+    scores, ids = _topk_out(out, nq, k, queries.device)
     if nq == 0:
         return scores, ids
-    words = 0
     if exclude_bits is not None:
         exclude_bits = exclude_bits.contiguous()
-        if exclude_bits.dtype not in (torch.int32, torch.uint32) or exclude_bits.shape[0] != nq:
-            raise ValueError("exclude_bits must be int32/uint32 [nq, words]")
-        words = exclude_bits.shape[1]
+    words = _exclude_words(exclude_bits, nq, False)
     nbytes = native.lib().rt_flatip_topk_workspace_bytes(nq, nx, d, dt, k)
     ws = workspace(queries.device, nbytes, "topk")
     with TIMER.region("flatip_topk", flops=2.0 * nq * nx * d,
@@ -234,19 +250,10 @@ def flatip_topk_online(queries: torch.Tensor, items: torch.Tensor, k: int,
     nq, d = queries.shape
     nx = items.shape[0]
     dt = native.dtype_code(queries.dtype)
-    if out is None:
-        scores = torch.empty((nq, k), dtype=torch.float32, device=queries.device)
-        ids = torch.empty((nq, k), dtype=torch.int64, device=queries.device)
-    else:
-        scores, ids = out
+    scores, ids = _topk_out(out, nq, k, queries.device)
     if nq == 0:
         return scores, ids
-    words = 0
-    if exclude_bits is not None:
-        if exclude_bits.dtype not in (torch.int32, torch.uint32) or exclude_bits.shape[0] != nq \
-                or not exclude_bits.is_contiguous():
-            raise ValueError("exclude_bits must be contiguous int32/uint32 [nq, words]")
-        words = exclude_bits.shape[1]
+    words = _exclude_words(exclude_bits, nq, True)
     ws = workspace_buf
     if ws is None:
         ws = workspace(queries.device, native.lib().rt_flatip_topk_online_workspace_bytes(nq, nx, d, dt, k),
@@ -317,9 +324,7 @@ def _flatip_topk_wide(queries, items, k, exclude_bits, id_offset, out):
     words = (nx + 31) // 32
     if exclude_bits is not None:
         exclude_bits = exclude_bits.contiguous()
-        if exclude_bits.dtype not in (torch.int32, torch.uint32) or exclude_bits.shape[0] != nq:
-            raise ValueError("exclude_bits must be int32/uint32 [nq, words]")
-        if exclude_bits.shape[1] < words:
+        if _exclude_words(exclude_bits, nq, False) < words:
             raise ValueError("exclude_bits has fewer words than ceil(n_items / 32)")
     parts_s, parts_i = [], []
     found = None  # [nq, m] local row ids returned so far (-1 = none)
@@ -423,8 +428,7 @@ def flatip_topk_shard_search(queries: torch.Tensor, items: torch.Tensor, k: int,
     if nbytes == 0:
         raise native.RTError("rt_flatip_topk_shard_search", -2, "no v4 plan for this shape")
     ws = workspace(queries.device, nbytes, "topk_shard")
-    scores = torch.empty((nq, k), dtype=torch.float32, device=queries.device)
-    ids = torch.empty((nq, k), dtype=torch.int64, device=queries.device)
+    scores, ids = _topk_out(None, nq, k, queries.device)
     with TIMER.region("flatip_topk", flops=2.0 * nq * items.shape[0] * d,
                       bytes_=float((nq + items.shape[0]) * d * queries.element_size() + nq * k * 12)):
         call("rt_flatip_topk_shard_search", ptr(queries), nq, ptr(items), items.shape[0], d, dt, k, ptr(thr),
@@ -470,8 +474,7 @@ def flatl2_topk(q_aug: torch.Tensor, x_aug: torch.Tensor, d: int, k: int,
     possible when more than 512 - k items tie within rounding of the k-th)."""
     nq, nx = q_aug.shape[0], x_aug.shape[0]
     k_sel = min(k + L2_MARGIN, 512)
-    s = torch.empty((nq, k), dtype=torch.float32, device=q_aug.device)
-    i = torch.empty((nq, k), dtype=torch.int64, device=q_aug.device)
+    s, i = _topk_out(None, nq, k, q_aug.device)
     if nq == 0:
         return s, i
     verify = verify and k_sel < nx  # a selection of the whole corpus is exact by construction
@@ -491,8 +494,7 @@ def flatl2_topk(q_aug: torch.Tensor, x_aug: torch.Tensor, d: int, k: int,
         if nb and k_sel < min(512, nx):
             qb = q_aug.index_select(0, bad).contiguous()
             bb = exclude_bits.index_select(0, bad).contiguous() if exclude_bits is not None else None
-            s2 = torch.empty((nb, k), dtype=torch.float32, device=q_aug.device)
-            i2 = torch.empty((nb, k), dtype=torch.int64, device=q_aug.device)
+            s2, i2 = _topk_out(None, nb, k, q_aug.device)
             k2 = min(512, nx)
             # a re-selection of the whole corpus is exact by construction: no certificate
             f2 = torch.empty(nb, dtype=torch.int32, device=q_aug.device) if k2 < nx else None
@@ -518,8 +520,7 @@ def topk_merge(scores: torch.Tensor, ids: torch.Tensor, k_out: int
     scores = scores.contiguous().float()
     ids = ids.contiguous().to(torch.int64)
     n_lists, nq, k_in = scores.shape
-    os_ = torch.empty((nq, k_out), dtype=torch.float32, device=scores.device)
-    oi = torch.empty((nq, k_out), dtype=torch.int64, device=scores.device)
+    os_, oi = _topk_out(None, nq, k_out, scores.device)
     call("rt_topk_merge", ptr(scores), ptr(ids), nq, n_lists, k_in, k_out, ptr(os_), ptr(oi),
          stream_of(scores))
     return os_, oi
@@ -581,17 +582,8 @@ def ivf_topk(queries: torch.Tensor, rows: torch.Tensor, list_offsets: torch.Tens
         raise ValueError(f"nprobe={nprobe}: 1..{IVF_MAX_NPROBE}")
     nlist = list_offsets.numel() - 1
     dt = native.dtype_code(queries.dtype)
-    if out is None:
-        scores = torch.empty((nq, k), dtype=torch.float32, device=queries.device)
-        ids = torch.empty((nq, k), dtype=torch.int64, device=queries.device)
-    else:
-        scores, ids = out
-    words = 0
-    if exclude_bits is not None:
-        if exclude_bits.dtype not in (torch.int32, torch.uint32) or exclude_bits.shape[0] != nq \
-                or not exclude_bits.is_contiguous():
-            raise ValueError("exclude_bits must be contiguous int32/uint32 [nq, words]")
-        words = exclude_bits.shape[1]
+    scores, ids = _topk_out(out, nq, k, queries.device)
+    words = _exclude_words(exclude_bits, nq, True)
     for a in range(0, nq, IVF_QUERY_CHUNK):
         b = min(nq, a + IVF_QUERY_CHUNK)
         ws = workspace_buf

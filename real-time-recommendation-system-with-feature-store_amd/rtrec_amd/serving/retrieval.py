@@ -90,7 +90,144 @@ def _default_device() -> torch.device:
     return torch.device("cuda", torch.cuda.current_device())
 
 
-class HipFlatIPIndex(IndexBase):
+class _HbmIndex(IndexBase):
+    """What the HBM-resident indexes share: the common config keys and their
+    validation, the device, the preparation of rows and queries, the id
+    bookkeeping and its ``.pkl`` payload, and — for the two single-GPU indexes —
+    the front of ``search``."""
+
+    # whether the resident searcher takes ``exclude`` lists (it reads them in its
+    # scan); otherwise a call with ``exclude_ids`` goes to the bitmap path
+    _searcher_takes_exclude = False
+
+    def __init__(self, config: Dict[str, Any]):
+        self.config = config
+        self.dimension = config.get("dimension", 128)
+        self.metric = config.get("metric", "cosine")
+        # retrieval.py:96-100: "cosine" → IndexFlatIP on normalised rows, any other
+        # metric → IndexFlatL2; "inner_product" (this build's extension) → raw IP
+        self._l2 = self.metric not in ("cosine", "inner_product")
+        self.storage_dtype = _STORAGE[config.get("storage_dtype", "float32")]
+        self._check_metric()
+        # what rt_flatip_topk serves (include/rtrec_hip.h): fail at construction,
+        # not at the first search
+        d_max = MAX_DIM - 4 if self._l2 else MAX_DIM
+        step = 4 if self.storage_dtype == torch.float32 else 8
+        if not (0 < self.dimension <= d_max) or self.dimension % step:
+            raise ValueError(f"dimension {self.dimension} unsupported: the MI355X index serves d % {step} == 0, "
+                             f"d <= {d_max}" + self._dimension_detail())
+        dev = config.get("device")
+        self.device = torch.device(dev) if dev is not None else None
+        self._reset_ids()
+        self.current_size = 0
+        self._generation = 0   # bumped by build / add / load / remove (OnlineSearcher validity)
+
+    def _check_metric(self):
+        """Raise for a metric (or a metric / storage pair) the class does not serve."""
+
+    def _dimension_detail(self) -> str:
+        """The class's own tail of the dimension error."""
+        return ""
+
+    def _init_online(self):
+        """The ``online_max_batch`` option of the indexes that hold a resident searcher."""
+        self.online_max_batch = int(self.config.get("online_max_batch", 0) or 0)
+        if not 0 <= self.online_max_batch <= OnlineSearcher.MAX_BATCH:
+            raise ValueError(f"online_max_batch={self.online_max_batch}: 0 (off) or 1..{OnlineSearcher.MAX_BATCH}")
+        self._online: Optional["OnlineSearcher"] = None
+
+    # -- device, rows ------------------------------------------------------
+    def _dev(self) -> torch.device:
+        if self.device is None:
+            self.device = _default_device()
+        return self.device
+
+    def _renorm_(self, t: torch.Tensor) -> torch.Tensor:
+        return kernels.l2_renorm_(t)
+
+    def _prepare(self, x: Array) -> torch.Tensor:
+        """Copy to a contiguous fp32 device tensor (the index owns its vectors,
+        retrieval.py:82) and renormalise in place for the cosine metric
+        (retrieval.py:86)."""
+        t = torch.as_tensor(x) if not isinstance(x, torch.Tensor) else x
+        if t.dim() == 1:
+            t = t.reshape(1, -1)
+        t = t.to(device=self._dev(), dtype=torch.float32, copy=True).contiguous()
+        if t.shape[1] != self.dimension:
+            raise ValueError(f"expected dimension {self.dimension}, got {t.shape[1]}")
+        if self.metric == "cosine" and t.shape[0]:
+            self._renorm_(t)
+        return t
+
+    def _searcher_lock(self):
+        """The resident searcher's lock when the index holds one: its replays read the rows."""
+        return self._online.lock if self._online is not None else contextlib.nullcontext()
+
+    # -- ids ---------------------------------------------------------------
+    def _reset_ids(self):
+        self.id_map: Dict[int, str] = {}
+        self.reverse_id_map: Dict[str, int] = {}
+        self._ids: List[Optional[str]] = []        # position -> id (vectorised id_map)
+
+    def _record_ids(self, start: int, ids: List[str], n_rows: int):
+        """Name the ``n_rows`` rows appended at position ``start``: both maps take
+        every id given, ``_ids`` one entry per row (None past the ids)."""
+        for i, item_id in enumerate(ids):
+            self.id_map[start + i] = item_id
+            self.reverse_id_map[item_id] = start + i
+        self._ids.extend(list(ids)[:n_rows] + [None] * max(0, n_rows - len(ids)))
+
+    def _save_ids(self, path: Path, **extra):
+        """``<path>.pkl``: the id maps, the size and the config (the reference's keys)."""
+        with open(path.with_suffix(".pkl"), "wb") as f:
+            pickle.dump({"id_map": self.id_map, "reverse_id_map": self.reverse_id_map,
+                         "current_size": self.current_size, "config": self.config, **extra}, f)
+
+    @staticmethod
+    def _read_pkl(path: Path) -> Dict[str, Any]:
+        with open(path.with_suffix(".pkl"), "rb") as f:
+            return pickle.load(f)  # files this package wrote (same layout as the reference's)
+
+    def _load_ids(self, data: Dict[str, Any], n: int):
+        """The id maps of a ``.pkl`` payload over ``n`` rows."""
+        self.id_map = data["id_map"]
+        self.reverse_id_map = data["reverse_id_map"]
+        self._ids = [self.id_map.get(i) for i in range(n)]
+
+    # -- search (the single-GPU indexes) -------------------------------------
+    def search(self, query_embeddings: Array, k: int = 10, filter_ids: Optional[List[str]] = None,
+               exclude_ids=None) -> Tuple[List[List[str]], List[List[float]]]:
+        """retrieval.py:141-197: normalise, top-k_search (2k when filtering), map
+        positions to ids, drop -1 padding, apply the filter, stop at k.
+
+        ``exclude_ids`` (the request schema's ``exclude_items``, src/api/schemas.py:
+        31-34): item ids that must not be returned — one list for every query, or
+        one list per query; unknown ids are ignored. Unlike ``filter_ids`` the
+        exclusion is applied IN the search and is exact: k results whenever k
+        eligible items exist, in every configuration (a resident searcher that
+        takes lists reads them in its scan; the other paths mask through a
+        bitmap). With ``filter_ids`` as well, the allow-list then applies to the
+        2k over-fetch."""
+        if self.index is None:
+            raise ValueError("Index not built yet")
+        k_search = min(k * 2, self.current_size) if filter_ids else k
+        nq = 1 if np.ndim(query_embeddings) == 1 else len(query_embeddings)
+        if k_search <= 0 or (self.mutable and self.current_size == 0):  # emptied by remove: nothing to scan
+            return [[] for _ in range(nq)], [[] for _ in range(nq)]
+        excl = None if exclude_ids is None else _exclude_positions(self.reverse_id_map, exclude_ids, nq)
+        if self.online_max_batch and not self._l2 and k_search <= OnlineSearcher.MAX_K \
+                and 1 <= nq <= self.online_max_batch and (excl is None or self._searcher_takes_exclude):
+            if self._online is None:
+                self._online = self.online_searcher(self.online_max_batch)
+            with self._online.lock:  # the returned buffers are the searcher's: read them under its lock
+                scores, pos = self._online.search(query_embeddings, k_search, exclude=excl)
+                return _lists_from_positions(scores, pos, self.id_map, k, filter_ids)
+        bits = None if excl is None else kernels.exclusion_bitmap(nq, self.current_size, excl, self._dev())
+        scores, pos = self.search_tensors(query_embeddings, k_search, exclude_bits=bits)
+        return _lists_from_positions(scores.cpu().numpy(), pos.cpu().numpy(), self.id_map, k, filter_ids)
+
+
+class HipFlatIPIndex(_HbmIndex):
     """Exact inner-product index resident in HBM (FaissIndex ``Flat`` semantics).
 
     Config keys (retrieval.py:58-63): ``dimension`` (128), ``metric``
@@ -128,64 +265,30 @@ class HipFlatIPIndex(IndexBase):
     lower-position-wins tie rule). Every metric and storage dtype.
     """
 
+    _searcher_takes_exclude = True   # OnlineSearcher: rt_flatip_topk_online_lists
+
     def __init__(self, config: Optional[Dict[str, Any]] = None):
-        self.config = config or {}
-        self.dimension = self.config.get("dimension", 128)
+        super().__init__(config or {})
         self.index_factory = self.config.get("index_factory", "Flat")
-        self.metric = self.config.get("metric", "cosine")
         self.nprobe = self.config.get("nprobe", 20)
-        self.storage_dtype = _STORAGE[self.config.get("storage_dtype", "float32")]
-        # retrieval.py:96-100: "cosine" → IndexFlatIP on normalised rows, any other
-        # metric → IndexFlatL2; "inner_product" (this build's extension) → raw IP
-        self._l2 = self.metric not in ("cosine", "inner_product")
-        if self._l2 and self.storage_dtype != torch.float32:
-            raise ValueError("the L2 metric (IndexFlatL2) stores float32 rows, like Faiss")
-        # what rt_flatip_topk serves (include/rtrec_hip.h): fail at construction,
-        # not at the first search
-        d_max = MAX_DIM - 4 if self._l2 else MAX_DIM
-        step = 4 if self.storage_dtype == torch.float32 else 8
-        if not (0 < self.dimension <= d_max) or self.dimension % step:
-            raise ValueError(f"dimension {self.dimension} unsupported: the MI355X index serves d % {step} == 0, "
-                             f"d <= {d_max} for {self.metric!r} / {self.config.get('storage_dtype', 'float32')}")
-        dev = self.config.get("device")
-        self.device = torch.device(dev) if dev is not None else None
         self.index: Optional[torch.Tensor] = None   # [capacity, d] device rows; first current_size valid
-        self.id_map: Dict[int, str] = {}
-        self.reverse_id_map: Dict[str, int] = {}
-        self._ids: List[str] = []                  # position -> id (vectorised id_map)
-        self.current_size = 0
-        self._generation = 0                       # bumped by build / add / load / remove (OnlineSearcher validity)
         self.mutable = bool(self.config.get("mutable", False))
-        self.online_max_batch = int(self.config.get("online_max_batch", 0) or 0)
-        if not 0 <= self.online_max_batch <= OnlineSearcher.MAX_BATCH:
-            raise ValueError(f"online_max_batch={self.online_max_batch}: 0 (off) or 1..{OnlineSearcher.MAX_BATCH}")
+        self._init_online()
         if self.online_max_batch and self._l2:
             raise ValueError("online_max_batch serves the inner-product metrics ('cosine', 'inner_product'); "
                              "the L2 metric keeps the default search path")
-        self._online: Optional["OnlineSearcher"] = None
         if "IVF" in str(self.index_factory):
             logger.warning("index_factory %s: the MI355X index serves every factory exactly (Flat)",
                            self.index_factory)
 
+    def _check_metric(self):
+        if self._l2 and self.storage_dtype != torch.float32:
+            raise ValueError("the L2 metric (IndexFlatL2) stores float32 rows, like Faiss")
+
+    def _dimension_detail(self) -> str:
+        return f" for {self.metric!r} / {self.config.get('storage_dtype', 'float32')}"
+
     # -- helpers -----------------------------------------------------------
-    def _dev(self) -> torch.device:
-        if self.device is None:
-            self.device = _default_device()
-        return self.device
-
-    def _prepare(self, x: Array) -> torch.Tensor:
-        """Copy to a contiguous fp32 device tensor (the index owns its vectors,
-        retrieval.py:82) and renormalise in place for the cosine metric."""
-        t = torch.as_tensor(x) if not isinstance(x, torch.Tensor) else x
-        if t.dim() == 1:
-            t = t.reshape(1, -1)
-        t = t.to(device=self._dev(), dtype=torch.float32, copy=True).contiguous()
-        if t.shape[1] != self.dimension:
-            raise ValueError(f"expected dimension {self.dimension}, got {t.shape[1]}")
-        if self.metric == "cosine":
-            kernels.l2_renorm_(t)
-        return t
-
     def _row_width(self) -> int:
         """Stored row width: d, or d + 4 augmented columns in the L2 mode
         ([x, -||x||^2/2, 0, 0, 0], rt_l2_augment_f32)."""
@@ -220,12 +323,9 @@ class HipFlatIPIndex(IndexBase):
         rows = self._prepare(embeddings)
         self.index = None
         self.current_size = 0
-        self.id_map, self.reverse_id_map, self._ids = {}, {}, []
+        self._reset_ids()
         self._store(rows)
-        for i, item_id in enumerate(ids):
-            self.id_map[i] = item_id
-            self.reverse_id_map[item_id] = i
-        self._ids = list(ids) + [None] * max(0, rows.shape[0] - len(ids))
+        self._record_ids(0, ids, max(rows.shape[0], len(ids)))   # ids past the rows stay in _ids
         self.current_size = rows.shape[0]
         self._generation += 1
         self._online = None  # sized for the index as it was; the next small call makes a new one
@@ -253,36 +353,6 @@ class HipFlatIPIndex(IndexBase):
                                        exclude_bits=exclude_bits)
         return kernels.flatip_topk(q, self.index[: self.current_size], k, exclude_bits=exclude_bits)
 
-    def search(self, query_embeddings: Array, k: int = 10, filter_ids: Optional[List[str]] = None,
-               exclude_ids=None) -> Tuple[List[List[str]], List[List[float]]]:
-        """retrieval.py:141-197: normalise, top-k_search (2k when filtering), map
-        positions to ids, drop -1 padding, apply the filter, stop at k.
-
-        ``exclude_ids`` (the request schema's ``exclude_items``, src/api/schemas.py:
-        31-34): item ids that must not be returned — one list for every query, or
-        one list per query; unknown ids are ignored. Unlike ``filter_ids`` the
-        exclusion is applied IN the search and is exact: k results whenever k
-        eligible items exist, in every configuration (the online searcher reads
-        the lists in its scan; the other paths mask through a bitmap). With
-        ``filter_ids`` as well, the allow-list then applies to the 2k over-fetch."""
-        if self.index is None:
-            raise ValueError("Index not built yet")
-        k_search = min(k * 2, self.current_size) if filter_ids else k
-        nq = 1 if np.ndim(query_embeddings) == 1 else len(query_embeddings)
-        if k_search <= 0 or (self.mutable and self.current_size == 0):  # emptied by remove: nothing to scan
-            return [[] for _ in range(nq)], [[] for _ in range(nq)]
-        excl = None if exclude_ids is None else _exclude_positions(self.reverse_id_map, exclude_ids, nq)
-        if self.online_max_batch and not self._l2 and k_search <= OnlineSearcher.MAX_K:
-            if 1 <= nq <= self.online_max_batch:
-                if self._online is None:
-                    self._online = self.online_searcher(self.online_max_batch)
-                with self._online.lock:  # the returned buffers are the searcher's: read them under its lock
-                    scores, pos = self._online.search(query_embeddings, k_search, exclude=excl)
-                    return _lists_from_positions(scores, pos, self.id_map, k, filter_ids)
-        bits = None if excl is None else kernels.exclusion_bitmap(nq, self.current_size, excl, self._dev())
-        scores, pos = self.search_tensors(query_embeddings, k_search, exclude_bits=bits)
-        return _lists_from_positions(scores.cpu().numpy(), pos.cpu().numpy(), self.id_map, k, filter_ids)
-
     def add(self, embeddings: Array, ids: List[str]):
         """retrieval.py:199-226: incremental append (Kafka item_update path)."""
         if self.index is None:
@@ -292,18 +362,10 @@ class HipFlatIPIndex(IndexBase):
     def _append(self, rows: torch.Tensor, ids: List[str]):
         """Append prepared rows and their ids (``add``; the unknown ids of ``update``)."""
         self._store(rows)
-        for i, item_id in enumerate(ids):
-            new_idx = self.current_size + i
-            self.id_map[new_idx] = item_id
-            self.reverse_id_map[item_id] = new_idx
-        self._ids.extend(list(ids) + [None] * max(0, rows.shape[0] - len(ids)))
+        self._record_ids(self.current_size, ids, max(rows.shape[0], len(ids)))
         self.current_size += rows.shape[0]
         self._generation += 1
         logger.info("Added %d items to index. Total size: %d", rows.shape[0], self.current_size)
-
-    def _searcher_lock(self):
-        """The resident searcher's lock when the index holds one: its replays read the rows."""
-        return self._online.lock if self._online is not None else contextlib.nullcontext()
 
     def update(self, embeddings: Array, ids: List[str]):
         """retrieval.py:228-237: a no-op with a warning, like the reference, unless
@@ -401,19 +463,14 @@ class HipFlatIPIndex(IndexBase):
         path = Path(path)
         path.parent.mkdir(parents=True, exist_ok=True)
         write_flat_index(path.with_suffix(".faiss"), self.vectors(), not self._l2)
-        with open(path.with_suffix(".pkl"), "wb") as f:
-            pickle.dump({"id_map": self.id_map, "reverse_id_map": self.reverse_id_map,
-                         "current_size": self.current_size, "config": self.config}, f)
+        self._save_ids(path)
         logger.info("Saved index to %s", path)
 
     def load(self, path: str):
         """retrieval.py:275-299."""
         path = Path(path)
         vecs, _ip = read_flat_index(path.with_suffix(".faiss"))
-        with open(path.with_suffix(".pkl"), "rb") as f:
-            data = pickle.load(f)  # files this index wrote (same layout as the reference's)
-        self.id_map = data["id_map"]
-        self.reverse_id_map = data["reverse_id_map"]
+        data = self._read_pkl(path)
         self.config = data.get("config", self.config)
         self.metric = self.config.get("metric", self.metric)
         self._l2 = self.metric not in ("cosine", "inner_product")
@@ -423,7 +480,7 @@ class HipFlatIPIndex(IndexBase):
         self.current_size = 0
         self._store(torch.from_numpy(vecs).to(self._dev()))
         self.current_size = int(data["current_size"])
-        self._ids = [self.id_map.get(i) for i in range(self.current_size)]
+        self._load_ids(data, self.current_size)
         self._generation += 1
         self._online = None  # load may change the dimension and the metric
         logger.info("Loaded index from %s with %d items", path, self.current_size)
@@ -701,7 +758,7 @@ class OnlineSearcher:
             return self._h_s_np[:nq * k].reshape(nq, k), self._h_p_np[:nq * k].reshape(nq, k)
 
 
-class HipShardedFlatIPIndex(IndexBase):
+class HipShardedFlatIPIndex(_HbmIndex):
     """The same ``IndexBase`` contract as :class:`HipFlatIPIndex` (FaissIndex
     ``Flat``, retrieval.py:49-329) over a corpus ROW-SHARDED across the ranks
     of a process group, one shard in each GPU's HBM.
@@ -749,37 +806,23 @@ class HipShardedFlatIPIndex(IndexBase):
     MAX_K = 512  # rt_topk_merge: k_out <= 512
 
     def __init__(self, config: Optional[Dict[str, Any]] = None):
-        self.config = dict(config or {})
-        self.dimension = self.config.get("dimension", 128)
+        super().__init__(dict(config or {}))
         self.index_factory = self.config.get("index_factory", "Flat")
-        self.metric = self.config.get("metric", "cosine")
         self.nprobe = self.config.get("nprobe", 20)
-        if self.metric not in ("cosine", "inner_product"):
-            raise ValueError("the sharded index serves the inner-product metrics ('cosine', 'inner_product'); "
-                             "IndexFlatL2 is the single-GPU HipFlatIPIndex")
-        self.storage_dtype = _STORAGE[self.config.get("storage_dtype", "float32")]
-        step = 4 if self.storage_dtype == torch.float32 else 8
-        if not (0 < self.dimension <= MAX_DIM) or self.dimension % step:
-            raise ValueError(f"dimension {self.dimension} unsupported: the MI355X index serves d % {step} == 0, "
-                             f"d <= {MAX_DIM}")
         self.group = self.config.pop("process_group", None)
         self.query_tile = int(self.config.get("query_tile", 65536))
-        dev = self.config.get("device")
-        self.device = torch.device(dev) if dev is not None else None
         from ..dist import sharded as _sh
         self._sh = _sh
         self.world, self.rank = _sh._world(self.group)
         self._reset()
 
-    # -- hooks (the CPU orchestration tests substitute these) ---------------
-    def _dev(self) -> torch.device:
-        if self.device is None:
-            self.device = _default_device()
-        return self.device
+    def _check_metric(self):
+        if self._l2:
+            raise ValueError("the sharded index serves the inner-product metrics ('cosine', 'inner_product'); "
+                             "IndexFlatL2 is the single-GPU HipFlatIPIndex")
 
-    def _renorm_(self, t: torch.Tensor) -> torch.Tensor:
-        return kernels.l2_renorm_(t)
-
+    # -- hooks (the CPU orchestration tests substitute these, and the base's _dev
+    # and _renorm_) -----------------------------------------------------------
     def _ops(self, rows: torch.Tensor):
         return self._sh.ShardOps(rows, self.begin, self.gpos)
 
@@ -793,24 +836,9 @@ class HipShardedFlatIPIndex(IndexBase):
         self.begin = 0                             # global position of local row 0 (contiguous shard)
         self.gpos: Optional[torch.Tensor] = None   # int64 [n_local] global positions once non-contiguous
         self.shard_sizes: List[int] = [0] * self.world
-        self.id_map: Dict[int, str] = {}
-        self.reverse_id_map: Dict[str, int] = {}
-        self._ids: List[Optional[str]] = []
+        self._reset_ids()
         self._implicit_ids = False                 # build_shard without ids: id = str(position)
         self.current_size = 0
-
-    def _prepare(self, x: Array) -> torch.Tensor:
-        """Contiguous fp32 device copy (the index owns its vectors), Faiss
-        renorm for the cosine metric (retrieval.py:82-86)."""
-        t = torch.as_tensor(x) if not isinstance(x, torch.Tensor) else x
-        if t.dim() == 1:
-            t = t.reshape(1, -1)
-        t = t.to(device=self._dev(), dtype=torch.float32, copy=True).contiguous()
-        if t.shape[1] != self.dimension:
-            raise ValueError(f"expected dimension {self.dimension}, got {t.shape[1]}")
-        if self.metric == "cosine" and t.shape[0]:
-            self._renorm_(t)
-        return t
 
     def _append_local(self, rows: torch.Tensor, positions: Optional[torch.Tensor]):
         """Append prepared rows (their global positions: ``positions``, or the
@@ -831,12 +859,6 @@ class HipShardedFlatIPIndex(IndexBase):
             self.gpos = torch.cat([self.gpos, positions.to(device=self._dev(), dtype=torch.int64)])
         self.n_local = n_new
 
-    def _set_ids(self, start: int, ids: List[str], n_rows: int):
-        for i, item_id in enumerate(ids):
-            self.id_map[start + i] = item_id
-            self.reverse_id_map[item_id] = start + i
-        self._ids.extend(list(ids)[:n_rows] + [None] * max(0, n_rows - len(ids)))
-
     # -- IndexBase -------------------------------------------------------------
     def build(self, embeddings: Array, ids: List[str]):
         """retrieval.py:70-139 (Flat): every rank passes the whole corpus and
@@ -848,7 +870,7 @@ class HipShardedFlatIPIndex(IndexBase):
         self.begin = b
         self._append_local(self._prepare(embeddings[b:b + c]), None)
         self.shard_sizes = [self._sh.shard_range(n, self.world, r)[1] for r in range(self.world)]
-        self._set_ids(0, ids, n)
+        self._record_ids(0, ids, n)
         self.current_size = n
         logger.info("Sharded index built in %.2f seconds (%d of %d rows on rank %d)", time.time() - start, c, n,
                     self.rank)
@@ -872,14 +894,14 @@ class HipShardedFlatIPIndex(IndexBase):
         if ids is None:  # string ids = positions, materialised only when needed (add / save / load)
             self._implicit_ids = True
         else:
-            self._set_ids(0, ids, n_total)
+            self._record_ids(0, ids, n_total)
         self.current_size = int(n_total)
         return self
 
     def _materialize_ids(self):
         if self._implicit_ids:
             self._implicit_ids = False
-            self._set_ids(0, [str(i) for i in range(self.current_size)], self.current_size)
+            self._record_ids(0, [str(i) for i in range(self.current_size)], self.current_size)
 
     def add(self, embeddings: Array, ids: List[str]):
         """retrieval.py:199-226: every rank passes the whole batch; the new
@@ -893,7 +915,7 @@ class HipShardedFlatIPIndex(IndexBase):
         pos = torch.arange(self.current_size + b, self.current_size + b + c, dtype=torch.int64)
         self._append_local(self._prepare(embeddings[b:b + c]), pos)
         self.shard_sizes = [s + self._sh.shard_range(m, self.world, r)[1] for r, s in enumerate(self.shard_sizes)]
-        self._set_ids(self.current_size, ids, m)
+        self._record_ids(self.current_size, ids, m)
         self.current_size += m
         logger.info("Added %d items to index. Total size: %d", m, self.current_size)
 
@@ -991,10 +1013,7 @@ class HipShardedFlatIPIndex(IndexBase):
         with open(fp, "wb") as f:
             np.save(f, self.positions(), allow_pickle=False)
         if self.rank == 0:
-            with open(path.with_suffix(".pkl"), "wb") as f:
-                pickle.dump({"id_map": self.id_map, "reverse_id_map": self.reverse_id_map,
-                             "current_size": self.current_size, "config": self.config,
-                             "world": self.world, "shard_sizes": self.shard_sizes}, f)
+            self._save_ids(path, world=self.world, shard_sizes=self.shard_sizes)
         self._barrier()
         logger.info("Saved shard %d of %d to %s", self.rank, self.world, fx)
 
@@ -1003,8 +1022,7 @@ class HipShardedFlatIPIndex(IndexBase):
         another world size, or a single-GPU save (``<path>.faiss``): the rows
         are re-sharded by global position."""
         path = Path(path)
-        with open(path.with_suffix(".pkl"), "rb") as f:
-            data = pickle.load(f)  # files this package wrote
+        data = self._read_pkl(path)
         n = int(data["current_size"])
         saved_world = data.get("world")
         self._reset()
@@ -1033,9 +1051,7 @@ class HipShardedFlatIPIndex(IndexBase):
         self.begin = int(pos[0]) if pos.size else int(sum(self.shard_sizes[:self.rank]))
         self._append_local(torch.from_numpy(vecs).to(self._dev()),  # stored rows: no second renorm
                            None if contiguous else torch.from_numpy(pos))
-        self.id_map = data["id_map"]
-        self.reverse_id_map = data["reverse_id_map"]
-        self._ids = [self.id_map.get(i) for i in range(n)]
+        self._load_ids(data, n)
         self.current_size = n
         logger.info("Loaded shard %d of %d from %s (%d of %d rows)", self.rank, self.world, path, self.n_local, n)
 
@@ -1123,7 +1139,7 @@ def _parse_ivf_factory(factory: str) -> int:
     return int(head[3:])
 
 
-class HipIVFFlatIndex(IndexBase):
+class HipIVFFlatIndex(_HbmIndex):
     """IVF-Flat index resident in HBM: the reference's DEFAULT configuration,
     ``faiss.index_factory(d, "IVF1024,Flat")`` searched with ``nprobe = 20``
     (retrieval.py:60-62, 101-133). k-means lists over the corpus, a coarse
@@ -1164,33 +1180,18 @@ class HipIVFFlatIndex(IndexBase):
     """
 
     def __init__(self, config: Optional[Dict[str, Any]] = None):
-        self.config = dict(config or {})
-        self.dimension = self.config.get("dimension", 128)
-        self.metric = self.config.get("metric", "cosine")
-        if self.metric not in ("cosine", "inner_product"):
-            raise ValueError(f"metric {self.metric!r}: HipIVFFlatIndex serves 'cosine' and 'inner_product'; "
-                             "the L2 metric (IndexFlatL2) is HipFlatIPIndex")
+        super().__init__(dict(config or {}))
         if self.config.get("mutable", False):
             raise ValueError("HipIVFFlatIndex is not mutable: in-place list mutation is not built "
                              "(HipFlatIPIndex takes mutable=True)")
+        self.mutable = False
         self.index_factory = self.config.get("index_factory", _IVF_FACTORY)
         self.nlist = _parse_ivf_factory(self.index_factory)
         self.nprobe = int(self.config.get("nprobe", 20))
-        self.storage_dtype = _STORAGE[self.config.get("storage_dtype", "float32")]
-        step = 4 if self.storage_dtype == torch.float32 else 8
-        if not (0 < self.dimension <= MAX_DIM) or self.dimension % step:
-            raise ValueError(f"dimension {self.dimension} unsupported: the MI355X index serves d % {step} == 0, "
-                             f"d <= {MAX_DIM}")
         self.train_iters = int(self.config.get("train_iters", 10))
         self.max_points_per_centroid = int(self.config.get("max_points_per_centroid", 256))
         self.seed = int(self.config.get("seed", 1234))
-        self.online_max_batch = int(self.config.get("online_max_batch", 0) or 0)
-        if not 0 <= self.online_max_batch <= OnlineSearcher.MAX_BATCH:
-            raise ValueError(f"online_max_batch={self.online_max_batch}: 0 (off) or 1..{OnlineSearcher.MAX_BATCH}")
-        dev = self.config.get("device")
-        self.device = torch.device(dev) if dev is not None else None
-        self._l2 = False
-        self.mutable = False
+        self._init_online()
         self._flat: Optional[HipFlatIPIndex] = None   # the Flat fallback of a small corpus
         self.index: Optional[torch.Tensor] = None     # [n, d] storage dtype, list-contiguous
         self.centroids: Optional[torch.Tensor] = None     # [nlist, d] fp32
@@ -1198,17 +1199,13 @@ class HipIVFFlatIndex(IndexBase):
         self.row_pos: Optional[torch.Tensor] = None       # [n] int32: original position of a stored row
         self.assign: Optional[torch.Tensor] = None        # [n] int64: list of an original position
         self.max_list_rows = 0
-        self.id_map: Dict[int, str] = {}
-        self.reverse_id_map: Dict[str, int] = {}
-        self._ids: List[str] = []
-        self.current_size = 0
-        self._generation = 0
-        self._online: Optional["OnlineSearcher"] = None
+
+    def _check_metric(self):
+        if self._l2:
+            raise ValueError(f"metric {self.metric!r}: HipIVFFlatIndex serves 'cosine' and 'inner_product'; "
+                             "the L2 metric (IndexFlatL2) is HipFlatIPIndex")
 
     # -- helpers -----------------------------------------------------------
-    _dev = HipFlatIPIndex._dev
-    _prepare = HipFlatIPIndex._prepare
-
     def _flat_config(self) -> Dict[str, Any]:
         cfg = {k: v for k, v in self.config.items()
                if k in ("dimension", "metric", "storage_dtype", "device", "online_max_batch")}
@@ -1263,13 +1260,6 @@ class HipIVFFlatIndex(IndexBase):
         self.max_list_rows = int(counts.max().item()) if assign.numel() else 0
         self.current_size = int(assign.numel())
 
-    def _set_ids(self, ids: List[str], n: int):
-        self.id_map, self.reverse_id_map = {}, {}
-        for i, item_id in enumerate(ids):
-            self.id_map[i] = item_id
-            self.reverse_id_map[item_id] = i
-        self._ids = list(ids) + [None] * max(0, n - len(ids))
-
     def _sync_flat(self):
         """Mirror the inner Flat index's public state (the fallback of a small corpus)."""
         f = self._flat
@@ -1297,7 +1287,8 @@ class HipIVFFlatIndex(IndexBase):
         self.centroids = self._train(rows)
         assign = self._assign_rows(rows, self.centroids)
         self._regroup(rows.to(self.storage_dtype), None, assign)
-        self._set_ids(ids, n)
+        self._reset_ids()
+        self._record_ids(0, ids, max(n, len(ids)))   # ids past the rows stay in _ids, as in the Flat index
         self._generation += 1
         logger.info("Index built in %.2f seconds", time.time() - start)
 
@@ -1339,28 +1330,11 @@ class HipIVFFlatIndex(IndexBase):
                exclude_ids=None) -> Tuple[List[List[str]], List[List[float]]]:
         """retrieval.py:141-197, as :meth:`HipFlatIPIndex.search`: the 2k over-fetch
         for ``filter_ids``, exact ``exclude_ids`` in the search (over the probed
-        lists). A call with ``exclude_ids`` takes the bitmap path."""
-        if self.index is None:
-            raise ValueError("Index not built yet")
-        if self._flat is not None:
+        lists). A call with ``exclude_ids`` takes the bitmap path: the probed-list
+        scan does not read lists (``_searcher_takes_exclude``)."""
+        if self.index is not None and self._flat is not None:
             return self._flat.search(query_embeddings, k, filter_ids, exclude_ids=exclude_ids)
-        k_search = min(k * 2, self.current_size) if filter_ids else k
-        nq = 1 if np.ndim(query_embeddings) == 1 else len(query_embeddings)
-        if k_search <= 0:
-            return [[] for _ in range(nq)], [[] for _ in range(nq)]
-        if exclude_ids is None and self.online_max_batch and k_search <= OnlineSearcher.MAX_K \
-                and 1 <= nq <= self.online_max_batch:
-            if self._online is None:
-                self._online = self.online_searcher(self.online_max_batch)
-            with self._online.lock:
-                scores, pos = self._online.search(query_embeddings, k_search)
-                return _lists_from_positions(scores, pos, self.id_map, k, filter_ids)
-        bits = None
-        if exclude_ids is not None:
-            excl = _exclude_positions(self.reverse_id_map, exclude_ids, nq)
-            bits = kernels.exclusion_bitmap(nq, self.current_size, excl, self._dev())
-        scores, pos = self.search_tensors(query_embeddings, k_search, exclude_bits=bits)
-        return _lists_from_positions(scores.cpu().numpy(), pos.cpu().numpy(), self.id_map, k, filter_ids)
+        return super().search(query_embeddings, k, filter_ids, exclude_ids=exclude_ids)
 
     def add(self, embeddings: Array, ids: List[str]):
         """retrieval.py:199-226. The new rows are assigned to the existing centroids
@@ -1381,12 +1355,9 @@ class HipIVFFlatIndex(IndexBase):
         src_index = torch.cat([inv, torch.arange(n_old, n_old + m, dtype=torch.int64, device=dev)])
         assign = torch.cat([self.assign, self._assign_rows(rows, self.centroids)])
         src = torch.cat([self.index, rows.to(self.storage_dtype)])
-        with (self._online.lock if self._online is not None else contextlib.nullcontext()):
+        with self._searcher_lock():
             self._regroup(src, src_index, assign)
-            for i, item_id in enumerate(ids):
-                self.id_map[n_old + i] = item_id
-                self.reverse_id_map[item_id] = n_old + i
-            self._ids.extend(list(ids) + [None] * max(0, m - len(ids)))
+            self._record_ids(n_old, ids, max(m, len(ids)))
             self._generation += 1
         logger.info("Added %d items to index. Total size: %d", m, self.current_size)
 
@@ -1424,9 +1395,7 @@ class HipIVFFlatIndex(IndexBase):
             return
         path.parent.mkdir(parents=True, exist_ok=True)
         write_flat_index(path.with_suffix(".faiss"), self.vectors(), True)
-        with open(path.with_suffix(".pkl"), "wb") as f:
-            pickle.dump({"id_map": self.id_map, "reverse_id_map": self.reverse_id_map,
-                         "current_size": self.current_size, "config": self.config}, f)
+        self._save_ids(path)
         cfg = {k: v for k, v in self.config.items() if isinstance(v, (str, int, float, bool, type(None)))}
         np.savez(path.with_suffix(".ivf.npz"), centroids=self.centroids.cpu().numpy(),
                  assign=self.assign.cpu().numpy(), config=np.array(json.dumps(cfg)), seed=np.int64(self.seed),
@@ -1447,13 +1416,11 @@ class HipIVFFlatIndex(IndexBase):
             self._sync_flat()
             return
         vecs, _ip = read_flat_index(path.with_suffix(".faiss"))
-        with open(path.with_suffix(".pkl"), "rb") as f:
-            data = pickle.load(f)  # files this index wrote
+        data = self._read_pkl(path)
         with np.load(ivf) as z:
             centroids, assign = z["centroids"], z["assign"]
             self.seed, self.nlist = int(z["seed"]), int(z["nlist"])
         self._flat = None
-        self.id_map, self.reverse_id_map = data["id_map"], data["reverse_id_map"]
         self.config = dict(data.get("config", self.config))
         self.metric = self.config.get("metric", self.metric)
         self.dimension = vecs.shape[1]
@@ -1461,7 +1428,7 @@ class HipIVFFlatIndex(IndexBase):
         dev = self._dev()
         self.centroids = torch.from_numpy(centroids).to(dev)
         self._regroup(torch.from_numpy(vecs).to(dev).to(self.storage_dtype), None, torch.from_numpy(assign).to(dev))
-        self._ids = [self.id_map.get(i) for i in range(self.current_size)]
+        self._load_ids(data, self.current_size)
         self._generation += 1
         logger.info("Loaded index from %s with %d items", path, self.current_size)
 
