@@ -494,9 +494,30 @@ typedef struct {
     uint16_t* next_w_planes;      /* [3][next_n][next_k] */
     int next_n;
     int next_k;
+    /* Fragment-ordered weight images: the fp32 values of a weight in the order the
+     * lanes of the MFMA k-loops read them, so a wave's W load covers whole 128-byte lines. Written
+     * once per step by a side task, read by every row block; values and MFMA order are those of
+     * the loads from w / wt, so results are bit-identical. Sizes: rt_linear_w_frag_bytes. */
+    const float* w_frag;          /* optional float4 [T][S][4][64] image of THIS launch's w (k % 8 == 0,
+                                     n <= 256, 16-B aligned; T = ceil(n/32), S = ceil(k/32)): entry
+                                     (t, s, j, l) with c = l & 31, h = l >> 5 holds
+                                     w[32t + c][32s + 16(j>>1) + 8h + 4(j&1) + 0..3], zeros past n / k.
+                                     NULL = the loads from w. Used when every argument set of the
+                                     launch brings one */
+    float* next_w_frag;           /* optional side task: that image of next_w [next_n][next_k]
+                                     (next_k % 8 == 0, 16-B aligned) */
+    float* wt_frag_out;           /* optional side task (n % 8 == 0, 16-B aligned): the dz image of Wᵀ,
+                                     float4 [KT][NS][2][64], KT = ceil(k/32), NS = ceil(n/32)·2: entry
+                                     (kt, sb, j, l) holds Wᵀ[32kt + c][16sb + 8h + 4j + 0..3], zeros past
+                                     k / n; read by the backward's dz launch as rt_linear_bwd_args.wt_frag */
 } rt_linear_fwd_args;
 
 int rt_linear_fwd_f32(const rt_linear_fwd_args* args, void* stream);
+/* Bytes of a fragment-ordered image of a Linear W [n][k]: transposed == 0 the forward image
+ * (rt_linear_fwd_args.w_frag; 0 when k % 8 != 0 or n > 256), else the dz image
+ * (rt_linear_bwd_args.wt_frag; 0 when n % 8 != 0 or k > 256). Rows and columns are padded to
+ * whole 32-wide tiles: 32·ceil(n/32) · 32·ceil(k/32) · 4. Host-only, no GPU work. */
+size_t rt_linear_w_frag_bytes(int n, int k, int transposed);
 
 /* Backward of one Linear and of the block that produced its output gradient.
  *   grad_mode 0: dz = normalize_bwd(dout; l2_out, norms)            (final layer)
@@ -576,6 +597,10 @@ typedef struct {
     const uint16_t* wt_planes; /* optional [3][k][n] split pieces of Wᵀ (rt_linear_fwd_args.wt_planes_out
                                   of THIS step; n % 8 == 0, 16-B aligned): dA = dz·W reads them instead
                                   of splitting wt / w in registers (bit-identical) */
+    const float* wt_frag;      /* optional dz image of Wᵀ (rt_linear_fwd_args.wt_frag_out of THIS step;
+                                  n % 8 == 0, k <= 256, 16-B aligned): dA = dz·W reads its W fragments
+                                  from it in whole lines (bit-identical). Used when every argument set
+                                  of the launch that has a dA brings one; otherwise wt, else w */
 } rt_linear_bwd_args;
 
 int rt_linear_bwd_f32(const rt_linear_bwd_args* args, void* stream);

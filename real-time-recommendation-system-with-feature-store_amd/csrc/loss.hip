@@ -9,7 +9,8 @@
 // (src/training/trainers/two_tower.py:111-137), forward AND backward.
 //
 // Block geometry of the in-batch part: a FIXED tile of 32 rows (users, or items
-// in the column pass) whose fragments sit in registers, and a STREAMED span of
+// in the column pass) whose fragments sit in registers (the block loads the tile
+// once, coalesced, and hands it to its waves through LDS), and a STREAMED span of
 // 256 rows: each wave stages 32-row tiles through its own LDS slice (all loads
 // of a tile in flight at once; a wave with two tiles prefetches the second into
 // registers while the first is on the MFMAs).
@@ -126,6 +127,52 @@ __device__ __forceinline__ void load_fixed3(const T* __restrict__ F, int64_t f0,
         pf[kb] = split8(x);
     }
 }
+// The block's fixed 32 x DP tile through LDS (every wave of a block uses the
+// same tile): the NW waves load it once, each 32 / NW of its rows, coalesced
+// (whole 128-byte lines; rows >= n and columns >= D as zeros, 16-bit types
+// widened as load4 widens them), instead of every wave issuing load_fixed3's
+// fragment-shaped loads (32 rows x 32 bytes per instruction). After a block
+// barrier fixed_from_lds gives each wave the pieces load_fixed3 gives: the same
+// fp32 values, split the same way. -DRT_LOSS_FIXED_DIRECT keeps load_fixed3 (A/B).
+template <int DP, int NW>
+constexpr int fixed_per_thread() { return (32 * DP / 4 + 64 * NW - 1) / (64 * NW); }
+// (load and store apart: the caller's other global reads go out between them)
+template <int DP, typename T, int NW>
+__device__ __forceinline__ void fixed_load(const T* __restrict__ F, int64_t f0, int64_t n, int D,
+                                           float4 (&v)[fixed_per_thread<DP, NW>()]) {
+    constexpr int TOT = 32 * DP / 4;
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int u = 0; u < fixed_per_thread<DP, NW>(); ++u) {
+        const int e = tid + 64 * NW * u;
+        const int row = e / (DP / 4), c = (e % (DP / 4)) * 4;
+        v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (e < TOT && f0 + row < n && c < D) v[u] = load4<T>(F + (f0 + row) * D + c);
+    }
+}
+template <int DP, int NW>
+__device__ __forceinline__ void fixed_store(float* __restrict__ Fs, const float4 (&v)[fixed_per_thread<DP, NW>()]) {
+    constexpr int TOT = 32 * DP / 4;
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int u = 0; u < fixed_per_thread<DP, NW>(); ++u) {
+        const int e = tid + 64 * NW * u;
+        const int row = e / (DP / 4), c = (e % (DP / 4)) * 4;
+        if (e < TOT) *reinterpret_cast<float4*>(Fs + row * (DP + LDP) + c) = v[u];
+    }
+}
+template <int DP>
+__device__ __forceinline__ void fixed_from_lds(const float* __restrict__ Fs, Pieces (&pf)[DP / 16]) {
+    const int lane = threadIdx.x & 63, c = lane & 31, h = lane >> 5;
+    const float* ap = Fs + c * (DP + LDP) + 8 * h;
+#pragma unroll
+    for (int kb = 0; kb < DP / 16; ++kb) {
+        const float4 u = *reinterpret_cast<const float4*>(ap + 16 * kb);
+        const float4 v = *reinterpret_cast<const float4*>(ap + 16 * kb + 4);
+        const float x[8] = {u.x, u.y, u.z, u.w, v.x, v.y, v.z, v.w};
+        pf[kb] = split8(x);
+    }
+}
 // acc[r] = <streamed row tile_row(r,h) of Ss, fixed row (lane & 31)> (raw dots),
 // one bf16 MFMA sextet per 16-deep k-block
 template <int DP>
@@ -157,6 +204,20 @@ constexpr int bwd_waves() {
     return DP <= 128 ? 8 : 4;
 #endif
 }
+// launch 2's fixed tile (stage through LDS, above) gets a region of its own
+// behind the waves' slices where the CU's 160 KiB hold it beside them and lse_s
+// (DP <= 128: 132 KiB + 16.5 KiB + 1 KiB); else it passes through wave 0's
+// slice before that wave's first streamed tile lands there (DP = 256)
+template <int DP, int NW>
+constexpr bool bwd_fixed_own() {
+#ifdef RT_LOSS_FIXED_DIRECT
+    return false;
+#else
+    return inb_lds_bytes<DP>(NW + 1) + SPAN * sizeof(float) <= 160 * 1024;
+#endif
+}
+template <int DP, int NW>
+constexpr size_t bwd_lds_bytes() { return inb_lds_bytes<DP>(bwd_fixed_own<DP, NW>() ? NW + 1 : NW); }
 
 // ---------------------------------------------------------------- launch 1
 // block (it, js < n_split): in-batch partial row log-sum-exp of users
@@ -182,10 +243,23 @@ __global__ __launch_bounds__(256) void loss_fwd_kernel(Args a) {
         // ---- in-batch partial lse: S^T tiles (items j × users i) ----
         float* Ss = sm_f + w * 32 * (DP + LDP);
         Pieces pf[DP / 16];
-        load_fixed3<DP, T>(U, i0, a.b, D, pf);
         const int64_t t0 = static_cast<int64_t>(js) * SPAN + 32 * w, t1 = t0 + 128;
         float4 buf[DP / 8];
+#ifdef RT_LOSS_FIXED_DIRECT
+        load_fixed3<DP, T>(U, i0, a.b, D, pf);
         load_rows<DP, T>(P, t0, a.nx, D, buf);
+#else
+        // the fixed users through wave 0's slice, before its first streamed tile
+        // lands there (a region of its own would cost this kernel its second
+        // block per CU); the branch is block-uniform (js), so the barriers are too
+        float4 fx[fixed_per_thread<DP, 4>()];
+        fixed_load<DP, T, 4>(U, i0, a.b, D, fx);
+        load_rows<DP, T>(P, t0, a.nx, D, buf);  // in flight across the barriers
+        fixed_store<DP, 4>(sm_f, fx);
+        __syncthreads();
+        fixed_from_lds<DP>(sm_f, pf);
+        __syncthreads();  // every wave has its pieces: slice 0 is wave 0's again
+#endif
         float om = -INFINITY, ol = 0.f;
 #pragma unroll 1
         for (int q = 0; q < 2; ++q) {
@@ -369,6 +443,15 @@ __global__ __launch_bounds__(64 * NW) void loss_bwd_kernel(Args a, float wb_eff,
     const float scale = wb_eff / static_cast<float>(a.b);
     float lse_fixed = 0.f;  // row pass: lse of user f0 + c
     const bool ib = wb_eff != 0.f;
+    const bool active = a.grad && ib && f0 < n_fixed && s0 < n_str;  // block-uniform: this block has gradient work
+#ifndef RT_LOSS_FIXED_DIRECT
+    // the fixed tile, once per block: requested here, stored below (after the
+    // LSE reads went out), visible to every wave after the barrier that also
+    // publishes lse_s
+    float* const Fs = bwd_fixed_own<DP, NW>() ? sm_b + NW * 32 * (DP + LDP) : sm_b;
+    float4 fx[fixed_per_thread<DP, NW>()];
+    if (active) fixed_load<DP, T, NW>(Fm, f0, n_fixed, D, fx);
+#endif
     if (row_pass) {
         const int64_t i = f0 + c;
         if (ib && i < a.b) lse_fixed = combine_lse(a.part, a.n_split, a.b, i);
@@ -402,15 +485,24 @@ __global__ __launch_bounds__(64 * NW) void loss_bwd_kernel(Args a, float wb_eff,
             lse_s[x] = i < a.b ? combine_lse(a.part, a.n_split, a.b, i) : 0.f;
         }
     }
+#ifndef RT_LOSS_FIXED_DIRECT
+    if (active) fixed_store<DP, NW>(Fs, fx);
+#endif
     __syncthreads();
-    if (!a.grad || !ib || f0 >= n_fixed || s0 >= n_str) return;
+    if (!active) return;
 
     float* Ss = sm_b + w * 32 * (DP + LDP);
     Pieces pf[DP / 16];
-    load_fixed3<DP, T>(Fm, f0, n_fixed, D, pf);
     const int64_t t0 = s0 + 32 * w;
     float4 buf[DP / 8];
+#ifdef RT_LOSS_FIXED_DIRECT
+    load_fixed3<DP, T>(Fm, f0, n_fixed, D, pf);
     load_rows<DP, T>(Sm, t0, n_str, D, buf);
+#else
+    load_rows<DP, T>(Sm, t0, n_str, D, buf);
+    fixed_from_lds<DP>(Fs, pf);
+    if constexpr (!bwd_fixed_own<DP, NW>()) __syncthreads();  // every wave has its pieces: slice 0 is wave 0's again
+#endif
     f32x16 acc[DT];
 #pragma unroll
     for (int x = 0; x < DT; ++x) acc[x] = f32x16{};
@@ -525,7 +617,7 @@ int launch_loss(const loss::Args& a, dim3 grid1, dim3 grid2, float wb_eff, hipSt
     const int rc = check_launch("loss_fwd_kernel");
     if (rc) return rc;
     constexpr int NW = loss::bwd_waves<DP>();
-    const size_t lds2 = loss::inb_lds_bytes<DP>(NW);
+    const size_t lds2 = loss::bwd_lds_bytes<DP, NW>();
     allow_lds<loss::loss_bwd_kernel<DP, T, NW>>(lds2);
     hipLaunchKernelGGL((loss::loss_bwd_kernel<DP, T, NW>), grid2, dim3(64 * NW), lds2, st, a, wb_eff, true);
     return check_launch("loss_bwd_kernel");

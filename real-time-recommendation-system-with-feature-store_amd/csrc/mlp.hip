@@ -16,6 +16,7 @@
 // same prologue. BN column sums go to RT_STAT_SLOTS fp64 slots (include/rtrec_hip.h).
 #include "rt_common.h"
 #include "split3.h"
+#include "w_frag.h"
 
 namespace rt {
 namespace mlp {
@@ -285,7 +286,8 @@ __device__ __forceinline__ void bn_finalize_last(const rt_linear_fwd_args& a, un
 // Block = 32 rows x all n columns; the transformed A tile (32 x k) lives in LDS
 // as its three bf16 pieces for the whole reduction (A fragments by
 // ds_read_b128), W fragments stream straight from L2 (two float4 per lane per
-// k-block) and are split in registers; each 16-deep k-block is one bf16 MFMA
+// k-block; from rows of W, or in whole lines from its fragment-ordered image,
+// w_frag.h) and are split in registers; each 16-deep k-block is one bf16 MFMA
 // sextet (mfma3); 4 waves split the output columns.
 constexpr int FM = 32;  // rows per block
 
@@ -309,9 +311,13 @@ __host__ __device__ __forceinline__ bool dz_da_fast(const rt_linear_bwd_args& a)
 
 // WPL: the k-loop reads W's split pieces from rt_linear_fwd_args.w_planes
 // (TPW == 1, k % 8 == 0) instead of splitting W fragments in registers
-template <int TPW, bool KVEC, bool WPL>  // 32-col tiles per wave (n <= 128*TPW); KVEC: k % 4 == 0
+// WF: the k-loop reads its W fragments from the fragment-ordered image
+// rt_linear_fwd_args.w_frag (k % 8 == 0, TPW <= 2): 64 consecutive float4 per
+// load, zero-padded, so no per-lane row / column predicate
+template <int TPW, bool KVEC, bool WPL, bool WF = false>  // 32-col tiles per wave (n <= 128*TPW); KVEC: k % 4 == 0
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TPW == 1 ? 3 : 2))) void linear_fwd_kernel(FwdLaunch L) {
     static_assert(!WPL || (TPW == 1 && KVEC), "split-weight planes: one-tile waves, k % 4 == 0");
+    static_assert(!WF || (TPW <= 2 && KVEC && !WPL), "fragment image: one- or two-tile waves, k % 8 == 0");
     const bool g1 = blockIdx.x >= L.split;
     const rt_linear_fwd_args& a = g1 ? L.a1 : L.a0;
     const unsigned bid = blockIdx.x - (g1 ? L.split : 0u);
@@ -421,6 +427,38 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TPW == 1 ? 
             }
         }
     }
+    // fragment-ordered images (side tasks, once per step): the next layer's W
+    // for its forward k-loop and this layer's Wᵀ for its dz launch; one float4
+    // entry per thread, consecutive threads write consecutive entries
+    if (a.next_w_frag || a.wt_frag_out) {
+        const int nblk = static_cast<int>(g1 ? gridDim.x - L.split : L.split);
+        const int64_t e0 = static_cast<int64_t>(bid) * 256 + tid, estep = static_cast<int64_t>(nblk) * 256;
+        if (a.next_w_frag) {
+            const int nn = a.next_n, nk = a.next_k;
+            const int64_t tot = wfrag::fwd_entries(nn, nk);
+            float4* dst = reinterpret_cast<float4*>(a.next_w_frag);
+            for (int64_t e = e0; e < tot; e += estep) {
+                int row, col;
+                wfrag::fwd_coords(nk, e, row, col);
+                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (row < nn && col < nk) v = *reinterpret_cast<const float4*>(a.next_w + static_cast<int64_t>(row) * nk + col);
+                dst[e] = v;
+            }
+        }
+        if (a.wt_frag_out) {
+            const int64_t tot = wfrag::dz_entries(n, k);
+            float4* dst = reinterpret_cast<float4*>(a.wt_frag_out);
+            for (int64_t e = e0; e < tot; e += estep) {
+                int trow, tcol;
+                wfrag::dz_coords(n, e, trow, tcol);
+                float x[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    x[q] = (trow < k && tcol + q < n) ? a.w[static_cast<int64_t>(tcol + q) * k + trow] : 0.f;
+                dst[e] = make_float4(x[0], x[1], x[2], x[3]);
+            }
+        }
+    }
     // one-tile waves (every C2 layer but the first) request their first W
     // fragments before the prologue (they do not depend on it), so the L2
     // latency hides behind the A-tile staging (wider waves would spill)
@@ -437,7 +475,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TPW == 1 ? 
     // kb + 8h .. kb + 8h + 7 of k-block kb); the W fragments of the next
     // iteration are loaded during this one's MFMAs (register double buffer)
     float4 wv[TPW][4], wn[TPW][4];
+    // WF: tile t's fragments of iteration s / 32 are the four 64-float4 runs at
+    // ((t·S + s/32)·4 + j)·64 of the image, one float4 per lane
+    const float4* wfb[TPW];
+#pragma unroll
+    for (int i = 0; i < TPW; ++i)
+        wfb[i] = WF ? reinterpret_cast<const float4*>(a.w_frag) + wfrag::fwd_index(k, w + 4 * i, 0, 0, lane) : nullptr;
     auto load_w = [&](int s, float4 (&dst)[TPW][4]) {
+        if constexpr (WF) {
+#pragma unroll
+            for (int i = 0; i < TPW; ++i) {
+                const float4* p = wfb[i] + (s >> 5) * 256;
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    dst[i][j] = tile_on[i] ? p[j * 64] : make_float4(0.f, 0.f, 0.f, 0.f);  // wave-uniform
+            }
+            return;
+        }
 #pragma unroll
         for (int i = 0; i < TPW; ++i)
 #pragma unroll
@@ -834,8 +888,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TPW == 1 ? 
 // generic passes, the strided W loads, the predicated epilogue and the dsrc
 // store are not compiled in, so their live values do not count against the
 // three-wave register cap
-template <int TPWK, bool WPL, bool KS, int FE>  // 32-col dA tiles per wave (k <= 128*TPWK)
+// WF: dA reads its W fragments from the fragment-ordered image
+// rt_linear_bwd_args.wt_frag (n % 8 == 0, TPWK <= 2): 64 consecutive float4 per
+// load, zero-padded, so no per-lane predicate
+template <int TPWK, bool WPL, bool KS, int FE, bool WF = false>  // 32-col dA tiles per wave (k <= 128*TPWK)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void linear_bwd_dz_kernel(BwdLaunch L) {
+    static_assert(!WF || (TPWK <= 2 && !WPL), "fragment image: one- or two-tile waves");
 #ifdef RT_FOLD_FIRST
     fold_side(L, 0);
 #endif
@@ -876,7 +934,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void l
 #else
     const float* __restrict__ WtT = (a.wt && (n % 8) == 0) ? a.wt : nullptr;
 #endif
+    const float4* __restrict__ Wfr = WF ? reinterpret_cast<const float4*>(a.wt_frag) : nullptr;
     auto load_w = [&](int s, float (&dst)[TPWK][8]) {
+        if constexpr (WF) {
+            // tile kt's fragments of k-block s / 16: the two 64-float4 runs at
+            // ((kt·NS + s/16)·2 + j)·64 of the image
+#pragma unroll
+            for (int i = 0; i < TPWK; ++i) {
+                const int kt = tb + w + 4 * i;
+                float4 v0 = make_float4(0.f, 0.f, 0.f, 0.f), v1 = v0;
+                if (kt * 32 < k) {  // wave-uniform
+                    const float4* p = Wfr + wfrag::dz_index(n, kt, s >> 4, 0, lane);
+                    v0 = p[0];
+                    v1 = p[64];
+                }
+                dst[i][0] = v0.x; dst[i][1] = v0.y; dst[i][2] = v0.z; dst[i][3] = v0.w;
+                dst[i][4] = v1.x; dst[i][5] = v1.y; dst[i][6] = v1.z; dst[i][7] = v1.w;
+            }
+            return;
+        }
 #pragma unroll
         for (int i = 0; i < TPWK; ++i) {
             const int kk = (tb + w + 4 * i) * 32 + c32;
@@ -1815,11 +1891,32 @@ static int validate_fwd(const rt_linear_fwd_args* args) {
                             (reinterpret_cast<uintptr_t>(a.next_w) & 15) ||
                             (reinterpret_cast<uintptr_t>(a.next_w_planes) & 15)))
         return RT_ERR_INVALID;
+    // fragment-ordered images: only on the shapes they cover
+    if (a.w_frag && (rt_linear_w_frag_bytes(a.n, a.k, 0) == 0 || (reinterpret_cast<uintptr_t>(a.w_frag) & 15) ||
+                     (reinterpret_cast<uintptr_t>(a.w) & 15)))
+        return RT_ERR_INVALID;
+    // (the side tasks write rt_linear_w_frag_bytes of the shape: a shape without an image has no size)
+    if (a.next_w_frag && (!a.next_w || rt_linear_w_frag_bytes(a.next_n, a.next_k, 0) == 0 ||
+                          (reinterpret_cast<uintptr_t>(a.next_w) & 15) ||
+                          (reinterpret_cast<uintptr_t>(a.next_w_frag) & 15)))
+        return RT_ERR_INVALID;
+    if (a.wt_frag_out && (rt_linear_w_frag_bytes(a.n, a.k, 1) == 0 || (reinterpret_cast<uintptr_t>(a.wt_frag_out) & 15)))
+        return RT_ERR_INVALID;
     const int kp = mlp::pad8(a.k);
     const int tpw = a.n <= 128 ? 1 : a.n <= 256 ? 2 : 4;
     const size_t lds = (2 * kp + 3 * mlp::FM * kp / 2 + 4 * tpw * mlp::FM) * sizeof(float) + mlp::FM * sizeof(int64_t) + 16;
     if (lds > 160 * 1024) return RT_ERR_UNSUPPORTED;
     return RT_OK;
+}
+
+extern "C" size_t rt_linear_w_frag_bytes(int n, int k, int transposed) {
+    if (n <= 0 || k <= 0) return 0;
+    if (transposed) {
+        if ((n % 8) != 0 || k > 256) return 0;
+        return static_cast<size_t>(wfrag::dz_entries(n, k)) * sizeof(float4);
+    }
+    if ((k % 8) != 0 || n > 256) return 0;
+    return static_cast<size_t>(wfrag::fwd_entries(n, k)) * sizeof(float4);
 }
 
 extern "C" int rt_linear_fwd_f32_multi(const rt_linear_fwd_args* args, int n_args, void* stream) {
@@ -1831,12 +1928,14 @@ extern "C" int rt_linear_fwd_f32_multi(const rt_linear_fwd_args* args, int n_arg
 #endif
     int tpw = 1, kp_max = 0;
     bool kvec = true, wpl = true;  // wpl: every argument set brings its W planes
+    bool wfr = true;               // wfr: every argument set brings its fragment image
     unsigned blocks[2] = {0u, 0u};
     for (int g = 0; g < n_args; ++g) {
         const int v = validate_fwd(&args[g]);
         if (v) return v;
         const rt_linear_fwd_args& a = args[g];
         wpl = wpl && a.w_planes != nullptr;
+        wfr = wfr && a.w_frag != nullptr;
         const int t = a.n <= 128 ? 1 : a.n <= 256 ? 2 : 4;
         tpw = t > tpw ? t : tpw;
         kvec = kvec && (a.k % 4) == 0 && (reinterpret_cast<uintptr_t>(a.w) & 15) == 0;
@@ -1856,13 +1955,15 @@ extern "C" int rt_linear_fwd_f32_multi(const rt_linear_fwd_args* args, int n_arg
     if (total == 0) return RT_OK;
     hipStream_t st = as_stream(stream);
     const dim3 grid(total);
-#define RT_FWD(T, V, P)                                                                           \
-    do {                                                                                          \
-        allow_lds<mlp::linear_fwd_kernel<T, V, P>>(lds);                                          \
-        hipLaunchKernelGGL((mlp::linear_fwd_kernel<T, V, P>), grid, dim3(256), lds, st, L);       \
+#define RT_FWD(T, V, P, ...)                                                                              \
+    do {                                                                                                  \
+        allow_lds<mlp::linear_fwd_kernel<T, V, P, ##__VA_ARGS__>>(lds);                                   \
+        hipLaunchKernelGGL((mlp::linear_fwd_kernel<T, V, P, ##__VA_ARGS__>), grid, dim3(256), lds, st, L); \
     } while (0)
     if (kvec && tpw == 1 && wpl) {
         RT_FWD(1, true, true);
+    } else if (kvec && wfr && tpw <= 2) {  // (an image implies k % 8 == 0 and n <= 256: validate_fwd)
+        if (tpw == 1) RT_FWD(1, true, false, true); else RT_FWD(2, true, false, true);
     } else if (kvec) {
         if (tpw == 1) RT_FWD(1, true, false); else if (tpw == 2) RT_FWD(2, true, false); else RT_FWD(4, true, false);
     } else {
@@ -1902,7 +2003,7 @@ static int dz_fast_class(const rt_linear_bwd_args& a) {
 #if defined(RT_DZ_NO_FE) || defined(RT_NO_WT_ROWS)  // A/B variants
     return 0;
 #endif
-    if (!a.wt || (a.n % 8) != 0) return 0;  // dA reads W through Wᵀ's rows
+    if ((!a.wt && !a.wt_frag) || (a.n % 8) != 0) return 0;  // dA reads W through Wᵀ's rows or its image
     if ((a.m % mlp::FM) != 0 || !mlp::dz_da_fast(a)) return 0;  // every row block full
     if (a.grad_mode == 0) return mlp::dz_norm_fast(a.n) ? 1 : 0;
     return ((a.grad_mode == 1 || a.grad_mode == 2) && mlp::dz_bn_fast(a.n, a.act, a.grad_mode)) ? 2 : 0;
@@ -1929,6 +2030,8 @@ static int validate_bwd(const rt_linear_bwd_args* args) {
                        (reinterpret_cast<uintptr_t>(a.fold_src) & 15) || (reinterpret_cast<uintptr_t>(a.fold_dst) & 15)))
         return RT_ERR_INVALID;
     if (a.wt_planes && ((a.n % 8) != 0 || (reinterpret_cast<uintptr_t>(a.wt_planes) & 15))) return RT_ERR_INVALID;
+    if (a.wt_frag && (rt_linear_w_frag_bytes(a.n, a.k, 1) == 0 || (reinterpret_cast<uintptr_t>(a.wt_frag) & 15)))
+        return RT_ERR_INVALID;
     return RT_OK;
 }
 
@@ -1938,6 +2041,8 @@ extern "C" int rt_linear_bwd_dz_f32_multi(const rt_linear_bwd_args* args, int n_
     size_t lds = 0;
     unsigned blocks[2] = {0u, 0u};
     bool wpl = true;  // every argument set with a dA brings Wᵀ's planes
+    bool wfr = true;  // every argument set with a dA brings Wᵀ's fragment image
+    bool wt_all = true;  // ... row-major Wᵀ (what the FE instances without the image read)
     int fe = -1;      // the fast-paths-only class all argument sets share, or 0
     for (int g = 0; g < n_args; ++g) {
         const int v = validate_bwd(&args[g]);
@@ -1947,6 +2052,8 @@ extern "C" int rt_linear_bwd_dz_f32_multi(const rt_linear_bwd_args* args, int n_
         const int fc = dz_fast_class(a);
         fe = (fe < 0 || fe == fc) ? fc : 0;
         wpl = wpl && (!need_da || a.wt_planes != nullptr);
+        wfr = wfr && need_da && a.wt_frag != nullptr;
+        wt_all = wt_all && a.wt != nullptr;
         const int t = !need_da ? 1 : a.k <= 128 ? 1 : a.k <= 256 ? 2 : 4;
         tpwk = t > tpwk ? t : tpwk;
         const int np = mlp::pad8(a.n);
@@ -1979,13 +2086,23 @@ extern "C" int rt_linear_bwd_dz_f32_multi(const rt_linear_bwd_args* args, int n_
     if (ks == 2) tpwk = 1;
     const dim3 grid(total * ks);
     hipStream_t st = as_stream(stream);
-#define RT_DZ(T, P, K, F)                                                                        \
-    do {                                                                                         \
-        allow_lds<mlp::linear_bwd_dz_kernel<T, P, K, F>>(lds);                                   \
-        hipLaunchKernelGGL((mlp::linear_bwd_dz_kernel<T, P, K, F>), grid, dim3(256), lds, st, L); \
+#define RT_DZ(T, P, K, F, ...)                                                                               \
+    do {                                                                                                     \
+        allow_lds<mlp::linear_bwd_dz_kernel<T, P, K, F, ##__VA_ARGS__>>(lds);                                \
+        hipLaunchKernelGGL((mlp::linear_bwd_dz_kernel<T, P, K, F, ##__VA_ARGS__>), grid, dim3(256), lds, st, L); \
     } while (0)
+    // the FE instances without the image read row-major Wᵀ unconditionally
+    if (!wfr && !wt_all) fe = 0;
     if (ks > 1) {
-        if (wpl) RT_DZ(1, true, true, 0); else RT_DZ(1, false, true, 0);
+        if (wpl) RT_DZ(1, true, true, 0); else if (wfr) RT_DZ(1, false, true, 0, true); else RT_DZ(1, false, true, 0);
+    } else if (wfr && !wpl && tpwk <= 2) {
+        if (tpwk == 1) {
+            if (fe == 1) RT_DZ(1, false, false, 1, true); else RT_DZ(1, false, false, 0, true);
+        } else {
+            if (fe == 1) RT_DZ(2, false, false, 1, true);
+            else if (fe == 2) RT_DZ(2, false, false, 2, true);
+            else RT_DZ(2, false, false, 0, true);
+        }
     } else {
         switch (tpwk) {
             case 1:

@@ -208,6 +208,9 @@ class ChainCtx:
     # Linear's own forward reads) and of its Wᵀ ([3][k][n]: the forward writes, dz reads)
     w_planes: List[Optional[torch.Tensor]] = field(default_factory=list)
     wt_planes: List[Optional[torch.Tensor]] = field(default_factory=list)
+    # fragment-ordered image of each Linear's Wᵀ (the forward writes, dz reads instead of wts)
+    wt_frags: List[Optional[torch.Tensor]] = field(default_factory=list)
+    w_frags: List[torch.Tensor] = field(default_factory=list)  # forward images (kept alive until the launches ran)
     ains: List[Optional[torch.Tensor]] = field(default_factory=list)  # transformed inputs (fwd writes, dW reads)
 
 
@@ -243,6 +246,23 @@ _WPL = os.environ.get("RTREC_W_PLANES", "0")
 SPLIT_W_PLANES = _WPL in ("1", "fwd", "dz")
 SPLIT_W_PLANES_FWD = _WPL in ("1", "fwd")
 SPLIT_W_PLANES_DZ = _WPL in ("1", "dz")
+# Fragment-ordered weight images: the fp32 values of a
+# training chain's weights stored in the order the lanes of the forward / dz
+# k-loops read them, written once per chain by a side task (the previous
+# launch writes rt_linear_fwd_args.next_w_frag for the forward, the Linear's own
+# forward writes wt_frag_out for its dz launch), so every W load of a wave is
+# 64 consecutive float4 instead of 32 rows x 32 bytes. Same values, same MFMA
+# order: bit-identical (tests/test_gpu_w_frag.py). The images are rewritten by
+# every chain, never cached. RTREC_W_FRAG=0 turns them off, =fwd / =dz enable
+# one side only (A/B).
+_WFR = os.environ.get("RTREC_W_FRAG", "1")
+W_FRAG_FWD = _WFR in ("1", "fwd")
+W_FRAG_DZ = _WFR in ("1", "dz")
+
+
+def _w_frag_floats(n: int, k: int, transposed: bool) -> int:
+    """fp32 words of a weight's fragment-ordered image (0: the shape has none)."""
+    return int(native.lib().rt_linear_w_frag_bytes(n, k, 1 if transposed else 0)) // 4
 
 
 def stats_arena_size(blocks: List[Block], n_seg: int = 1) -> int:
@@ -407,16 +427,23 @@ def _forward_plan(blocks: List[Block], src: torch.Tensor, ids: Optional[torch.Te
         # dz launch computes the previous block's gradient); training forwards
         # only — eval / serving forwards have no backward to read it. With
         # SPLIT_W_PLANES the forward writes Wᵀ's split pieces instead (n % 8 == 0).
-        wt = wtp = None
+        # With W_FRAG_DZ the forward writes Wᵀ's fragment-ordered image instead
+        # (n % 8 == 0, k <= 256); row-major Wᵀ is then not written at all.
+        wt = wtp = wtf = None
         if li > 0 and lin.training:
+            ftw = _w_frag_floats(lin.out_features, lin.in_features, True) if W_FRAG_DZ else 0
             if SPLIT_W_PLANES and SPLIT_W_PLANES_DZ and lin.out_features % 8 == 0:
                 wtp = torch.empty((3, lin.in_features, lin.out_features), dtype=torch.int16, device=dev)
                 a.wt_planes_out = wtp.data_ptr()
+            elif ftw:
+                wtf = torch.empty(ftw, dtype=torch.float32, device=dev)
+                a.wt_frag_out = wtf.data_ptr()
             else:
                 wt = torch.empty((lin.in_features, lin.out_features), dtype=torch.float32, device=dev)
                 a.wt_out = wt.data_ptr()
         ctx.wts.append(wt)
         ctx.wt_planes.append(wtp)
+        ctx.wt_frags.append(wtf)
         # W's split pieces for this launch's k-loop, written by the previous
         # launch of the chain (layers past the first; k % 8 == 0, n <= 128)
         wp = None
@@ -428,6 +455,19 @@ def _forward_plan(blocks: List[Block], src: torch.Tensor, ids: Optional[torch.Te
             prev.next_n, prev.next_k = lin.out_features, lin.in_features
             a.w_planes = wp.data_ptr()
         ctx.w_planes.append(wp)
+        # W's fragment-ordered image for this launch's k-loop, written by the
+        # previous launch of a training chain (layers past the first; k % 8 == 0,
+        # n <= 256); eval / serving forwards keep the loads from W
+        if wp is None and W_FRAG_FWD and li > 0 and lin.training:
+            fw = _w_frag_floats(lin.out_features, lin.in_features, False)
+            if fw:
+                wf = torch.empty(fw, dtype=torch.float32, device=dev)
+                prev = layers[li - 1]
+                prev.next_w = lin.weight.data_ptr()
+                prev.next_w_frag = wf.data_ptr()
+                prev.next_n, prev.next_k = lin.out_features, lin.in_features
+                a.w_frag = wf.data_ptr()
+                ctx.w_frags.append(wf)
         # training: the launch also writes the transformed input it stages (act →
         # BN → dropout of the previous block), which this Linear's dW launch then
         # reads as is instead of recomputing it (rt_linear_fwd_args.a_out / a_in)
@@ -746,6 +786,8 @@ def _backward_plan(blocks: List[Block], ctx: ChainCtx, dout: torch.Tensor, slab:
                 a.wt = ctx.wts[li].data_ptr()
             if li < len(ctx.wt_planes) and ctx.wt_planes[li] is not None:
                 a.wt_planes = ctx.wt_planes[li].data_ptr()
+            if li < len(ctx.wt_frags) and ctx.wt_frags[li] is not None:
+                a.wt_frag = ctx.wt_frags[li].data_ptr()
             if li < len(ctx.ains) and ctx.ains[li] is not None:
                 a.a_in = ctx.ains[li].data_ptr()
         layers.append(a)

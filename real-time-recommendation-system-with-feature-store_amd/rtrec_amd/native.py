@@ -55,6 +55,7 @@ class LinearFwdArgs(ctypes.Structure):
         ("fin_num_batches_tracked", vp), ("fin_eps", c_f32), ("fin_momentum", c_f32), ("prev_final", c_int),
         ("w_planes", vp), ("wt_planes_out", vp), ("next_w", vp), ("next_w_planes", vp), ("next_n", c_int),
         ("next_k", c_int),
+        ("w_frag", vp), ("next_w_frag", vp), ("wt_frag_out", vp),
     ]
 
 
@@ -70,7 +71,7 @@ class LinearBwdArgs(ctypes.Structure):
         ("seed_offset", vp), ("g_prev", vp), ("g_prev_stats", vp), ("dsrc", vp), ("seg_split", c_i64),
         ("dbias_slots", vp), ("wt", vp), ("fuse_dz", c_int), ("a_in", vp), ("dw_part", vp),
         ("fold_src", vp), ("fold_dst", vp), ("fold_words", c_i64), ("fold_splits", c_int), ("fold_in", c_int),
-        ("wt_planes", vp),
+        ("wt_planes", vp), ("wt_frag", vp),
     ]
 
 
@@ -146,6 +147,7 @@ SIGNATURES = {
     "rt_feeder_batch": (c_int, [vp, vp, vp, vp, c_i64, vp, vp, vp]),
     "rt_feeder_commit": (c_int, [vp, vp, c_i64, vp, vp]),
     "rt_linear_fwd_f32": (c_int, [ctypes.POINTER(LinearFwdArgs), vp]),
+    "rt_linear_w_frag_bytes": (c_size, [c_int, c_int, c_int]),
     "rt_linear_bwd_f32": (c_int, [ctypes.POINTER(LinearBwdArgs), vp]),
     "rt_linear_bwd_dz_f32": (c_int, [ctypes.POINTER(LinearBwdArgs), vp]),
     "rt_linear_bwd_dz_fused": (c_int, [ctypes.POINTER(LinearBwdArgs), c_int]),
