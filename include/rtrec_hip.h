@@ -234,6 +234,29 @@ int rt_flatip_topk_online_lists(const void* queries, int64_t nq, const void* ite
  *   workspace (8 bytes), exclude_words too small; RT_ERR_UNSUPPORTED for
  *   k > RT_IVF_MAX_K, nprobe > RT_IVF_MAX_NPROBE, nq > 65,535, a refused
  *   d / dtype pair, nx >= 2^31 - 1; RT_ERR_WORKSPACE. nq == 0: RT_OK.
+ * rt_ivf_topk_lists: rt_ivf_topk with the bitmap replaced by up to
+ *   RT_ONLINE_MAX_EXCL_SOURCES CSR sources that the scan reads itself;
+ *   RtExclusionLists means what it means for rt_flatip_topk_online_lists:
+ *   query q uses CSR row rows ? rows[q] : q of each source, a CSR row outside
+ *   [0, n_rows) excludes nothing, items ascend within a CSR row, duplicates
+ *   are allowed, items >= nx are ignored. Items are ORIGINAL corpus positions:
+ *   the space of row_pos values, of exclude_bits and of out_ids. A query skips
+ *   the union of its CSR rows over all sources. Any list length; a list may
+ *   exclude every probed row (then every slot is (-FLT_MAX, -1)). A CSR row
+ *   that does not ascend gives unspecified exclusions for that query and
+ *   nothing worse: no read falls outside [offsets[r], offsets[r + 1]) of
+ *   `items` (offsets[r + 1] < offsets[r] is an empty row). A lane whose row
+ *   passed the range and threshold tests looks its position up by bisection —
+ *   the order of row_pos plays no part; CSR rows of up to 8,960 entries per
+ *   query (all sources together) are searched in LDS, longer ones in global
+ *   memory. n_lists == 0: rt_ivf_topk without a bitmap, bit for bit.
+ *   Workspace (rt_ivf_topk_workspace_bytes), plan (rt_ivf_topk_plan), result
+ *   order and score bits are rt_ivf_topk's; every nq <= 65,535 is served (a
+ *   scan block serves one query).
+ *   Status, before any device work: RT_ERR_INVALID for n_lists < 0, lists ==
+ *   NULL with n_lists > 0, a source with offsets == NULL, n_rows < 0, or items
+ *   == NULL with n_rows > 0; RT_ERR_UNSUPPORTED for n_lists >
+ *   RT_ONLINE_MAX_EXCL_SOURCES; then every refusal of rt_ivf_topk.
  * rt_ivf_topk_plan: host only. out = {chunks per list, rows per chunk, scan
  *   blocks}: a probed list is scanned by `chunks` blocks of `rows per chunk`
  *   rows (a multiple of 256; chunks x rows >= max_list_rows), blocks = nq x
@@ -269,6 +292,10 @@ int rt_ivf_topk(const void* queries, int64_t nq, const void* rows, int64_t nx, i
                 const int64_t* list_offsets, int64_t nlist, const int32_t* row_pos, const int64_t* probes,
                 int nprobe, int64_t max_list_rows, int k, const uint32_t* exclude_bits, int64_t exclude_words,
                 float* out_scores, int64_t* out_ids, void* workspace, size_t workspace_bytes, void* stream);
+int rt_ivf_topk_lists(const void* queries, int64_t nq, const void* rows, int64_t nx, int d, int dtype,
+                      const int64_t* list_offsets, int64_t nlist, const int32_t* row_pos, const int64_t* probes,
+                      int nprobe, int64_t max_list_rows, int k, const RtExclusionLists* lists, int n_lists,
+                      float* out_scores, int64_t* out_ids, void* workspace, size_t workspace_bytes, void* stream);
 int rt_segment_mean_f32(const void* rows, int64_t n, int d, int dtype, const int64_t* offsets, int64_t n_seg,
                         const float* prev, int normalize, float* out, void* stream);
 

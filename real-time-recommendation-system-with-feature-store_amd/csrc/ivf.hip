@@ -27,6 +27,16 @@
 //
 // The grid depends on host arguments only (nq, nprobe, max_list_rows): no host
 // read, stream-ordered, capturable.
+//
+// rt_ivf_topk_lists: the same two launches, the scan's LISTS instantiation. The
+// exclusions are CSR lists of ORIGINAL positions instead of the bitmap. Stored
+// rows do not arrive in position order (row_pos is any permutation), so the
+// Flat scan's cursors and windows do not apply: a lane whose row passed the
+// range and threshold tests looks its position up by a lower-bound binary
+// search in its query's CSR row of every source. The block resolves those rows
+// once, in its prologue, and copies them into LDS when together they fit
+// kListCap entries (else the search reads `items` in global memory): one
+// search routine over a generic pointer serves both.
 #include "topk_online.h"
 
 namespace rt {
@@ -74,16 +84,49 @@ __device__ __forceinline__ void compact_keep_ties(Cand* buf, int& n, int k, int 
     thr = lo;
 }
 
-template <typename T>
+// ---- exclusion lists (the LISTS instantiation) ----
+// The staged lists take what two blocks per CU leave of the LDS next to the
+// scan's own Lds<1>: (163,840 / 2 - 128) - 45,568 - 384 = 35,840 B = 8,960
+// positions for the query's CSR rows of all sources together. The 384 B stand
+// for what the block holds outside `lds`: cnt and thr, the 256 B scratch of the
+// block-wide reduction behind __syncthreads_or, and alignment.
+constexpr int kLdsPerBlock = 163840 / 2 - 128;
+constexpr int kListSlack = 384;
+constexpr int kListBytes = ((kLdsPerBlock - on::Lds<1>::kBytes - kListSlack) / 16) * 16;
+constexpr int kListCap = kListBytes / 4;
+static_assert(kListBytes > 0 && kListBytes % 16 == 0, "ivf: the staged lists follow the scan's 16-byte aligned LDS");
+static_assert(2 * (on::Lds<1>::kBytes + kListBytes + kListSlack + 128) <= 163840, "ivf: two blocks per CU");
+
+// Whether items[lo, hi) (ascending; LDS or global) holds `pos`, for the lanes
+// with `act`: a lower bound by bisection. Every lane of the wave calls it; the
+// loop runs until no lane has a range left (wave-uniform trip count, no
+// barrier inside). Every read is at an index in [lo, hi), whatever the items
+// hold: a row that does not ascend gives a wrong answer, nothing worse.
+__device__ __forceinline__ bool list_has(const int32_t* items, int64_t lo, int64_t hi, int32_t pos, bool act) {
+    int64_t a = lo, b = act ? hi : lo;
+    while (__any(a < b)) {
+        if (a < b) {
+            const int64_t mid = a + ((b - a) >> 1);
+            if (items[mid] < pos) a = mid + 1;
+            else b = mid;
+        }
+    }
+    return act && a < hi && items[a] == pos;
+}
+
+// LISTS: the exclusions are `la`'s CSR lists (excl is not read); otherwise the
+// optional dense bitmap `excl`.
+template <typename T, bool LISTS>
 __global__ __launch_bounds__(on::kThreads, 2) void ivf_scan(
     const T* __restrict__ Q, const char* __restrict__ X, int64_t nx, int d, int k,
     const int64_t* __restrict__ list_offsets, int64_t nlist, const int32_t* __restrict__ row_pos,
     const int64_t* __restrict__ probes, int nprobe, int chunks, int64_t rows_per_chunk,
-    const uint32_t* __restrict__ excl, int64_t excl_words, uint64_t* __restrict__ partials) {
+    const uint32_t* __restrict__ excl, int64_t excl_words, uint64_t* __restrict__ partials,
+    const on::ListArgs<LISTS> la) {
     constexpr int EPU = 16 / static_cast<int>(sizeof(T));
     constexpr int kThreads = on::kThreads, kTileRows = on::kTileRows, kStepUnits = on::kStepUnits;
     using L = on::Lds<1>;
-    __shared__ __attribute__((aligned(16))) char lds[L::kBytes];
+    __shared__ __attribute__((aligned(16))) char lds[L::kBytes + (LISTS ? kListBytes : 0)];
     __shared__ int cnt;
     __shared__ float thr;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -131,6 +174,40 @@ __global__ __launch_bounds__(on::kThreads, 2) void ivf_scan(
 
     uint4 R[kStepUnits];
     on::load_step(R, w, 0, 0);
+    // the query's CSR row of every source: items xit[s][xlo[s], xhi[s]) (block-uniform)
+    const int32_t* xit[on::kMaxSrc];
+    int64_t xlo[on::kMaxSrc], xhi[on::kMaxSrc];
+    if constexpr (LISTS) {
+#pragma unroll
+        for (int s = 0; s < on::kMaxSrc; ++s) {
+            xit[s] = nullptr;
+            xlo[s] = xhi[s] = 0;
+            if (s < la.n) {
+                const on::ListSrc& src = la.src[s];
+                const int64_t r = src.rows ? src.rows[q] : static_cast<int64_t>(q);
+                if (r >= 0 && r < src.n_rows) {
+                    const int64_t lo = src.offsets[r], hi = src.offsets[r + 1];
+                    xit[s] = src.items;
+                    xlo[s] = lo;
+                    xhi[s] = hi < lo ? lo : hi;
+                }
+            }
+        }
+        // while the first step is in flight: rows that fit the region together are
+        // searched in LDS; the barrier below publishes them
+        static_assert(on::kMaxSrc == 2, "ivf: the staging lays two sources side by side");
+        const int64_t n0 = xhi[0] - xlo[0], n1 = xhi[1] - xlo[1];
+        if (n0 <= kListCap && n1 <= kListCap - n0) {
+            int32_t* const stg = reinterpret_cast<int32_t*>(lds + L::kBytes);
+            for (int e = threadIdx.x; e < static_cast<int>(n0); e += kThreads) stg[e] = xit[0][xlo[0] + e];
+            for (int e = threadIdx.x; e < static_cast<int>(n1); e += kThreads)
+                stg[static_cast<int>(n0) + e] = xit[1][xlo[1] + e];
+            xit[0] = xit[1] = stg;
+            xlo[0] = 0;
+            xhi[0] = xlo[1] = n0;
+            xhi[1] = n0 + n1;
+        }
+    }
     __syncthreads();
 
     int over = 0;  // decided through the barrier that ends a tile: block-uniform (flatip_online_scan)
@@ -159,7 +236,16 @@ __global__ __launch_bounds__(on::kThreads, 2) void ivf_scan(
         // a position outside [0, nx) (a corrupt row_pos) is dropped: it has no bit in
         // the bitmap and no row in the caller's corpus
         bool pass = pos >= 0 && static_cast<int64_t>(pos) < nx && acc[0] >= th;
-        if (excl && pass)
+        if constexpr (LISTS) {
+            if (__any(pass)) {  // wave-uniform
+#pragma unroll
+                for (int s = 0; s < on::kMaxSrc; ++s) {
+                    if (xhi[s] <= xlo[s]) continue;  // block-uniform
+                    const bool listed = list_has(xit[s], xlo[s], xhi[s], pos, pass);  // every lane calls
+                    pass = pass && !listed;
+                }
+            }
+        } else if (excl && pass)
             pass = ((excl[static_cast<int64_t>(q) * excl_words + (pos >> 5)] >> (pos & 31)) & 1u) == 0u;
         over = __syncthreads_or(on::append<true>(pass, &cnt, cand, acc[0], static_cast<uint32_t>(pos)));
     }
@@ -261,11 +347,12 @@ extern "C" size_t rt_ivf_topk_workspace_bytes(int64_t nq, int nprobe, int64_t ma
     return need < 256 ? 256 : need;
 }
 
-extern "C" int rt_ivf_topk(const void* queries, int64_t nq, const void* rows, int64_t nx, int d, int dtype,
-                           const int64_t* list_offsets, int64_t nlist, const int32_t* row_pos,
-                           const int64_t* probes, int nprobe, int64_t max_list_rows, int k,
-                           const uint32_t* exclude_bits, int64_t exclude_words, float* out_scores,
-                           int64_t* out_ids, void* workspace, size_t workspace_bytes, void* stream) {
+// both entry points: the dense bitmap (la == nullptr) or the lists
+static int ivf_search(const void* queries, int64_t nq, const void* rows, int64_t nx, int d, int dtype,
+                      const int64_t* list_offsets, int64_t nlist, const int32_t* row_pos, const int64_t* probes,
+                      int nprobe, int64_t max_list_rows, int k, const uint32_t* exclude_bits, int64_t exclude_words,
+                      const ivon::ListArgs<true>* la, float* out_scores, int64_t* out_ids, void* workspace,
+                      size_t workspace_bytes, void* stream) {
     if (nq < 0 || nx < 0 || d <= 0 || k <= 0 || nlist <= 0 || nprobe <= 0 || max_list_rows < 0) return RT_ERR_INVALID;
     if (nq == 0) return RT_OK;
     if (!queries || !out_scores || !out_ids || !list_offsets || !probes || (nx > 0 && (!rows || !row_pos)))
@@ -285,19 +372,56 @@ extern "C" int rt_ivf_topk(const void* queries, int64_t nq, const void* rows, in
     uint64_t* partials = static_cast<uint64_t*>(workspace);
     const dim3 grid(static_cast<unsigned>(lists), static_cast<unsigned>(nq)), block(ivon::kThreads);
     const char* x = static_cast<const char*>(rows);
-#define RT_IVF_LAUNCH(T)                                                                                      \
-    hipLaunchKernelGGL((iv::ivf_scan<T>), grid, block, 0, st, static_cast<const T*>(queries), x, nx, d, k,    \
-                       list_offsets, nlist, row_pos, probes, nprobe, p.chunks, p.rows_per_chunk, exclude_bits, \
-                       exclude_words, partials)
-    switch (dtype) {
-        case RT_F32: RT_IVF_LAUNCH(float); break;
-        case RT_F16: RT_IVF_LAUNCH(__half); break;
-        default: RT_IVF_LAUNCH(__hip_bfloat16); break;
+#define RT_IVF_LAUNCH(T, LISTS, LA)                                                                             \
+    hipLaunchKernelGGL((iv::ivf_scan<T, LISTS>), grid, block, 0, st, static_cast<const T*>(queries), x, nx, d, k, \
+                       list_offsets, nlist, row_pos, probes, nprobe, p.chunks, p.rows_per_chunk, exclude_bits,     \
+                       exclude_words, partials, LA)
+    if (la) {
+        switch (dtype) {
+            case RT_F32: RT_IVF_LAUNCH(float, true, *la); break;
+            case RT_F16: RT_IVF_LAUNCH(__half, true, *la); break;
+            default: RT_IVF_LAUNCH(__hip_bfloat16, true, *la); break;
+        }
+    } else {
+        const ivon::ListArgs<false> none{};
+        switch (dtype) {
+            case RT_F32: RT_IVF_LAUNCH(float, false, none); break;
+            case RT_F16: RT_IVF_LAUNCH(__half, false, none); break;
+            default: RT_IVF_LAUNCH(__hip_bfloat16, false, none); break;
+        }
     }
 #undef RT_IVF_LAUNCH
     int rc = check_launch("ivf_scan");
     if (rc) return rc;
     return ivon::launch_finish(partials, lists, k, out_scores, out_ids, 0, nq, st);
+}
+
+extern "C" int rt_ivf_topk(const void* queries, int64_t nq, const void* rows, int64_t nx, int d, int dtype,
+                           const int64_t* list_offsets, int64_t nlist, const int32_t* row_pos,
+                           const int64_t* probes, int nprobe, int64_t max_list_rows, int k,
+                           const uint32_t* exclude_bits, int64_t exclude_words, float* out_scores,
+                           int64_t* out_ids, void* workspace, size_t workspace_bytes, void* stream) {
+    return ivf_search(queries, nq, rows, nx, d, dtype, list_offsets, nlist, row_pos, probes, nprobe, max_list_rows, k,
+                      exclude_bits, exclude_words, nullptr, out_scores, out_ids, workspace, workspace_bytes, stream);
+}
+
+extern "C" int rt_ivf_topk_lists(const void* queries, int64_t nq, const void* rows, int64_t nx, int d, int dtype,
+                                 const int64_t* list_offsets, int64_t nlist, const int32_t* row_pos,
+                                 const int64_t* probes, int nprobe, int64_t max_list_rows, int k,
+                                 const RtExclusionLists* lists, int n_lists, float* out_scores, int64_t* out_ids,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+    if (n_lists < 0 || (n_lists > 0 && !lists)) return RT_ERR_INVALID;
+    if (n_lists > RT_ONLINE_MAX_EXCL_SOURCES) return RT_ERR_UNSUPPORTED;
+    ivon::ListArgs<true> la{};
+    la.n = n_lists;
+    for (int s = 0; s < n_lists; ++s) {
+        const RtExclusionLists& L = lists[s];
+        if (!L.offsets || L.n_rows < 0 || (L.n_rows > 0 && !L.items)) return RT_ERR_INVALID;
+        la.src[s] = ivon::ListSrc{L.offsets, L.items, L.rows, L.n_rows};
+    }
+    // no source: the plain scan, bit for bit rt_ivf_topk without a bitmap
+    return ivf_search(queries, nq, rows, nx, d, dtype, list_offsets, nlist, row_pos, probes, nprobe, max_list_rows, k,
+                      nullptr, 0, n_lists ? &la : nullptr, out_scores, out_ids, workspace, workspace_bytes, stream);
 }
 
 extern "C" int rt_segment_mean_f32(const void* rows, int64_t n, int d, int dtype, const int64_t* offsets,

@@ -551,15 +551,26 @@ def ivf_topk_tuning(min_chunk_tiles: int = 0) -> None:
 def ivf_topk(queries: torch.Tensor, rows: torch.Tensor, list_offsets: torch.Tensor, row_pos: torch.Tensor,
              probes: torch.Tensor, max_list_rows: int, k: int, exclude_bits: Optional[torch.Tensor] = None,
              out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
-             workspace_buf: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+             workspace_buf: Optional[torch.Tensor] = None,
+             exclude_lists=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Top-k over the union of the probed lists (rt_ivf_topk): (scores [nq, k] f32,
     original positions [nq, k] int64) in (score desc, position asc) order,
     (-FLT_MAX, -1) pads. ``rows`` [nx, d] are stored list-contiguous, list l =
     stored rows ``[list_offsets[l], list_offsets[l + 1])``; ``row_pos`` int32 [nx]
     = original position of each stored row; ``probes`` int64 [nq, nprobe] list
     ids (-1: skipped); ``exclude_bits`` is indexed by original position.
+    ``exclude_lists`` (rt_ivf_topk_lists; not together with ``exclude_bits``):
+    the forms of :func:`flatip_topk_online`'s — one or two ``(offsets, items[,
+    rows])`` CSR sources of ORIGINAL positions that the scan reads itself.
     Batches above 32,768 queries run in chunks."""
+    if exclude_lists is not None and exclude_bits is not None:
+        raise ValueError("exclude_bits and exclude_lists are mutually exclusive")
+    sources = _exclusion_sources(exclude_lists, queries)
     native.require_device(queries, rows, list_offsets, row_pos, probes, exclude_bits, what="ivf_topk")
+    for src in sources:
+        native.require_device(*src, what="ivf_topk")
+    # a source without items excludes nothing (and has no items pointer to give)
+    sources = [src for src in sources if src[1].numel()]
     if queries.dim() != 2 or rows.dim() != 2 or queries.shape[1] != rows.shape[1]:
         raise ValueError(f"shape mismatch: queries {tuple(queries.shape)} rows {tuple(rows.shape)}")
     if queries.dtype != rows.dtype:
@@ -590,6 +601,27 @@ def ivf_topk(queries: torch.Tensor, rows: torch.Tensor, list_offsets: torch.Tens
         if ws is None:
             ws = workspace(queries.device,
                            native.lib().rt_ivf_topk_workspace_bytes(b - a, nprobe, int(max_list_rows), k), "ivf_topk")
+        if exclude_lists is not None:
+            # query a + q of the chunk: rows[a + q] of a source with rows, else CSR row a + q —
+            # the offsets advanced by a (a source the chunk lies past: dropped)
+            arr = (native.ExclusionLists * native.ONLINE_MAX_EXCL_SOURCES)()
+            n_src = 0
+            for offsets, its, xrows in sources:
+                n_rows = offsets.numel() - 1
+                if xrows is None:
+                    if n_rows - a <= 0:
+                        continue
+                    offsets, n_rows = offsets[a:], n_rows - a
+                else:
+                    xrows = xrows[a:b]
+                s = arr[n_src]
+                s.offsets, s.items, s.n_rows, s.rows = ptr(offsets), ptr(its), n_rows, ptr(xrows)
+                n_src += 1
+            call("rt_ivf_topk_lists", ptr(queries[a:b]), b - a, ptr(rows) if nx else None, nx, d, dt,
+                 ptr(list_offsets), nlist, ptr(row_pos) if nx else None, ptr(probes[a:b]), nprobe,
+                 int(max_list_rows), k, arr, n_src, ptr(scores[a:b]), ptr(ids[a:b]), ptr(ws), ws.numel(),
+                 stream_of(queries))
+            continue
         call("rt_ivf_topk", ptr(queries[a:b]), b - a, ptr(rows) if nx else None, nx, d, dt, ptr(list_offsets), nlist,
              ptr(row_pos) if nx else None, ptr(probes[a:b]), nprobe, int(max_list_rows), k,
              ptr(exclude_bits[a:b]) if exclude_bits is not None else None, words, ptr(scores[a:b]), ptr(ids[a:b]),

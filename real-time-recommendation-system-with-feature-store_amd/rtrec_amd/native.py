@@ -99,7 +99,8 @@ ONLINE_MAX_EXCL_SOURCES = 2   # RT_ONLINE_MAX_EXCL_SOURCES
 
 
 class ExclusionLists(ctypes.Structure):
-    """RtExclusionLists: one CSR source of rt_flatip_topk_online_lists (device pointers)."""
+    """RtExclusionLists: one CSR source of rt_flatip_topk_online_lists / rt_ivf_topk_lists
+    (device pointers)."""
     _fields_ = [("offsets", vp), ("items", vp), ("n_rows", c_i64), ("rows", vp)]
 
 
@@ -132,6 +133,8 @@ SIGNATURES = {
     "rt_ivf_topk_workspace_bytes": (c_size, [c_i64, c_int, c_i64, c_int]),
     "rt_ivf_topk": (c_int, [vp, c_i64, vp, c_i64, c_int, c_int, vp, c_i64, vp, vp, c_int, c_i64, c_int, vp, c_i64,
                             vp, vp, vp, c_size, vp]),
+    "rt_ivf_topk_lists": (c_int, [vp, c_i64, vp, c_i64, c_int, c_int, vp, c_i64, vp, vp, c_int, c_i64, c_int,
+                                  ctypes.POINTER(ExclusionLists), c_int, vp, vp, vp, c_size, vp]),
     "rt_segment_mean_f32": (c_int, [vp, c_i64, c_int, c_int, vp, c_i64, vp, c_int, vp, vp]),
     "rt_topk_merge": (c_int, [vp, vp, c_i64, c_int, c_int, c_int, vp, vp, vp]),
     "rt_flatip_topk_tuning": (c_int, [c_int, c_int, c_int]),

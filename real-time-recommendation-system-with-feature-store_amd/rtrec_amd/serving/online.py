@@ -22,8 +22,8 @@ import torch.nn as nn
 
 from .. import kernels, native
 from ..models.fused import blocks_from_sequential
-from .retrieval import (HipFlatIPIndex, OnlineSearcher, RetrievalEngine, _capture, _exclude_positions,
-                        _lists_from_positions, _per_query)
+from .retrieval import (HipFlatIPIndex, HipIVFFlatIndex, OnlineSearcher, RetrievalEngine, _capture,
+                        _exclude_positions, _lists_from_positions, _per_query)
 
 Features = Union[np.ndarray, torch.Tensor, Dict[str, Any]]
 Rows = Union[np.ndarray, torch.Tensor]
@@ -39,8 +39,9 @@ class OnlineRecommender:
     """``OnlineRecommender(model, index, max_batch=8, user_table=None)``.
 
     ``model``: a :class:`~rtrec_amd.models.two_tower.TwoTowerModel` (its user
-    tower is served) or a tower. ``index``: a :class:`HipFlatIPIndex`, or a
-    :class:`RetrievalEngine` whose index is one. ``user_table``: an optional
+    tower is served) or a tower. ``index``: a :class:`HipFlatIPIndex` or a
+    :class:`HipIVFFlatIndex`, or a :class:`RetrievalEngine` whose index is one
+    of them. ``user_table``: an optional
     resident ``[n_users, F]`` fp32 device tensor (the MovieLens user table
     ``evaluation/offline.py`` gathers from); ``user_ids`` are its rows.
 
@@ -58,6 +59,15 @@ class OnlineRecommender:
     positions; from the renorm on it is ``OnlineSearcher._device_chain``, so
     ``recommend(x, k)`` returns what ``index.search(embed(x), k)`` returns
     through the online searcher. ``embed`` replays H2D → tower → D2H.
+    Over a :class:`HipIVFFlatIndex` the searcher is the index's own
+    (``index.online_searcher``: an ``OnlineIVFSearcher``, or the inner Flat
+    index's searcher for a corpus that fell back to Flat) and the tail of the
+    chain is its ``_device_chain``: renorm → coarse search over the centroids →
+    cast → ``rt_ivf_topk`` (``rt_ivf_topk_lists`` with exclusions, in original
+    positions like the seen-items CSR). ``index.nprobe`` is read at every call
+    and is part of those graphs' keys. An index that switches between lists and
+    the Flat fallback (``build`` / ``load``) after the recommender was made
+    needs a new recommender: ``recommend`` raises ``ValueError``.
     ``RTREC_ONLINE_GRAPH=0`` (read at every call) runs the chains eagerly.
 
     Calls outside the graphs' range (``k_search`` > 128, more than
@@ -70,7 +80,8 @@ class OnlineRecommender:
     (``rt_flatip_topk_online_lists``) — the per-request ids through the
     searcher's two fixed-size H2D copies, the seen items from a resident CSR
     indexed by the device ids the tower gather reads. Graphs with exclusions
-    are keyed ``(nq, k_search, by_ids, items, seen)``.
+    are keyed ``(nq, k_search, by_ids, items, seen)``; over IVF lists every
+    search graph is keyed ``(nq, k_search, by_ids, items, seen, nprobe)``.
 
     Staleness. Index: ``build`` / ``add`` / ``load`` bump its generation and
     the search graphs are dropped and captured again. Model: the graphs hold the live
@@ -89,7 +100,8 @@ class OnlineRecommender:
     MAX_BATCH = native.TOWER_MAX_ROWS
     MAX_GRAPHS = 64
 
-    def __init__(self, model: nn.Module, index: Union[HipFlatIPIndex, RetrievalEngine], max_batch: int = 8,
+    def __init__(self, model: nn.Module, index: Union[HipFlatIPIndex, HipIVFFlatIndex, RetrievalEngine],
+                 max_batch: int = 8,
                  user_table: Optional[torch.Tensor] = None, max_exclude: int = 8192):
         if not 1 <= int(max_batch) <= self.MAX_BATCH:
             raise ValueError(f"max_batch={max_batch}: 1..{self.MAX_BATCH}")
@@ -98,9 +110,9 @@ class OnlineRecommender:
         self.tower = getattr(model, "user_tower", model)
         if isinstance(index, RetrievalEngine):
             index = index.index
-        if not isinstance(index, HipFlatIPIndex):
-            raise ValueError(f"index must be a HipFlatIPIndex (or a RetrievalEngine over one), got "
-                             f"{type(index).__name__}")
+        if not isinstance(index, (HipFlatIPIndex, HipIVFFlatIndex)):
+            raise ValueError(f"index must be a HipFlatIPIndex or a HipIVFFlatIndex (or a RetrievalEngine over "
+                             f"one), got {type(index).__name__}")
         self.index = index
         # -- what rt_tower_infer_f32 serves ------------------------------------
         if len(getattr(self.tower, "embeddings", {})) or getattr(self.tower, "categorical_features", None):
@@ -144,7 +156,13 @@ class OnlineRecommender:
         self.user_table = user_table
         native.lib()
         mb, f, d = self.max_batch, self.input_dim, self.dimension
-        self._searcher = OnlineSearcher(index, mb, max_exclude)
+        if isinstance(index, HipIVFFlatIndex):
+            if index.index is None:
+                raise ValueError("OnlineRecommender over a HipIVFFlatIndex needs the index built: its searcher "
+                                 "is sized for the lists (or for the Flat fallback of a small corpus)")
+            self._searcher = index.online_searcher(mb, max_exclude)
+        else:
+            self._searcher = OnlineSearcher(index, mb, max_exclude)
         self.lock = self._searcher.lock
         self._seen_ids = None       # histories as given (set_seen)
         self._seen = None           # their device CSR of positions: (offsets, items)
@@ -301,6 +319,12 @@ class OnlineRecommender:
             raise ValueError(f"expected features [nq, {self.input_dim}], got {tuple(t.shape)}")
         return t, None
 
+    def _searched(self):
+        """The index the searcher has to be over: the index itself, or the inner Flat
+        index of an IVF index that fell back to Flat."""
+        flat = getattr(self.index, "_flat", None)
+        return self.index if flat is None else flat
+
     def _run(self, x: Optional[Rows], ids: Optional[np.ndarray], k: int, items: bool = False, seen: bool = False):
         """Stage the rows, run / replay the chain, synchronise. Under ``lock``."""
         by_ids = ids is not None
@@ -314,6 +338,9 @@ class OnlineRecommender:
         stream = torch.cuda.current_stream(self._d_x.device)
         # without exclusions the keys (and graphs) of a recommender that has none
         key = (nq, k, by_ids, items, seen) if (items or seen) else (nq, k, by_ids)
+        nprobe = getattr(self._searcher, "_nprobe", 0)   # OnlineIVFSearcher: read from the index at this call
+        if k and nprobe:
+            key = (nq, k, by_ids, items, seen, nprobe)
         if os.environ.get("RTREC_ONLINE_GRAPH", "1") == "0":
             self._sequence(nq, k, by_ids, items, seen)
         else:
@@ -397,6 +424,9 @@ class OnlineRecommender:
                         for q, u in enumerate(ids):
                             excl[q].extend(self._history(int(u)))
                 return idx.search(self._embed_any(x, ids), k, filter_ids, exclude_ids=excl)
+            if s.index is not self._searched():
+                raise ValueError("the index switched between its lists and the Flat fallback (or was rebuilt "
+                                 "onto another inner index) since this recommender was made: make a new one")
             if s._revalidate():  # the corpus rows moved or grew: the search graphs hold stale pointers
                 for key in [key for key in self._graphs if key[1]]:
                     del self._graphs[key]

@@ -1162,7 +1162,9 @@ class HipIVFFlatIndex(_HbmIndex):
     probed per search); ``storage_dtype``, ``device``; ``train_iters`` (10);
     ``max_points_per_centroid`` (256: training subsamples to that many rows per
     list); ``seed`` (1234); ``online_max_batch`` (as :class:`HipFlatIPIndex`:
-    small calls go through the resident :class:`OnlineIVFSearcher`).
+    small calls go through the resident :class:`OnlineIVFSearcher`, with
+    ``exclude_ids`` too: its scan reads the lists, ``rt_ivf_topk_lists``; measured
+    0.14-0.25 ms against 0.21-0.31 ms through a bitmap at 1M rows).
     ``mutable: True`` raises; ``update`` and ``remove`` only warn, as the
     reference's do. k <= 128 per search (2k <= 128 with ``filter_ids``).
 
@@ -1178,6 +1180,8 @@ class HipIVFFlatIndex(_HbmIndex):
     1.5-2M rows for single float16 queries; below that ``HipFlatIPIndex`` with
     ``online_max_batch`` is as fast and exact.
     """
+
+    _searcher_takes_exclude = True   # OnlineIVFSearcher: rt_ivf_topk_lists
 
     def __init__(self, config: Optional[Dict[str, Any]] = None):
         super().__init__(dict(config or {}))
@@ -1295,10 +1299,11 @@ class HipIVFFlatIndex(_HbmIndex):
     def online_searcher(self, max_batch: int = 8, max_exclude: int = 8192) -> "OnlineSearcher":
         """The resident searcher for calls of at most ``max_batch`` (1..8) queries and
         k <= 128: an :class:`OnlineIVFSearcher` (the Flat fallback: an
-        :class:`OnlineSearcher` over the inner Flat index)."""
+        :class:`OnlineSearcher` over the inner Flat index); ``max_exclude``: the
+        exclusion-list entries one call may carry through its resident buffers."""
         if self._flat is not None:
             return self._flat.online_searcher(max_batch, max_exclude)
-        return OnlineIVFSearcher(self, max_batch)
+        return OnlineIVFSearcher(self, max_batch, max_exclude)
 
     def _n_probe(self, nprobe: Optional[int] = None) -> int:
         np_ = min(int(self.nprobe if nprobe is None else nprobe), self.nlist)
@@ -1330,8 +1335,9 @@ class HipIVFFlatIndex(_HbmIndex):
                exclude_ids=None) -> Tuple[List[List[str]], List[List[float]]]:
         """retrieval.py:141-197, as :meth:`HipFlatIPIndex.search`: the 2k over-fetch
         for ``filter_ids``, exact ``exclude_ids`` in the search (over the probed
-        lists). A call with ``exclude_ids`` takes the bitmap path: the probed-list
-        scan does not read lists (``_searcher_takes_exclude``)."""
+        lists). With ``online_max_batch`` a small call with ``exclude_ids`` stays on
+        the resident searcher, whose scan reads the lists (``rt_ivf_topk_lists``);
+        the other calls mask through a bitmap."""
         if self.index is not None and self._flat is not None:
             return self._flat.search(query_embeddings, k, filter_ids, exclude_ids=exclude_ids)
         return super().search(query_embeddings, k, filter_ids, exclude_ids=exclude_ids)
@@ -1443,15 +1449,18 @@ class OnlineIVFSearcher(OnlineSearcher):
     (nq, k, nprobe): ``index.nprobe`` is read at every call. Generation
     invalidation as the base class (``build`` / ``add`` / ``load``).
 
-    Exclusion lists are not read by the probed-list scan yet: a call with
-    ``exclude`` takes the bitmap path through ``search_tensors`` and returns
-    fresh arrays, as the base class's oversize-list fallback does."""
+    Exclusion lists (``search(q, k, exclude=...)``) are staged and uploaded as in
+    the base class and read by the probed-list scan (``rt_ivf_topk_lists``: a
+    membership test per candidate row, in ORIGINAL positions): graphs with
+    lists are keyed (nq, k, nprobe, True), one for every list length up to
+    ``max_exclude`` entries per call. A call with more takes the bitmap path
+    through ``search_tensors`` and returns fresh arrays, as in the base class."""
 
-    def __init__(self, index: "HipIVFFlatIndex", max_batch: int = 8):
+    def __init__(self, index: "HipIVFFlatIndex", max_batch: int = 8, max_exclude: int = 8192):
         if not isinstance(index, HipIVFFlatIndex) or index._flat is not None or index.index is None:
             raise ValueError("OnlineIVFSearcher serves a built HipIVFFlatIndex that holds lists "
                              "(a small corpus falls back to Flat: index.online_searcher() returns its searcher)")
-        super().__init__(index, max_batch, 0)
+        super().__init__(index, max_batch, max_exclude)
         dev, mb = index._dev(), self.max_batch
         # workspace sizing: both searches write [mb][<= 128][<= 512 lists] 8-byte keys at most —
         # the base class's bound; the coarse search gets a workspace of its own
@@ -1461,11 +1470,8 @@ class OnlineIVFSearcher(OnlineSearcher):
         self._nprobe = 0
         self._lists = None
 
-    def _stage_lists(self, nq: int, exclude) -> bool:
-        return False   # every call with lists: the bitmap path
-
     def _graph_key(self, nq: int, k: int, lists: bool) -> tuple:
-        return (nq, k, self._nprobe)
+        return (nq, k, self._nprobe, True) if lists else (nq, k, self._nprobe)
 
     def _revalidate(self) -> bool:
         idx = self.index
@@ -1482,6 +1488,9 @@ class OnlineIVFSearcher(OnlineSearcher):
         return True
 
     def _device_chain(self, nq: int, k: int, sources=None):
+        """As the base class's, over the lists: ``l2_renorm`` (cosine) -> coarse search
+        -> storage-dtype cast -> ``rt_ivf_topk`` (``sources``: ``rt_ivf_topk_lists`` with
+        these exclusion sources, positions in ORIGINAL order)."""
         n, np_ = nq * k, self._nprobe
         offsets, row_pos, centroids, max_list_rows = self._lists
         q32 = self._d_q32[:nq]
@@ -1494,7 +1503,8 @@ class OnlineIVFSearcher(OnlineSearcher):
         if q.data_ptr() != q32.data_ptr():
             q.copy_(q32)
         kernels.ivf_topk(q, self._rows, offsets, row_pos, probes, max_list_rows, k,
-                         out=(self._d_s[:n].view(nq, k), self._d_p[:n].view(nq, k)), workspace_buf=self._ws)
+                         out=(self._d_s[:n].view(nq, k), self._d_p[:n].view(nq, k)), workspace_buf=self._ws,
+                         exclude_lists=sources or None)
 
 
 # Backwards-compatible name: configs with index_type "faiss" get the exact

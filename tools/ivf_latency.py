@@ -15,6 +15,22 @@ against the Flat result on the same queries. The build time of each index is
 reported once. ``--chunk-tiles`` adds the scan alone at other chunk floors
 (rt_ivf_topk_tuning) — the measurement behind the plan's rule.
 
+``--legs exclude`` (not in the default list): exclusion lists on the resident
+IVF search, on the model of ``tools/serve_latency.py --legs exclude``. nprobe =
+20, nq in {1, 8}, 166 random positions per query (MovieLens-1M's mean
+history) and one case of 8,192 entries per call. Three sides alternate call by
+call, 3 rounds with each side first in turn, every side ending in host arrays:
+  none    the resident IVF search without exclusion;
+  lists   the resident IVF search with ``exclude=`` (the scan reads the lists);
+  bitmap  what a build whose scan does not read lists offers: the lists to the
+          device, rt_exclusion_bitmap into a resident bitmap,
+          ``search_tensors(exclude_bits=...)``, the result to the host — a path
+          this change leaves as it was, run in the same process.
+The bar: the p50 of ``lists`` in every round is below the MINIMUM p50 of
+``bitmap`` over its rounds. ``lists`` - ``none`` is reported per round (no bar),
+and the scan launch alone (hipEvent pairs) without exclusion, with lists and
+with the bitmap.
+
 Prints one JSON line per case and a closing summary line; run it under a time
 limit, e.g. ``timeout 900 python tools/ivf_latency.py > profiles/ivf_latency.txt``.
 """
@@ -88,6 +104,90 @@ def recall(got, want):
     return float(np.mean([len(set(g[g >= 0]) & set(w[w >= 0])) / max(1, (w >= 0).sum()) for g, w in zip(got, want)]))
 
 
+def leg_exclude(args, storage, ivf, queries, dev):
+    """The exclude leg for one built index: one JSON line per (nq, entries per call)."""
+    from rtrec_amd.serving.retrieval import _sorted_positions
+    n, k, nprobe = ivf.current_size, args.k, args.exclude_nprobe
+    ivf.nprobe = nprobe
+    s = ivf.online_searcher(8)
+    words = (n + 31) // 32
+    rng = np.random.default_rng(3)
+    cases = []
+    for nq in [int(x) for x in args.nq.split(",")]:
+        for per_q, what in ((166, "166_per_query"), (8192 // nq, "8192_per_call")):
+            pool = [rng.choice(n, size=min(per_q, n), replace=False) for _ in range(len(queries))]
+            bits = torch.zeros((nq, words), dtype=torch.int32, device=dev)
+            state = {"i": 0}
+
+            def request():
+                state["i"] += 1
+                o = (state["i"] * nq) % (len(queries) - nq)
+                return queries[o:o + nq], pool[o:o + nq]
+
+            def none():
+                q, _ = request()
+                sc, pos = s.search(q, k)
+                return sc.copy(), pos.copy()
+
+            def lists():
+                q, ex = request()
+                sc, pos = s.search(q, k, exclude=ex)
+                return sc.copy(), pos.copy()
+
+            def csr(ex):
+                ex = [_sorted_positions(e, n) for e in ex]
+                off = np.zeros(nq + 1, np.int64)
+                np.cumsum([len(e) for e in ex], out=off[1:])
+                return torch.from_numpy(off).to(dev), torch.from_numpy(np.concatenate(ex)).to(dev)
+
+            def bitmap():
+                q, ex = request()
+                d_off, d_it = csr(ex)
+                kernels.exclusion_bitmap_csr(d_off, d_it, n, out=bits)
+                sc, pos = ivf.search_tensors(q, k, exclude_bits=bits)
+                return sc.cpu().numpy(), pos.cpu().numpy()
+
+            got = lists()
+            state["i"] -= 1   # the same request again
+            want = bitmap()
+            agree = bool(np.array_equal(got[1], want[1]) and
+                         np.array_equal(got[0].view(np.uint32), want[0].view(np.uint32)))
+            if not agree:
+                raise SystemExit(f"exclude leg {storage} nq={nq} {what}: the list side and the bitmap side differ")
+            resident = (nq, k, nprobe, True) in s._graphs
+            sides = {"none": none, "lists": lists, "bitmap": bitmap}
+            names, rounds = list(sides), []
+            for r in range(3):
+                order = names[r:] + names[:r]
+                res = timed_alternating({name: sides[name] for name in order}, args.calls, args.warmup)
+                rounds.append({"first": order[0], **res})
+            floor = min(r["bitmap"]["p50_ms"] for r in rounds)
+            # the scan launch alone, on prepared device operands
+            q32 = torch.nn.functional.normalize(torch.from_numpy(np.ascontiguousarray(queries[:nq])).to(dev), dim=1)
+            qs = q32.to(ivf.storage_dtype)
+            _, probes = kernels.flatip_topk_online(q32, ivf.centroids, nprobe)
+            d_off, d_it = csr(pool[:nq])
+            kernels.exclusion_bitmap_csr(d_off, d_it, n, out=bits)
+            scan = lambda **kw: kernels.ivf_topk(qs, ivf.index, ivf.list_offsets, ivf.row_pos, probes,  # noqa: E731
+                                                 ivf.max_list_rows, k, **kw)
+            a, b = scan(exclude_lists=(d_off, d_it)), scan(exclude_bits=bits)
+            if not (torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])):
+                raise SystemExit(f"exclude leg {storage} nq={nq} {what}: lists and bitmap differ in the scan")
+            ev = event_timed({"scan_none": scan, "scan_lists": lambda: scan(exclude_lists=(d_off, d_it)),
+                              "scan_bitmap": lambda: scan(exclude_bits=bits)}, min(args.calls, 300), 10)
+            case = {"leg": "exclude", "storage": storage, "nq": nq, "nprobe": nprobe, "entries": what,
+                    "entries_per_query": per_q, "lists_resident": resident, "sides_agree": agree, "rounds": rounds,
+                    "bar": {"bitmap_min_p50_ms": floor, "lists_p50_ms": [r["lists"]["p50_ms"] for r in rounds],
+                            "none_p50_ms": [r["none"]["p50_ms"] for r in rounds],
+                            "lists_minus_none_p50_ms": [round(r["lists"]["p50_ms"] - r["none"]["p50_ms"], 5)
+                                                        for r in rounds],
+                            "lower_in_every_round": all(r["lists"]["p50_ms"] < floor for r in rounds)},
+                    "scan_event_p50_ms": ev}
+            print(json.dumps(case), flush=True)
+            cases.append({"storage": storage, "nq": nq, "entries": what, **case["bar"]})
+    return cases
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=1_000_000)
@@ -101,13 +201,26 @@ def main():
     ap.add_argument("--nq", default="1,8")
     ap.add_argument("--chunk-tiles", default="", help="comma list of chunk floors (256-row tiles) for the scan alone")
     ap.add_argument("--train-iters", type=int, default=10)
+    ap.add_argument("--legs", default="search", help="comma list of: search (the default), exclude")
+    ap.add_argument("--exclude-nprobe", type=int, default=20)
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     n, d, k = args.rows, args.dim, args.k
     rows, queries = corpus(n, d, 4096, 64, dev)
     ids = []   # positions only: the id maps are not what is measured
     summary = {"rows": n, "dim": d, "k": k, "nlist": args.nlist, "cases": []}
+    legs = args.legs.split(",")
+    if set(legs) - {"search", "exclude"}:
+        raise SystemExit(f"unknown leg in {args.legs!r}")
     for storage in args.storage.split(","):
+        if "search" not in legs:
+            ivf = HipIVFFlatIndex({"dimension": d, "metric": "cosine", "storage_dtype": storage, "nprobe": 20,
+                                   "index_factory": f"IVF{args.nlist},Flat", "train_iters": args.train_iters})
+            ivf.build(rows, ids)
+            summary.setdefault("exclude", []).extend(leg_exclude(args, storage, ivf, queries, dev))
+            del ivf
+            torch.cuda.empty_cache()
+            continue
         flat = HipFlatIPIndex({"dimension": d, "metric": "cosine", "storage_dtype": storage})
         t0 = time.perf_counter()
         flat.build(rows, ids)
@@ -168,6 +281,8 @@ def main():
                 print(json.dumps(case), flush=True)
                 summary["cases"].append({key: case[key] for key in ("storage", "nq", "nprobe", "ivf_over_flat_p50",
                                                                      f"recall_at_{k}")})
+        if "exclude" in legs:
+            summary.setdefault("exclude", []).extend(leg_exclude(args, storage, ivf, queries, dev))
         del s_flat, s_ivf, flat, ivf
         torch.cuda.empty_cache()
     print(json.dumps(summary), flush=True)
