@@ -257,6 +257,20 @@ int rt_flatip_topk_online_lists(const void* queries, int64_t nq, const void* ite
  *   NULL with n_lists > 0, a source with offsets == NULL, n_rows < 0, or items
  *   == NULL with n_rows > 0; RT_ERR_UNSUPPORTED for n_lists >
  *   RT_ONLINE_MAX_EXCL_SOURCES; then every refusal of rt_ivf_topk.
+ * rt_ivf_topk_lens, rt_ivf_topk_lists_lens: rt_ivf_topk and rt_ivf_topk_lists
+ *   over lists stored with slack (rt_ivf_lists_update below), with two more
+ *   operands. list_len (int64 [nlist], device, not NULL): list l is the stored
+ *   rows [off[l], off[l] + min(max(list_len[l], 0), off[l + 1] - off[l])),
+ *   clamped to [0, nx) as before. n_pos (host): positions are valid in
+ *   [0, n_pos) — a row whose row_pos is outside it (the -1 of an empty slot) is
+ *   dropped; exclude_words >= ceil(n_pos / 32); exclusion items >= n_pos are
+ *   ignored; n_pos < 2^31 - 1. nx is the number of stored rows (the total
+ *   capacity) and max_list_rows an upper bound of the largest CAPACITY: the
+ *   grid depends on host arguments only, so a captured call stays valid while
+ *   lists change in place. The same scan and finish: results, score bits,
+ *   workspace, plan and refusals are those of the entry point without _lens
+ *   (plus RT_ERR_INVALID for list_len == NULL or n_pos < 0, RT_ERR_UNSUPPORTED
+ *   for n_pos >= 2^31 - 1).
  * rt_ivf_topk_plan: host only. out = {chunks per list, rows per chunk, scan
  *   blocks}: a probed list is scanned by `chunks` blocks of `rows per chunk`
  *   rows (a multiple of 256; chunks x rows >= max_list_rows), blocks = nq x
@@ -296,8 +310,70 @@ int rt_ivf_topk_lists(const void* queries, int64_t nq, const void* rows, int64_t
                       const int64_t* list_offsets, int64_t nlist, const int32_t* row_pos, const int64_t* probes,
                       int nprobe, int64_t max_list_rows, int k, const RtExclusionLists* lists, int n_lists,
                       float* out_scores, int64_t* out_ids, void* workspace, size_t workspace_bytes, void* stream);
+int rt_ivf_topk_lens(const void* queries, int64_t nq, const void* rows, int64_t nx, int d, int dtype,
+                     const int64_t* list_offsets, int64_t nlist, const int64_t* list_len, int64_t n_pos,
+                     const int32_t* row_pos, const int64_t* probes, int nprobe, int64_t max_list_rows, int k,
+                     const uint32_t* exclude_bits, int64_t exclude_words, float* out_scores, int64_t* out_ids,
+                     void* workspace, size_t workspace_bytes, void* stream);
+int rt_ivf_topk_lists_lens(const void* queries, int64_t nq, const void* rows, int64_t nx, int d, int dtype,
+                           const int64_t* list_offsets, int64_t nlist, const int64_t* list_len, int64_t n_pos,
+                           const int32_t* row_pos, const int64_t* probes, int nprobe, int64_t max_list_rows, int k,
+                           const RtExclusionLists* lists, int n_lists, float* out_scores, int64_t* out_ids,
+                           void* workspace, size_t workspace_bytes, void* stream);
 int rt_segment_mean_f32(const void* rows, int64_t n, int d, int dtype, const int64_t* offsets, int64_t n_seg,
                         const float* prev, int normalize, float* out, void* stream);
+
+/* ------------------------------------------------------------------------
+ * In-place mutation of IVF lists stored with slack: the streaming item_update
+ * path (RetrievalEngine.update_index, src/serving/retrieval.py:228-246,
+ * 629-641) on the reference's default index.
+ *
+ * State (all device): rows [total_rows, d] of `dtype`, 16-byte aligned;
+ *   list_offsets int64 [nlist + 1]: list l OWNS the stored rows
+ *   [list_offsets[l], list_offsets[l + 1]) — its capacity; list_len int64
+ *   [nlist]: its live rows are the first list_len[l] of them; row_pos int32
+ *   [total_rows]: the position of a stored row, -1 in every slot at or past
+ *   list_len[l]; pos_slot int32 [total_rows]: the stored row of a position
+ *   (-1: none); assign int64 [total_rows]: the list of a position (-1: none).
+ *   Positions live in [0, total_rows).
+ * rt_ivf_lists_update: one stream-ordered call (a memset of `status` and
+ *   three launches; no host read, capturable) for m operations. positions
+ *   int64 [m], UNIQUE (the caller's contract, as for rt_scatter_rows);
+ *   new_list int64 [m]: what rt_flatip_topk with k = 1 writes over the
+ *   centroids, or -1 = the position's row leaves; new_rows [m, d] of `dtype`,
+ *   16-byte aligned (read for new_list >= 0 only). Per operation: a position
+ *   whose current list equals new_list has its row overwritten where it lies;
+ *   otherwise it leaves its current list (if it has a row) and joins new_list
+ *   (if >= 0). After the call every touched list holds its old live rows minus
+ *   the leavers plus the joiners in its first list_len[l] slots, row_pos = -1
+ *   behind them, and pos_slot / row_pos / assign agree.
+ *   Placement rule (the same state and batch give the same bytes): per list,
+ *   holes = the slots of its leavers in ascending slot order, joiners in
+ *   ascending operation order; joiner j takes hole j; surplus joiners append
+ *   at the old length; surplus holes below the new length take the surviving
+ *   rows at or past the new length, both in ascending slot order. One
+ *   workgroup owns a list; rows move as 16-byte vectors.
+ *   status int32 [2] (device, written by the call): all or nothing —
+ *   status[0] = the number of lists whose new length would exceed their
+ *   capacity, status[1] = the number of refused operations (a position outside
+ *   [0, total_rows), a new_list outside [-1, nlist), a position whose pos_slot /
+ *   assign / row_pos entries do not name each other). If either is non-zero
+ *   NOTHING else is written. The caller reads the pair afterwards (8 bytes).
+ *   Positions that are not unique: unspecified list contents, nothing is
+ *   written outside the state buffers.
+ *   Status, before any device work: RT_ERR_INVALID for negative sizes, nlist <=
+ *   0, d <= 0, an unknown dtype, misaligned rows / new_rows / workspace (4
+ *   bytes), then (m > 0) any NULL operand; RT_ERR_UNSUPPORTED for a refused
+ *   d / dtype pair (those of rt_ivf_topk), total_rows, m or nlist >= 2^31 - 1;
+ *   RT_ERR_WORKSPACE. m == 0: RT_OK without a launch.
+ * rt_ivf_lists_update_workspace_bytes: 4 x (5 m + 3 nlist) bytes rounded up to
+ *   256 (negative arguments count as 0); monotone in both.
+ * ------------------------------------------------------------------------ */
+size_t rt_ivf_lists_update_workspace_bytes(int64_t nlist, int64_t m);
+int rt_ivf_lists_update(void* rows, int64_t total_rows, int d, int dtype, const int64_t* list_offsets,
+                        int64_t nlist, int64_t* list_len, int32_t* row_pos, int32_t* pos_slot, int64_t* assign,
+                        const int64_t* positions, const int64_t* new_list, const void* new_rows, int64_t m,
+                        int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Corpus-sharded search with ONE corpus-wide threshold per query (several
  * GPUs, each holding a row shard of the corpus that faiss.IndexFlatIP.search

@@ -37,6 +37,14 @@
 // once, in its prologue, and copies them into LDS when together they fit
 // kListCap entries (else the search reads `items` in global memory): one
 // search routine over a generic pointer serves both.
+//
+// rt_ivf_topk_lens / rt_ivf_topk_lists_lens: the same kernels over lists stored
+// with slack (ivf_mutate.hip). Two more operands: list_len (the live rows of a
+// list are the first list_len[l] of its capacity) and n_pos (positions are valid
+// in [0, n_pos), where the other two entry points use nx). The grid is sized by
+// the largest CAPACITY, a host argument, so a captured call sees lists that
+// changed in place. The other two entry points pass list_len = nullptr and
+// n_pos = nx: the window and the range test they had.
 #include "topk_online.h"
 
 namespace rt {
@@ -119,8 +127,9 @@ __device__ __forceinline__ bool list_has(const int32_t* items, int64_t lo, int64
 template <typename T, bool LISTS>
 __global__ __launch_bounds__(on::kThreads, 2) void ivf_scan(
     const T* __restrict__ Q, const char* __restrict__ X, int64_t nx, int d, int k,
-    const int64_t* __restrict__ list_offsets, int64_t nlist, const int32_t* __restrict__ row_pos,
-    const int64_t* __restrict__ probes, int nprobe, int chunks, int64_t rows_per_chunk,
+    const int64_t* __restrict__ list_offsets, int64_t nlist, const int64_t* __restrict__ list_len, int64_t n_pos,
+    const int32_t* __restrict__ row_pos, const int64_t* __restrict__ probes, int nprobe, int chunks,
+    int64_t rows_per_chunk,
     const uint32_t* __restrict__ excl, int64_t excl_words, uint64_t* __restrict__ partials,
     const on::ListArgs<LISTS> la) {
     constexpr int EPU = 16 / static_cast<int>(sizeof(T));
@@ -144,6 +153,10 @@ __global__ __launch_bounds__(on::kThreads, 2) void ivf_scan(
         int64_t lo = list_offsets[l], hi = list_offsets[l + 1];
         lo = lo < 0 ? 0 : lo;
         hi = hi > nx ? nx : hi;
+        if (list_len && lo < hi) {  // lists with slack: the first list_len[l] rows of the capacity
+            const int64_t live = list_len[l];
+            hi = live <= 0 ? lo : (live < hi - lo ? lo + live : hi);
+        }
         if (lo < hi) {
             const int64_t len = hi - lo, first = static_cast<int64_t>(c) * rows_per_chunk;
             if (first < len) {
@@ -233,9 +246,9 @@ __global__ __launch_bounds__(on::kThreads, 2) void ivf_scan(
         on::score_tile<T, 1>(R, w, t, stage, qs, d, acc);
 
         // ---- selection: at most one append per row ----
-        // a position outside [0, nx) (a corrupt row_pos) is dropped: it has no bit in
-        // the bitmap and no row in the caller's corpus
-        bool pass = pos >= 0 && static_cast<int64_t>(pos) < nx && acc[0] >= th;
+        // a position outside [0, n_pos) (a corrupt row_pos, an empty slot of a list with
+        // slack) is dropped: it has no bit in the bitmap and no row in the caller's corpus
+        bool pass = pos >= 0 && static_cast<int64_t>(pos) < n_pos && acc[0] >= th;
         if constexpr (LISTS) {
             if (__any(pass)) {  // wave-uniform
 #pragma unroll
@@ -347,22 +360,26 @@ extern "C" size_t rt_ivf_topk_workspace_bytes(int64_t nq, int nprobe, int64_t ma
     return need < 256 ? 256 : need;
 }
 
-// both entry points: the dense bitmap (la == nullptr) or the lists
+// the four entry points: the dense bitmap (la == nullptr) or the lists; list_len ==
+// nullptr and n_pos == nx (rt_ivf_topk, rt_ivf_topk_lists) or the lists with slack
 static int ivf_search(const void* queries, int64_t nq, const void* rows, int64_t nx, int d, int dtype,
-                      const int64_t* list_offsets, int64_t nlist, const int32_t* row_pos, const int64_t* probes,
+                      const int64_t* list_offsets, int64_t nlist, const int64_t* list_len, int64_t n_pos,
+                      const int32_t* row_pos, const int64_t* probes,
                       int nprobe, int64_t max_list_rows, int k, const uint32_t* exclude_bits, int64_t exclude_words,
                       const ivon::ListArgs<true>* la, float* out_scores, int64_t* out_ids, void* workspace,
                       size_t workspace_bytes, void* stream) {
-    if (nq < 0 || nx < 0 || d <= 0 || k <= 0 || nlist <= 0 || nprobe <= 0 || max_list_rows < 0) return RT_ERR_INVALID;
+    if (nq < 0 || nx < 0 || d <= 0 || k <= 0 || nlist <= 0 || nprobe <= 0 || max_list_rows < 0 || n_pos < 0)
+        return RT_ERR_INVALID;
     if (nq == 0) return RT_OK;
     if (!queries || !out_scores || !out_ids || !list_offsets || !probes || (nx > 0 && (!rows || !row_pos)))
         return RT_ERR_INVALID;
     if (k > ivon::kMaxK || nprobe > iv::kMaxProbe || nq > iv::kMaxNq) return RT_ERR_UNSUPPORTED;
     if (dtype != RT_F32 && dtype != RT_F16 && dtype != RT_BF16) return RT_ERR_INVALID;
     if (!ivon::shape_ok(d, dtype)) return RT_ERR_UNSUPPORTED;
-    if (nx >= 0x7FFFFFFFll || max_list_rows >= 0xFFFFFFFFll) return RT_ERR_UNSUPPORTED;  // positions are int32
+    if (nx >= 0x7FFFFFFFll || n_pos >= 0x7FFFFFFFll || max_list_rows >= 0xFFFFFFFFll)
+        return RT_ERR_UNSUPPORTED;  // positions are int32
     if ((reinterpret_cast<uintptr_t>(queries) | reinterpret_cast<uintptr_t>(rows)) & 15) return RT_ERR_INVALID;
-    if (exclude_bits && exclude_words < (nx + 31) / 32) return RT_ERR_INVALID;
+    if (exclude_bits && exclude_words < (n_pos + 31) / 32) return RT_ERR_INVALID;
     if (!workspace || workspace_bytes < rt_ivf_topk_workspace_bytes(nq, nprobe, max_list_rows, k))
         return RT_ERR_WORKSPACE;
     if (reinterpret_cast<uintptr_t>(workspace) & 7) return RT_ERR_INVALID;
@@ -374,8 +391,8 @@ static int ivf_search(const void* queries, int64_t nq, const void* rows, int64_t
     const char* x = static_cast<const char*>(rows);
 #define RT_IVF_LAUNCH(T, LISTS, LA)                                                                             \
     hipLaunchKernelGGL((iv::ivf_scan<T, LISTS>), grid, block, 0, st, static_cast<const T*>(queries), x, nx, d, k, \
-                       list_offsets, nlist, row_pos, probes, nprobe, p.chunks, p.rows_per_chunk, exclude_bits,     \
-                       exclude_words, partials, LA)
+                       list_offsets, nlist, list_len, n_pos, row_pos, probes, nprobe, p.chunks, p.rows_per_chunk, \
+                       exclude_bits, exclude_words, partials, LA)
     if (la) {
         switch (dtype) {
             case RT_F32: RT_IVF_LAUNCH(float, true, *la); break;
@@ -401,15 +418,27 @@ extern "C" int rt_ivf_topk(const void* queries, int64_t nq, const void* rows, in
                            const int64_t* probes, int nprobe, int64_t max_list_rows, int k,
                            const uint32_t* exclude_bits, int64_t exclude_words, float* out_scores,
                            int64_t* out_ids, void* workspace, size_t workspace_bytes, void* stream) {
-    return ivf_search(queries, nq, rows, nx, d, dtype, list_offsets, nlist, row_pos, probes, nprobe, max_list_rows, k,
-                      exclude_bits, exclude_words, nullptr, out_scores, out_ids, workspace, workspace_bytes, stream);
+    return ivf_search(queries, nq, rows, nx, d, dtype, list_offsets, nlist, nullptr, nx, row_pos, probes, nprobe,
+                      max_list_rows, k, exclude_bits, exclude_words, nullptr, out_scores, out_ids, workspace,
+                      workspace_bytes, stream);
 }
 
-extern "C" int rt_ivf_topk_lists(const void* queries, int64_t nq, const void* rows, int64_t nx, int d, int dtype,
-                                 const int64_t* list_offsets, int64_t nlist, const int32_t* row_pos,
-                                 const int64_t* probes, int nprobe, int64_t max_list_rows, int k,
-                                 const RtExclusionLists* lists, int n_lists, float* out_scores, int64_t* out_ids,
-                                 void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int rt_ivf_topk_lens(const void* queries, int64_t nq, const void* rows, int64_t nx, int d, int dtype,
+                                const int64_t* list_offsets, int64_t nlist, const int64_t* list_len, int64_t n_pos,
+                                const int32_t* row_pos, const int64_t* probes, int nprobe, int64_t max_list_rows,
+                                int k, const uint32_t* exclude_bits, int64_t exclude_words, float* out_scores,
+                                int64_t* out_ids, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!list_len && nq > 0) return RT_ERR_INVALID;
+    return ivf_search(queries, nq, rows, nx, d, dtype, list_offsets, nlist, list_len, n_pos, row_pos, probes, nprobe,
+                      max_list_rows, k, exclude_bits, exclude_words, nullptr, out_scores, out_ids, workspace,
+                      workspace_bytes, stream);
+}
+
+static int ivf_search_lists(const void* queries, int64_t nq, const void* rows, int64_t nx, int d, int dtype,
+                            const int64_t* list_offsets, int64_t nlist, const int64_t* list_len, int64_t n_pos,
+                            const int32_t* row_pos, const int64_t* probes, int nprobe, int64_t max_list_rows, int k,
+                            const RtExclusionLists* lists, int n_lists, float* out_scores, int64_t* out_ids,
+                            void* workspace, size_t workspace_bytes, void* stream) {
     if (n_lists < 0 || (n_lists > 0 && !lists)) return RT_ERR_INVALID;
     if (n_lists > RT_ONLINE_MAX_EXCL_SOURCES) return RT_ERR_UNSUPPORTED;
     ivon::ListArgs<true> la{};
@@ -420,8 +449,30 @@ extern "C" int rt_ivf_topk_lists(const void* queries, int64_t nq, const void* ro
         la.src[s] = ivon::ListSrc{L.offsets, L.items, L.rows, L.n_rows};
     }
     // no source: the plain scan, bit for bit rt_ivf_topk without a bitmap
-    return ivf_search(queries, nq, rows, nx, d, dtype, list_offsets, nlist, row_pos, probes, nprobe, max_list_rows, k,
-                      nullptr, 0, n_lists ? &la : nullptr, out_scores, out_ids, workspace, workspace_bytes, stream);
+    return ivf_search(queries, nq, rows, nx, d, dtype, list_offsets, nlist, list_len, n_pos, row_pos, probes, nprobe,
+                      max_list_rows, k, nullptr, 0, n_lists ? &la : nullptr, out_scores, out_ids, workspace,
+                      workspace_bytes, stream);
+}
+
+extern "C" int rt_ivf_topk_lists(const void* queries, int64_t nq, const void* rows, int64_t nx, int d, int dtype,
+                                 const int64_t* list_offsets, int64_t nlist, const int32_t* row_pos,
+                                 const int64_t* probes, int nprobe, int64_t max_list_rows, int k,
+                                 const RtExclusionLists* lists, int n_lists, float* out_scores, int64_t* out_ids,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+    return ivf_search_lists(queries, nq, rows, nx, d, dtype, list_offsets, nlist, nullptr, nx, row_pos, probes, nprobe,
+                            max_list_rows, k, lists, n_lists, out_scores, out_ids, workspace, workspace_bytes, stream);
+}
+
+extern "C" int rt_ivf_topk_lists_lens(const void* queries, int64_t nq, const void* rows, int64_t nx, int d, int dtype,
+                                      const int64_t* list_offsets, int64_t nlist, const int64_t* list_len,
+                                      int64_t n_pos, const int32_t* row_pos, const int64_t* probes, int nprobe,
+                                      int64_t max_list_rows, int k, const RtExclusionLists* lists, int n_lists,
+                                      float* out_scores, int64_t* out_ids, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+    if (!list_len && nq > 0) return RT_ERR_INVALID;
+    return ivf_search_lists(queries, nq, rows, nx, d, dtype, list_offsets, nlist, list_len, n_pos, row_pos, probes,
+                            nprobe, max_list_rows, k, lists, n_lists, out_scores, out_ids, workspace, workspace_bytes,
+                            stream);
 }
 
 extern "C" int rt_segment_mean_f32(const void* rows, int64_t n, int d, int dtype, const int64_t* offsets,

@@ -552,7 +552,8 @@ def ivf_topk(queries: torch.Tensor, rows: torch.Tensor, list_offsets: torch.Tens
              probes: torch.Tensor, max_list_rows: int, k: int, exclude_bits: Optional[torch.Tensor] = None,
              out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
              workspace_buf: Optional[torch.Tensor] = None,
-             exclude_lists=None) -> Tuple[torch.Tensor, torch.Tensor]:
+             exclude_lists=None, list_len: Optional[torch.Tensor] = None,
+             n_pos: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Top-k over the union of the probed lists (rt_ivf_topk): (scores [nq, k] f32,
     original positions [nq, k] int64) in (score desc, position asc) order,
     (-FLT_MAX, -1) pads. ``rows`` [nx, d] are stored list-contiguous, list l =
@@ -562,11 +563,16 @@ def ivf_topk(queries: torch.Tensor, rows: torch.Tensor, list_offsets: torch.Tens
     ``exclude_lists`` (rt_ivf_topk_lists; not together with ``exclude_bits``):
     the forms of :func:`flatip_topk_online`'s — one or two ``(offsets, items[,
     rows])`` CSR sources of ORIGINAL positions that the scan reads itself.
+    ``list_len`` (int64 [nlist]) with ``n_pos``: lists stored with slack
+    (rt_ivf_topk_lens / rt_ivf_topk_lists_lens) — list l's live rows are the first
+    ``list_len[l]`` of its ``[list_offsets[l], list_offsets[l + 1])``, positions
+    are valid in ``[0, n_pos)`` (the bitmap's width), ``max_list_rows`` bounds the
+    largest capacity.
     Batches above 32,768 queries run in chunks."""
     if exclude_lists is not None and exclude_bits is not None:
         raise ValueError("exclude_bits and exclude_lists are mutually exclusive")
     sources = _exclusion_sources(exclude_lists, queries)
-    native.require_device(queries, rows, list_offsets, row_pos, probes, exclude_bits, what="ivf_topk")
+    native.require_device(queries, rows, list_offsets, row_pos, probes, exclude_bits, list_len, what="ivf_topk")
     for src in sources:
         native.require_device(*src, what="ivf_topk")
     # a source without items excludes nothing (and has no items pointer to give)
@@ -592,6 +598,16 @@ def ivf_topk(queries: torch.Tensor, rows: torch.Tensor, list_offsets: torch.Tens
     if not 1 <= nprobe <= IVF_MAX_NPROBE:
         raise ValueError(f"nprobe={nprobe}: 1..{IVF_MAX_NPROBE}")
     nlist = list_offsets.numel() - 1
+    lens = ()   # the two operands the _lens entry points take behind nlist
+    if list_len is not None:
+        if list_len.dtype != torch.int64 or list_len.numel() != nlist or not list_len.is_contiguous():
+            raise ValueError("list_len must be contiguous int64 [nlist]")
+        if n_pos is None or not 0 <= int(n_pos):
+            raise ValueError("list_len comes with n_pos >= 0, the number of valid positions")
+        lens = (ptr(list_len), int(n_pos))
+    elif n_pos is not None:
+        raise ValueError("n_pos comes with list_len")
+    suffix = "_lens" if lens else ""
     dt = native.dtype_code(queries.dtype)
     scores, ids = _topk_out(out, nq, k, queries.device)
     words = _exclude_words(exclude_bits, nq, True)
@@ -617,16 +633,57 @@ def ivf_topk(queries: torch.Tensor, rows: torch.Tensor, list_offsets: torch.Tens
                 s = arr[n_src]
                 s.offsets, s.items, s.n_rows, s.rows = ptr(offsets), ptr(its), n_rows, ptr(xrows)
                 n_src += 1
-            call("rt_ivf_topk_lists", ptr(queries[a:b]), b - a, ptr(rows) if nx else None, nx, d, dt,
-                 ptr(list_offsets), nlist, ptr(row_pos) if nx else None, ptr(probes[a:b]), nprobe,
+            call("rt_ivf_topk_lists" + suffix, ptr(queries[a:b]), b - a, ptr(rows) if nx else None, nx, d, dt,
+                 ptr(list_offsets), nlist, *lens, ptr(row_pos) if nx else None, ptr(probes[a:b]), nprobe,
                  int(max_list_rows), k, arr, n_src, ptr(scores[a:b]), ptr(ids[a:b]), ptr(ws), ws.numel(),
                  stream_of(queries))
             continue
-        call("rt_ivf_topk", ptr(queries[a:b]), b - a, ptr(rows) if nx else None, nx, d, dt, ptr(list_offsets), nlist,
-             ptr(row_pos) if nx else None, ptr(probes[a:b]), nprobe, int(max_list_rows), k,
-             ptr(exclude_bits[a:b]) if exclude_bits is not None else None, words, ptr(scores[a:b]), ptr(ids[a:b]),
-             ptr(ws), ws.numel(), stream_of(queries))
+        call("rt_ivf_topk" + suffix, ptr(queries[a:b]), b - a, ptr(rows) if nx else None, nx, d, dt,
+             ptr(list_offsets), nlist, *lens, ptr(row_pos) if nx else None, ptr(probes[a:b]), nprobe,
+             int(max_list_rows), k, ptr(exclude_bits[a:b]) if exclude_bits is not None else None, words,
+             ptr(scores[a:b]), ptr(ids[a:b]), ptr(ws), ws.numel(), stream_of(queries))
     return scores, ids
+
+
+def ivf_lists_update(rows: torch.Tensor, list_offsets: torch.Tensor, list_len: torch.Tensor, row_pos: torch.Tensor,
+                     pos_slot: torch.Tensor, assign: torch.Tensor, positions: torch.Tensor, new_list: torch.Tensor,
+                     new_rows: torch.Tensor, status: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One batch of in-place list mutations (rt_ivf_lists_update) on lists stored
+    with slack: operation i overwrites the row of ``positions[i]`` (unique, int64)
+    where it lies when its list stays ``new_list[i]``, otherwise moves it to that
+    list, ``new_list[i] == -1`` withdrawing it; ``new_rows`` [m, d] in the dtype of
+    ``rows``. Stream-ordered, nothing is read back. Returns ``status`` (int32 [2],
+    device): all or nothing — ``status[0]`` lists that would overflow their
+    capacity, ``status[1]`` refused operations; non-zero means no state changed."""
+    native.require_device(rows, list_offsets, list_len, row_pos, pos_slot, assign, positions, new_list, new_rows,
+                          status, what="ivf_lists_update")
+    _row_bytes(rows, "ivf_lists_update")
+    total, d = rows.shape
+    m = positions.numel()
+    if new_rows.dtype != rows.dtype or new_rows.dim() != 2 or tuple(new_rows.shape) != (m, d) \
+            or not new_rows.is_contiguous():
+        raise ValueError(f"ivf_lists_update: new_rows must be contiguous {rows.dtype} [{m}, {d}]")
+    nlist = list_offsets.numel() - 1
+    for t, dt_, n, what in ((list_offsets, torch.int64, nlist + 1, "list_offsets"),
+                            (list_len, torch.int64, nlist, "list_len"),
+                            (row_pos, torch.int32, total, "row_pos"), (pos_slot, torch.int32, total, "pos_slot"),
+                            (assign, torch.int64, total, "assign"), (positions, torch.int64, m, "positions"),
+                            (new_list, torch.int64, m, "new_list")):
+        if t.dtype != dt_ or t.dim() != 1 or t.numel() != n or not t.is_contiguous():
+            raise ValueError(f"ivf_lists_update: {what} must be contiguous {dt_} [{n}]")
+    if nlist < 1:
+        raise ValueError("ivf_lists_update: list_offsets must be int64 [nlist + 1]")
+    if status is None:
+        status = torch.empty(2, dtype=torch.int32, device=rows.device)
+    elif status.dtype != torch.int32 or status.numel() != 2 or not status.is_contiguous():
+        raise ValueError("ivf_lists_update: status must be int32 [2]")
+    if m == 0:
+        return status.zero_()
+    ws = workspace(rows.device, native.lib().rt_ivf_lists_update_workspace_bytes(nlist, m), "ivf_lists_update")
+    call("rt_ivf_lists_update", ptr(rows), total, d, native.dtype_code(rows.dtype), ptr(list_offsets), nlist,
+         ptr(list_len), ptr(row_pos), ptr(pos_slot), ptr(assign), ptr(positions), ptr(new_list), ptr(new_rows), m,
+         ptr(status), ptr(ws), ws.numel(), stream_of(rows))
+    return status
 
 
 def segment_mean(rows: torch.Tensor, offsets: torch.Tensor, prev: torch.Tensor, normalize: bool = False,

@@ -135,7 +135,14 @@ SIGNATURES = {
                             vp, vp, vp, c_size, vp]),
     "rt_ivf_topk_lists": (c_int, [vp, c_i64, vp, c_i64, c_int, c_int, vp, c_i64, vp, vp, c_int, c_i64, c_int,
                                   ctypes.POINTER(ExclusionLists), c_int, vp, vp, vp, c_size, vp]),
+    "rt_ivf_topk_lens": (c_int, [vp, c_i64, vp, c_i64, c_int, c_int, vp, c_i64, vp, c_i64, vp, vp, c_int, c_i64,
+                                 c_int, vp, c_i64, vp, vp, vp, c_size, vp]),
+    "rt_ivf_topk_lists_lens": (c_int, [vp, c_i64, vp, c_i64, c_int, c_int, vp, c_i64, vp, c_i64, vp, vp, c_int,
+                                       c_i64, c_int, ctypes.POINTER(ExclusionLists), c_int, vp, vp, vp, c_size, vp]),
     "rt_segment_mean_f32": (c_int, [vp, c_i64, c_int, c_int, vp, c_i64, vp, c_int, vp, vp]),
+    "rt_ivf_lists_update_workspace_bytes": (c_size, [c_i64, c_i64]),
+    "rt_ivf_lists_update": (c_int, [vp, c_i64, c_int, c_int, vp, c_i64, vp, vp, vp, vp, vp, vp, vp, c_i64, vp, vp,
+                                    c_size, vp]),
     "rt_topk_merge": (c_int, [vp, vp, c_i64, c_int, c_int, c_int, vp, vp, vp]),
     "rt_flatip_topk_tuning": (c_int, [c_int, c_int, c_int]),
     "rt_flatip_topk_shard_workspace_bytes": (c_size, [c_i64, c_i64, c_int, c_int, c_int]),

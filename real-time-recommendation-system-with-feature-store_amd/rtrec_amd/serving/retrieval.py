@@ -1165,8 +1165,10 @@ class HipIVFFlatIndex(_HbmIndex):
     small calls go through the resident :class:`OnlineIVFSearcher`, with
     ``exclude_ids`` too: its scan reads the lists, ``rt_ivf_topk_lists``; measured
     0.14-0.25 ms against 0.21-0.31 ms through a bitmap at 1M rows).
-    ``mutable: True`` raises; ``update`` and ``remove`` only warn, as the
-    reference's do. k <= 128 per search (2k <= 128 with ``filter_ids``).
+    ``mutable: True`` raises and names :class:`HipMutableIVFFlatIndex` (index
+    type ``hip_ivf_mutable``), whose lists change in place; on this class
+    ``update`` and ``remove`` only warn, as the reference's do. k <= 128 per
+    search (2k <= 128 with ``filter_ids``).
 
     Below 1,024 items, or below nlist, ``build`` logs the reference's message
     and everything is delegated to an inner :class:`HipFlatIPIndex`.
@@ -1182,13 +1184,15 @@ class HipIVFFlatIndex(_HbmIndex):
     """
 
     _searcher_takes_exclude = True   # OnlineIVFSearcher: rt_ivf_topk_lists
+    _lists_mutable = False           # HipMutableIVFFlatIndex: lists with slack, changed in place
 
     def __init__(self, config: Optional[Dict[str, Any]] = None):
         super().__init__(dict(config or {}))
-        if self.config.get("mutable", False):
-            raise ValueError("HipIVFFlatIndex is not mutable: in-place list mutation is not built "
-                             "(HipFlatIPIndex takes mutable=True)")
-        self.mutable = False
+        if self.config.get("mutable", False) and not self._lists_mutable:
+            raise ValueError("HipIVFFlatIndex is not mutable: its lists are stored without slack; "
+                             "HipMutableIVFFlatIndex (index type 'hip_ivf_mutable') updates, adds and removes "
+                             "in place (for a Flat index: HipFlatIPIndex with mutable=True)")
+        self.mutable = self._lists_mutable
         self.index_factory = self.config.get("index_factory", _IVF_FACTORY)
         self.nlist = _parse_ivf_factory(self.index_factory)
         self.nprobe = int(self.config.get("nprobe", 20))
@@ -1215,6 +1219,14 @@ class HipIVFFlatIndex(_HbmIndex):
                if k in ("dimension", "metric", "storage_dtype", "device", "online_max_batch")}
         cfg["index_factory"] = "Flat"
         return cfg
+
+    def _scan_operands(self) -> Dict[str, Any]:
+        """What ``kernels.ivf_topk`` takes beyond the lists of this class (none)."""
+        return {}
+
+    def _live_assign(self) -> torch.Tensor:
+        """The list of every position in [0, current_size)."""
+        return self.assign
 
     def _assign_rows(self, rows: torch.Tensor, centroids: torch.Tensor) -> torch.Tensor:
         """Nearest centroid of every fp32 row by inner product, the lowest centroid
@@ -1329,7 +1341,7 @@ class HipIVFFlatIndex(_HbmIndex):
         else:
             _, probes = kernels.flatip_topk(q32, self.centroids, np_)
         return kernels.ivf_topk(q32.to(self.storage_dtype), self.index, self.list_offsets, self.row_pos, probes,
-                                self.max_list_rows, k, exclude_bits=exclude_bits)
+                                self.max_list_rows, k, exclude_bits=exclude_bits, **self._scan_operands())
 
     def search(self, query_embeddings: Array, k: int = 10, filter_ids: Optional[List[str]] = None,
                exclude_ids=None) -> Tuple[List[List[str]], List[List[float]]]:
@@ -1346,7 +1358,8 @@ class HipIVFFlatIndex(_HbmIndex):
         """retrieval.py:199-226. The new rows are assigned to the existing centroids
         (no retraining), then every list is regrouped by a stable sort of all
         assignments and one gather: O(n) per call in the size of the index, not
-        in the size of the batch — batch the additions."""
+        in the size of the batch — batch the additions
+        (:class:`HipMutableIVFFlatIndex` adds in O(batch))."""
         if self.index is None:
             raise ValueError("Index not built yet")
         if self._flat is not None:
@@ -1404,7 +1417,7 @@ class HipIVFFlatIndex(_HbmIndex):
         self._save_ids(path)
         cfg = {k: v for k, v in self.config.items() if isinstance(v, (str, int, float, bool, type(None)))}
         np.savez(path.with_suffix(".ivf.npz"), centroids=self.centroids.cpu().numpy(),
-                 assign=self.assign.cpu().numpy(), config=np.array(json.dumps(cfg)), seed=np.int64(self.seed),
+                 assign=self._live_assign().cpu().numpy(), config=np.array(json.dumps(cfg)), seed=np.int64(self.seed),
                  nlist=np.int64(self.nlist))
         logger.info("Saved index to %s", path)
 
@@ -1469,6 +1482,7 @@ class OnlineIVFSearcher(OnlineSearcher):
         self._d_probes = torch.empty(mb * kernels.IVF_MAX_NPROBE, dtype=torch.int64, device=dev)
         self._nprobe = 0
         self._lists = None
+        self._scan_operands: Dict[str, Any] = {}
 
     def _graph_key(self, nq: int, k: int, lists: bool) -> tuple:
         return (nq, k, self._nprobe, True) if lists else (nq, k, self._nprobe)
@@ -1484,13 +1498,15 @@ class OnlineIVFSearcher(OnlineSearcher):
                              "searcher was made: obtain a new one (index.online_searcher)")
         self._rows = idx.index
         self._lists = (idx.list_offsets, idx.row_pos, idx.centroids, idx.max_list_rows)
+        self._scan_operands = idx._scan_operands()   # a mutable index: list_len and n_pos, fixed per generation
         self._generation = idx._generation
         return True
 
     def _device_chain(self, nq: int, k: int, sources=None):
         """As the base class's, over the lists: ``l2_renorm`` (cosine) -> coarse search
         -> storage-dtype cast -> ``rt_ivf_topk`` (``sources``: ``rt_ivf_topk_lists`` with
-        these exclusion sources, positions in ORIGINAL order)."""
+        these exclusion sources, positions in ORIGINAL order); over a
+        :class:`HipMutableIVFFlatIndex` their ``_lens`` forms, which read ``list_len``."""
         n, np_ = nq * k, self._nprobe
         offsets, row_pos, centroids, max_list_rows = self._lists
         q32 = self._d_q32[:nq]
@@ -1504,7 +1520,258 @@ class OnlineIVFSearcher(OnlineSearcher):
             q.copy_(q32)
         kernels.ivf_topk(q, self._rows, offsets, row_pos, probes, max_list_rows, k,
                          out=(self._d_s[:n].view(nq, k), self._d_p[:n].view(nq, k)), workspace_buf=self._ws,
-                         exclude_lists=sources or None)
+                         exclude_lists=sources or None, **self._scan_operands)
+
+
+class HipMutableIVFFlatIndex(HipIVFFlatIndex):
+    """:class:`HipIVFFlatIndex` whose lists change where they lie: ``update`` is
+    an upsert, ``add`` costs O(batch) and ``remove`` withdraws items — the
+    streaming ``item_update`` path (``RetrievalEngine.update_index``) on the
+    reference's default ``"IVF1024,Flat"`` index. Index type ``hip_ivf_mutable``;
+    ``.mutable`` is True. Searches, scores, result order, ``exclude_ids``, the
+    resident :class:`OnlineIVFSearcher` and :class:`~rtrec_amd.serving.online.
+    OnlineRecommender` are the base class's: the scan is the same kernel, told
+    each list's live length (``rt_ivf_topk_lens``).
+
+    Layout: list l owns a fixed range of stored rows — its capacity, ``len +
+    max(min_slack_rows, ceil(len x list_slack))`` at every (re)group — of which
+    the first ``list_len[l]`` are live; ``row_pos`` is -1 in the rest. Config
+    keys beyond the base class's: ``list_slack`` (default 0.25) and
+    ``min_slack_rows`` (default 32). Both defaults are policy choices, not
+    measured: more slack means fewer regroups and more HBM. The device holds
+    the lists, ``list_len``, ``pos_slot`` (the stored row of a position) and
+    ``assign``; the host holds the id maps, the size and the capacities only.
+
+    ``update(embeddings, ids)``: rows are prepared and assigned to the existing
+    centroids (no retraining); the last occurrence of an id given twice wins.
+    A known id's row is overwritten in place, or moved to its new nearest list
+    (``rt_ivf_lists_update``, one call per batch); its position does not
+    change, no pointer, size or ``max_list_rows`` changes, so the generation is
+    NOT bumped and captured serving graphs stay valid and read the new row at
+    their next replay. Unknown ids are appended as by ``add``, in call order.
+
+    ``add``: the new rows take the positions ``current_size ...`` and join their
+    lists through the same kernel call; the generation is bumped (the number of
+    positions is a captured host argument). An id already stored is stored
+    again, and ``reverse_id_map`` then names the last row, as on the Flat index.
+
+    ``remove(ids)``: every row stored under one of the ids leaves its list, and
+    positions are made dense again by this rule (NOT the Flat index's
+    shift-down): with R the removed positions and n' = n - |R|, the surviving
+    positions >= n' take, in ascending order, the removed positions < n', in
+    ascending order; no other item changes position. Equal scores tie by
+    position, so after a ``remove`` ties resolve by the rule's positions, not
+    by those of an index rebuilt on the surviving items. The id maps are
+    updated in O(|R|), the generation is bumped (``OnlineRecommender`` remaps
+    its seen lists); returns the number of rows removed, unknown ids are ignored.
+
+    A batch that would overflow a list's capacity changes nothing on the device;
+    the index then regroups every list once with fresh slack, the batch
+    included — the O(n) path of the base class's ``add``, amortised — bumps the
+    generation and logs at info level.
+
+    ``save`` writes the live rows in position order in the base class's three
+    files; a loaded index answers bit-identically (results never depend on the
+    storage order). Below 1,024 items or below nlist everything is delegated to
+    an inner :class:`HipFlatIPIndex` with ``mutable: True``.
+    """
+
+    _lists_mutable = True
+
+    def __init__(self, config: Optional[Dict[str, Any]] = None):
+        super().__init__(config)
+        self.list_slack = float(self.config.get("list_slack", 0.25))
+        self.min_slack_rows = int(self.config.get("min_slack_rows", 32))
+        if self.list_slack < 0 or self.min_slack_rows < 0:
+            raise ValueError(f"list_slack={self.list_slack}, min_slack_rows={self.min_slack_rows}: both >= 0")
+        self.list_len: Optional[torch.Tensor] = None    # [nlist] int64: live rows of a list
+        self.pos_slot: Optional[torch.Tensor] = None    # [capacity] int32: stored row of a position, -1 none
+        self.capacity = 0                               # stored rows in all: len(index), len(row_pos), ...
+
+    # -- helpers -----------------------------------------------------------
+    def _flat_config(self) -> Dict[str, Any]:
+        cfg = super()._flat_config()
+        cfg["mutable"] = True
+        return cfg
+
+    def _scan_operands(self) -> Dict[str, Any]:
+        return {"list_len": self.list_len, "n_pos": self.current_size}
+
+    def _live_assign(self) -> torch.Tensor:
+        return self.assign[: self.current_size]
+
+    def _regroup(self, src: torch.Tensor, src_index: Optional[torch.Tensor], assign: torch.Tensor):
+        """The base class's regroup into lists with slack: position p (``assign[p]``
+        >= 0) is stored from ``src[src_index[p]]``, original order kept within a
+        list; every array is sized to the new total capacity."""
+        dev, n = assign.device, int(assign.numel())
+        live = torch.nonzero(assign >= 0).view(-1)
+        a = assign[live]
+        order = live[torch.sort(a, stable=True).indices]       # positions, list by list
+        counts = torch.bincount(a, minlength=self.nlist)
+        slack = torch.clamp(torch.ceil(counts.double() * self.list_slack).long(), min=self.min_slack_rows)
+        caps = counts + slack
+        offsets = torch.zeros(self.nlist + 1, dtype=torch.int64, device=dev)
+        offsets[1:] = torch.cumsum(caps, 0)
+        starts = torch.zeros(self.nlist, dtype=torch.int64, device=dev)
+        starts[1:] = torch.cumsum(counts, 0)[:-1]
+        lists = assign[order]
+        slots = offsets[lists] + (torch.arange(order.numel(), dtype=torch.int64, device=dev) - starts[lists])
+        total, max_cap = (int(v) for v in torch.stack([offsets[-1], caps.max()]).tolist())   # the regroup's one read
+        total = max(total, n)   # pos_slot / assign hold every position
+        src_of_slot = torch.full((total,), -1, dtype=torch.int64, device=dev)
+        src_of_slot[slots] = order if src_index is None else src_index[order]
+        self.index = kernels.gather_rows(src, src_of_slot)      # an empty slot: a zero row
+        self.row_pos = torch.full((total,), -1, dtype=torch.int32, device=dev)
+        self.row_pos[slots] = order.to(torch.int32)
+        self.pos_slot = torch.full((total,), -1, dtype=torch.int32, device=dev)
+        self.pos_slot[order] = slots.to(torch.int32)
+        self.assign = torch.full((total,), -1, dtype=torch.int64, device=dev)
+        self.assign[:n] = assign
+        self.list_offsets, self.list_len = offsets, counts
+        self.capacity, self.max_list_rows = total, max_cap
+        self.current_size = n
+
+    def _mutate(self, positions: torch.Tensor, new_list: torch.Tensor, new_rows: torch.Tensor, n_pos: int):
+        """Apply one batch (``rt_ivf_lists_update``) under the searcher lock; ``n_pos``:
+        the positions in use after it. True when the lists were regrouped instead
+        (a position past the capacity, or a list that would overflow)."""
+        if n_pos <= self.capacity:
+            status = kernels.ivf_lists_update(self.index, self.list_offsets, self.list_len, self.row_pos,
+                                              self.pos_slot, self.assign, positions, new_list, new_rows)
+            overflow, refused = status.tolist()   # the call's one read: 8 bytes
+            if refused:
+                raise RuntimeError(f"rt_ivf_lists_update refused {refused} operations: the index state is inconsistent")
+            if not overflow:
+                return False
+            logger.info("%d lists would overflow their capacity: regrouping %d rows with fresh slack", overflow, n_pos)
+        else:
+            logger.info("%d positions exceed the capacity of %d rows: regrouping with fresh slack", n_pos,
+                        self.capacity)
+        n_old, dev = min(self.current_size, n_pos), positions.device
+        assign = torch.full((n_pos,), -1, dtype=torch.int64, device=dev)
+        assign[:n_old] = self.assign[:n_old]
+        src_index = torch.zeros(n_pos, dtype=torch.int64, device=dev)
+        src_index[:n_old] = self.pos_slot[:n_old].long().clamp_(min=0)
+        assign[positions] = new_list
+        src_index[positions] = self.capacity + torch.arange(positions.numel(), dtype=torch.int64, device=dev)
+        self._regroup(torch.cat([self.index, new_rows]), src_index, assign)
+        self._generation += 1
+        return True
+
+    # -- IndexBase ---------------------------------------------------------
+    def add(self, embeddings: Array, ids: List[str]):
+        """retrieval.py:199-226 in O(batch): the new rows are assigned to the existing
+        centroids and join their lists in place (see the class docstring)."""
+        if self.index is None:
+            raise ValueError("Index not built yet")
+        if self._flat is not None:
+            self._flat.add(embeddings, ids)
+            self._sync_flat()
+            return
+        self._append(self._prepare(embeddings), ids)
+
+    def _append(self, rows: torch.Tensor, ids: List[str]):
+        n_old, m = self.current_size, rows.shape[0]
+        positions = torch.arange(n_old, n_old + m, dtype=torch.int64, device=rows.device)
+        new_list = self._assign_rows(rows, self.centroids) if m else positions
+        with self._searcher_lock():
+            if m:
+                self._mutate(positions, new_list, rows.to(self.storage_dtype), n_old + m)
+            self.current_size = n_old + m
+            self._record_ids(n_old, ids, max(m, len(ids)))
+            self._generation += 1
+        logger.info("Added %d items to index. Total size: %d", m, self.current_size)
+
+    def update(self, embeddings: Array, ids: List[str]):
+        """An upsert (see the class docstring): known ids in place, without a
+        generation bump; unknown ids appended as by ``add``."""
+        if self.index is None:
+            raise ValueError("Index not built yet")
+        if self._flat is not None:
+            self._flat.update(embeddings, ids)
+            self._sync_flat()
+            return
+        ids = list(ids)
+        rows = self._prepare(embeddings)
+        if rows.shape[0] != len(ids):
+            raise ValueError(f"{rows.shape[0]} embeddings for {len(ids)} ids")
+        known: Dict[str, int] = {}     # id -> its last row in the call (positions stay unique)
+        unknown: Dict[str, int] = {}   # in order of first appearance, the last row wins too
+        for i, item_id in enumerate(ids):
+            (known if item_id in self.reverse_id_map else unknown)[item_id] = i
+        if known:
+            take = torch.tensor(list(known.values()), dtype=torch.int64, device=rows.device)
+            pos = torch.tensor([self.reverse_id_map[i] for i in known], dtype=torch.int64, device=rows.device)
+            new = rows[take]
+            new_list = self._assign_rows(new, self.centroids)
+            with self._searcher_lock():
+                self._mutate(pos, new_list, new.to(self.storage_dtype), self.current_size)
+        if unknown:
+            take = torch.tensor(list(unknown.values()), dtype=torch.int64, device=rows.device)
+            self._append(rows[take], list(unknown))
+        logger.info("Updated %d items in place, appended %d. Total size: %d", len(known), len(unknown),
+                    self.current_size)
+
+    def remove(self, ids: List[str]) -> Optional[int]:
+        """Withdraw every row stored under one of ``ids`` and renumber by the rule of
+        the class docstring. Returns the number of rows removed."""
+        if self.index is None:
+            raise ValueError("Index not built yet")
+        if self._flat is not None:
+            removed = self._flat.remove(ids)
+            self._sync_flat()
+            return removed
+        hit = {i for i in ids if i in self.reverse_id_map}
+        if not hit:
+            return 0
+        n = self.current_size
+        gone = {self.reverse_id_map[i] for i in hit}
+        if len(self.id_map) != len(self.reverse_id_map):
+            # an id stored more than once through add: every one of its rows goes
+            gone.update(p for p, i in self.id_map.items() if i in hit and p < n)
+        removed = sorted(gone)
+        n_new = n - len(removed)
+        targets = [p for p in removed if p < n_new]
+        movers = [p for p in range(n_new, n) if p not in gone]   # len(removed) candidates at most
+        dev = self._dev()
+        pos = torch.tensor(removed, dtype=torch.int64, device=dev)
+        with self._searcher_lock():
+            self._mutate(pos, torch.full_like(pos, -1),
+                         torch.zeros((len(removed), self.dimension), dtype=self.storage_dtype, device=dev), n)
+            if movers:
+                src = torch.tensor(movers, dtype=torch.int64, device=dev)
+                dst = torch.tensor(targets, dtype=torch.int64, device=dev)
+                slots = self.pos_slot[src]
+                self.row_pos[slots.long()] = dst.to(torch.int32)
+                self.pos_slot[dst] = slots
+                self.assign[dst] = self.assign[src]
+                self.pos_slot[src] = -1
+                self.assign[src] = -1
+            for p in removed:
+                item_id = self.id_map.pop(p, None)
+                if item_id is not None and self.reverse_id_map.get(item_id) == p:
+                    del self.reverse_id_map[item_id]
+            for p, t in zip(movers, targets):
+                item_id = self.id_map.pop(p, None)
+                if item_id is not None:
+                    self.id_map[t] = item_id
+                    if self.reverse_id_map.get(item_id) == p:
+                        self.reverse_id_map[item_id] = t
+                self._ids[t] = self._ids[p]
+            del self._ids[n_new:]
+            self.current_size = n_new
+            self._generation += 1   # positions moved: resident searchers and seen lists remap
+        logger.info("Removed %d items from index. Total size: %d", len(removed), n_new)
+        return len(removed)
+
+    def vectors(self) -> np.ndarray:
+        """The live rows in position order (fp32)."""
+        if self._flat is not None:
+            return self._flat.vectors()
+        if self.index is None or self.current_size == 0:
+            return np.zeros((0, self.dimension), np.float32)
+        return kernels.gather_rows(self.index, self.pos_slot[: self.current_size].long()).float().cpu().numpy()
 
 
 # Backwards-compatible name: configs with index_type "faiss" get the exact
@@ -1512,7 +1779,7 @@ class OnlineIVFSearcher(OnlineSearcher):
 FaissIndex = HipFlatIPIndex
 
 _INDEX_TYPES = {"hip_flat": HipFlatIPIndex, "faiss": HipFlatIPIndex, "hip_flat_sharded": HipShardedFlatIPIndex,
-                "hip_ivf": HipIVFFlatIndex}
+                "hip_ivf": HipIVFFlatIndex, "hip_ivf_mutable": HipMutableIVFFlatIndex}
 
 
 def register_index(name: str, cls):

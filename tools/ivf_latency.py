@@ -31,6 +31,20 @@ The bar: the p50 of ``lists`` in every round is below the MINIMUM p50 of
 and the scan launch alone (hipEvent pairs) without exclusion, with lists and
 with the bitmap.
 
+``--legs mutate`` (not in the default list): HipMutableIVFFlatIndex against
+HipIVFFlatIndex, both built on the same rows with the same seed (the same
+centroids and assignments), nprobe = 20.
+  update  ``update`` of 1, 64 and 1,024 known ids (host embeddings next to other
+          corpus rows, so most change list) on the mutable index, against the only
+          way a HipIVFFlatIndex reaches a state that answers with the new rows:
+          ``add`` (its regroup of every row; the item is then stored twice) —
+          the two alternate call by call, every call ending in a synchronise —
+          and, once per storage, a full ``build``. No ratio is promised.
+  search  p50 of the resident searchers of both indexes alternating call by call,
+          nq in {1, 8}, 3 rounds with each side first in turn. The bar: the
+          mutable side's p50 minus the other's is within 5 x the larger range of
+          the two sides' p50 over the rounds.
+
 Prints one JSON line per case and a closing summary line; run it under a time
 limit, e.g. ``timeout 900 python tools/ivf_latency.py > profiles/ivf_latency.txt``.
 """
@@ -50,7 +64,7 @@ for p in (REPO, os.path.join(REPO, "real-time-recommendation-system-with-feature
 import torch  # noqa: E402
 
 from rtrec_amd import kernels  # noqa: E402
-from rtrec_amd.serving.retrieval import HipFlatIPIndex, HipIVFFlatIndex  # noqa: E402
+from rtrec_amd.serving.retrieval import HipFlatIPIndex, HipIVFFlatIndex, HipMutableIVFFlatIndex  # noqa: E402
 
 
 def pct(samples_ms):
@@ -188,6 +202,97 @@ def leg_exclude(args, storage, ivf, queries, dev):
     return cases
 
 
+def leg_mutate(args, storage, rows, queries, dev):
+    """The mutate leg for one storage dtype: one JSON line per update size and per nq."""
+    n, d, k = rows.shape[0], rows.shape[1], args.k
+    cfg = {"dimension": d, "metric": "cosine", "storage_dtype": storage, "nprobe": 20,
+           "index_factory": f"IVF{args.nlist},Flat", "train_iters": args.train_iters}
+    ids = [f"i{p}" for p in range(n)]
+    built = {}
+    for name, cls in (("ivf", HipIVFFlatIndex), ("mutable", HipMutableIVFFlatIndex)):
+        idx = cls(dict(cfg))
+        t0 = time.perf_counter()
+        idx.build(rows, ids)
+        torch.cuda.synchronize()
+        built[name] = (idx, round(time.perf_counter() - t0, 3))
+    (ivf, t_ivf), (mut, t_mut) = built["ivf"], built["mutable"]
+    caps = torch.diff(mut.list_offsets)
+    print(json.dumps({"leg": "mutate", "part": "build", "storage": storage, "ivf_build_s": t_ivf,
+                      "mutable_build_s": t_mut, "rows": n, "capacity": mut.capacity,
+                      "max_list_rows": {"ivf": ivf.max_list_rows, "mutable": mut.max_list_rows},
+                      "same_centroids": bool(torch.equal(ivf.centroids, mut.centroids)),
+                      "min_capacity": int(caps.min())}), flush=True)
+    out = []
+    rng = np.random.default_rng(5)
+    host_rows = None
+    for m in [int(x) for x in args.mutate_sizes.split(",")]:
+        calls = max(3, min(args.mutate_calls, 20000 // m))
+        t_upd, t_add, moved = [], [], 0
+        gen = mut._generation
+        for c in range(calls + 2):
+            pos = rng.choice(n, size=m, replace=False)
+            src = torch.from_numpy(rng.integers(0, n, m)).to(dev)
+            host_rows = (rows[src] + 0.02 * torch.randn(m, d, device=dev)).cpu().numpy()
+            upd_ids = [ids[p] for p in pos]
+            before = mut.assign[torch.from_numpy(pos).to(dev)].clone()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            mut.update(host_rows, upd_ids)
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            ivf.add(host_rows, upd_ids)
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            if c >= 2:   # two warm-up rounds
+                t_upd.append((t1 - t0) * 1e3)
+                t_add.append((t2 - t1) * 1e3)
+                moved += int((mut.assign[torch.from_numpy(pos).to(dev)] != before).sum())
+        case = {"leg": "mutate", "part": "update", "storage": storage, "m": m, "calls": calls,
+                "update_in_place": pct(t_upd), "add_regroup": pct(t_add),
+                "regroup_over_update_p50": round(pct(t_add)["p50_ms"] / pct(t_upd)["p50_ms"], 1),
+                "rows_that_changed_list": moved, "of": calls * m,
+                "regrouped_on_overflow": mut._generation != gen, "full_build_s": t_ivf}
+        print(json.dumps(case), flush=True)
+        out.append(case)
+    # search: the mutable index (after the updates above) against a HipIVFFlatIndex on ITS rows
+    del ivf
+    torch.cuda.empty_cache()
+    same = HipIVFFlatIndex(dict(cfg))
+    same.centroids = mut.centroids
+    live = torch.from_numpy(mut.vectors()).to(dev).to(mut.storage_dtype)
+    same._regroup(live, None, mut.assign[: mut.current_size].clone())
+    same._generation += 1
+    s_mut, s_same = mut.online_searcher(8), same.online_searcher(8)
+    for nq in [int(x) for x in args.nq.split(",")]:
+        batches = [queries[i * nq:(i + 1) * nq] for i in range(len(queries) // nq)]
+        agree = all(np.array_equal(s_mut.search(b, k)[1].copy(), s_same.search(b, k)[1].copy()) and
+                    np.array_equal(s_mut.search(b, k)[0].copy(), s_same.search(b, k)[0].copy()) for b in batches)
+        state = {"i": 0}
+
+        def call(srch):
+            def f():
+                state["i"] += 1
+                srch.search(batches[state["i"] % len(batches)], k)
+            return f
+        sides = {"ivf": call(s_same), "mutable": call(s_mut)}
+        rounds = []
+        for r in range(3):
+            order = list(sides)[r % 2:] + list(sides)[:r % 2]
+            res = timed_alternating({name: sides[name] for name in order}, args.calls, args.warmup)
+            rounds.append({"first": order[0], **res})
+        p50 = {name: [r[name]["p50_ms"] for r in rounds] for name in sides}
+        rng_ = {name: round(max(v) - min(v), 5) for name, v in p50.items()}
+        diff = round(float(np.median(p50["mutable"]) - np.median(p50["ivf"])), 5)
+        case = {"leg": "mutate", "part": "search", "storage": storage, "nq": nq, "nprobe": 20, "results_agree": agree,
+                "rounds": rounds, "p50_ms": p50, "range_ms": rng_, "mutable_minus_ivf_p50_ms": diff,
+                "bar_ms": round(5 * max(rng_.values()), 5), "within_bar": diff <= 5 * max(rng_.values()),
+                "plan": {"ivf": kernels.ivf_topk_plan(nq, 20, same.max_list_rows),
+                         "mutable": kernels.ivf_topk_plan(nq, 20, mut.max_list_rows)}}
+        print(json.dumps(case), flush=True)
+        out.append(case)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=1_000_000)
@@ -201,7 +306,9 @@ def main():
     ap.add_argument("--nq", default="1,8")
     ap.add_argument("--chunk-tiles", default="", help="comma list of chunk floors (256-row tiles) for the scan alone")
     ap.add_argument("--train-iters", type=int, default=10)
-    ap.add_argument("--legs", default="search", help="comma list of: search (the default), exclude")
+    ap.add_argument("--legs", default="search", help="comma list of: search (the default), exclude, mutate")
+    ap.add_argument("--mutate-sizes", default="1,64,1024", help="known rows per update call of the mutate leg")
+    ap.add_argument("--mutate-calls", type=int, default=12, help="timed update calls per size (fewer for large sizes)")
     ap.add_argument("--exclude-nprobe", type=int, default=20)
     args = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -210,9 +317,16 @@ def main():
     ids = []   # positions only: the id maps are not what is measured
     summary = {"rows": n, "dim": d, "k": k, "nlist": args.nlist, "cases": []}
     legs = args.legs.split(",")
-    if set(legs) - {"search", "exclude"}:
+    if set(legs) - {"search", "exclude", "mutate"}:
         raise SystemExit(f"unknown leg in {args.legs!r}")
     for storage in args.storage.split(","):
+        if "mutate" in legs:
+            summary.setdefault("mutate", []).extend(
+                {key: v for key, v in case.items() if key != "rounds"} for case in leg_mutate(args, storage, rows,
+                                                                                              queries, dev))
+            torch.cuda.empty_cache()
+            if legs == ["mutate"]:
+                continue
         if "search" not in legs:
             ivf = HipIVFFlatIndex({"dimension": d, "metric": "cosine", "storage_dtype": storage, "nprobe": 20,
                                    "index_factory": f"IVF{args.nlist},Flat", "train_iters": args.train_iters})
