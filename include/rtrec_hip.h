@@ -324,6 +324,73 @@ int rt_segment_mean_f32(const void* rows, int64_t n, int d, int dtype, const int
                         const float* prev, int normalize, float* out, void* stream);
 
 /* ------------------------------------------------------------------------
+ * IVF-Flat, list-major batch search: faiss.IndexIVFFlat.search with a batch
+ * of users (src/serving/retrieval.py:141-197 at Q in the thousands, and the
+ * offline evaluation), where rt_ivf_topk reads a list again for every (query,
+ * probe) pair that names it.
+ *
+ * rt_ivf_topk_batch: the operands, limits and result contract of rt_ivf_topk
+ *   (list_len == NULL: lists without slack, n_pos is ignored in favour of nx)
+ *   or of rt_ivf_topk_lens (list_len != NULL: the first list_len[l] rows of a
+ *   list's capacity are live, positions are valid in [0, n_pos),
+ *   max_list_rows bounds the largest capacity); exclude_bits may be NULL. For
+ *   every operand set those two accept, out_scores and out_ids are theirs BIT
+ *   FOR BIT, for fp32, f16 and bf16: the first k of the union of the probed
+ *   lists in (score desc, original position asc) order, (-FLT_MAX, -1) pads;
+ *   a probe entry of -1 or outside [0, nlist) is skipped; a list named twice
+ *   in a probe row may repeat its rows, nothing worse; rows past
+ *   max_list_rows are not scanned; nothing outside a list's window clamped to
+ *   [0, nx) is ever read, whatever the offsets hold; a row whose row_pos is
+ *   outside the valid range is dropped. Scores are the sequential fmaf chain
+ *   over d of the oracle, computed by the fp32 MFMA (one accumulation chain
+ *   per score, d ascending; only k-steps inside d are issued); f16 / bf16
+ *   elements are widened to fp32 first. No 16-bit MFMA: which path serves a
+ *   call never changes a result.
+ *   Work: the (query, probe slot) pairs are grouped by list on the device
+ *   (integer counting and a prefix scan); a work item is (list, tile of QT
+ *   queries that probe it, row chunk) and scans its rows ONCE for the tile.
+ *   Six launches, stream-ordered, no host read; the grid
+ *   depends on host arguments only (the plan's bound of the work items,
+ *   surplus blocks leave), so a captured call may be replayed after probes,
+ *   queries or the lists changed in place. CSR exclusion lists are not taken
+ *   (rt_ivf_topk_lists remains the small-call path).
+ *   Limits: the d / dtype pairs of rt_ivf_topk; 1 <= k <= RT_IVF_MAX_K;
+ *   1 <= nprobe <= RT_IVF_MAX_NPROBE; nq x nprobe < 2^31 - 1; nx, n_pos <
+ *   2^31 - 1; nlist < 2^31 - 1; the plan's blocks < 2^31 - 1.
+ *   Status, before any device work: RT_ERR_INVALID for a NULL operand (rows /
+ *   row_pos may be NULL when nx == 0), k <= 0, nprobe <= 0, nlist <= 0, a
+ *   negative size, an unknown dtype, misaligned queries / rows (16 bytes) or
+ *   workspace (8 bytes), exclude_words < ceil(n_pos / 32); RT_ERR_UNSUPPORTED
+ *   for a limit above; RT_ERR_WORKSPACE. nq == 0: RT_OK without a launch.
+ * rt_ivf_topk_batch_plan: host only. out = {QT, rows per chunk, chunks per
+ *   list, upper bound of the work items, scan blocks launched}. QT = 32; rows
+ *   per chunk is a multiple of the scan's 128-row tile: min(8, tiles of
+ *   max_list_rows) tiles, more where nprobe x chunks <= 512 (the finish's
+ *   lists per query) demands it; chunks x rows per chunk >= max_list_rows;
+ *   bound = (floor(P / QT) + min(nlist, P)) x chunks with P = nq x nprobe;
+ *   blocks = bound. RT_ERR_INVALID for a non-positive nq, nprobe, nlist or k,
+ *   a negative max_list_rows or out == NULL; RT_ERR_UNSUPPORTED for a refused
+ *   shape.
+ * rt_ivf_topk_batch_workspace_bytes: 8 nq k nprobe chunks (the partial lists
+ *   [nq][k][nprobe x chunks] of composite keys) + 4 (3 nlist + 2 + 2 nq
+ *   nprobe) (the grouping tables), rounded up to 256; monotone in nq; 256 for
+ *   a refused shape.
+ * rt_ivf_topk_batch_tuning: process-wide, for measurements only: a bit mask
+ *   of the stages a call issues — 1 grouping (the fill and three launches),
+ *   2 scan, 4 finish; 0 = the default, all. A stage alone reads what an
+ *   earlier whole call left in the same workspace; anything but the default
+ *   leaves out_scores / out_ids unspecified. RT_ERR_INVALID outside [0, 7].
+ * ------------------------------------------------------------------------ */
+int rt_ivf_topk_batch_tuning(int stages);
+int rt_ivf_topk_batch_plan(int64_t nq, int nprobe, int64_t nlist, int64_t max_list_rows, int k, int64_t* out);
+size_t rt_ivf_topk_batch_workspace_bytes(int64_t nq, int nprobe, int64_t nlist, int64_t max_list_rows, int k);
+int rt_ivf_topk_batch(const void* queries, int64_t nq, const void* rows, int64_t nx, int d, int dtype,
+                      const int64_t* list_offsets, int64_t nlist, const int64_t* list_len, int64_t n_pos,
+                      const int32_t* row_pos, const int64_t* probes, int nprobe, int64_t max_list_rows, int k,
+                      const uint32_t* exclude_bits, int64_t exclude_words,
+                      float* out_scores, int64_t* out_ids, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * In-place mutation of IVF lists stored with slack: the streaming item_update
  * path (RetrievalEngine.update_index, src/serving/retrieval.py:228-246,
  * 629-641) on the reference's default index.

@@ -13,6 +13,12 @@ training interactions go to rt_list_metrics; the ranking is copied to the host
 once, for the dict the Evaluator takes. Without ``ml-1m/ratings.dat``
 (not shipped with the reference) the seeded ML-1M-shaped stream is used.
 
+``--index-type hip_ivf`` (with ``--index-factory`` / ``--nprobe``) evaluates the
+lists an index would serve instead of the exact ones — the reference's default
+index is ``"IVF1024,Flat"`` with ``nprobe = 20`` — and adds a ``retrieval`` block
+to the results: index type, nlist, nprobe and recall@k of the index's lists
+against the exact lists for every k of ``--k-values``.
+
     python -m rtrec_amd.evaluate_model --checkpoint models/checkpoints/two_tower_best.pth
 """
 from __future__ import annotations
@@ -38,7 +44,41 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--batch-size", type=int, default=256)
     p.add_argument("--k-values", type=str, default="5,10,20,50,100")
     p.add_argument("--synthetic", action="store_true", help="seeded ML-1M-shaped stream (default if ratings.dat is absent)")
+    p.add_argument("--index-type", type=str, default="exact",
+                   help="'exact' (default: the masked exact top-k) or a registered index type, e.g. hip_ivf: the "
+                        "recommendations are that index's, and the results gain a 'retrieval' block")
+    p.add_argument("--index-factory", type=str, default=None, help="the index's factory string (hip_ivf: IVF1024,Flat)")
+    p.add_argument("--nprobe", type=int, default=None, help="lists probed per user (hip_ivf: 20)")
     return p
+
+
+def index_config_from_args(args) -> Optional[dict]:
+    """The ``index_config`` of ``generate_recommendations`` for the CLI's index options (None: exact)."""
+    if getattr(args, "index_type", "exact") in (None, "exact"):
+        return None
+    cfg = {"index_type": args.index_type}
+    if args.index_factory is not None:
+        cfg["index_factory"] = args.index_factory
+    if args.nprobe is not None:
+        cfg["nprobe"] = int(args.nprobe)
+    return cfg
+
+
+def retrieval_recall(index_ids, exact_ids, k_values) -> dict:
+    """recall@k of an index's lists against the exact lists (device int64 [U, top_k],
+    -1 = no item): per user |index[:k] ∩ exact[:k]| / |exact[:k]|, averaged over the
+    users whose exact list holds an item."""
+    got, want = index_ids.cpu().numpy(), exact_ids.cpu().numpy()
+    out = {}
+    for k in k_values:
+        tot, users = 0.0, 0
+        for g, w in zip(got[:, :k], want[:, :k]):
+            w = set(int(i) for i in w if i >= 0)
+            if w:
+                tot += len(w & set(int(i) for i in g if i >= 0)) / len(w)
+                users += 1
+        out[f"recall@{k}"] = tot / users if users else 1.0
+    return out
 
 
 def prepare_evaluation_data(data):
@@ -89,10 +129,18 @@ def run(args) -> dict:
     model = load_model(args.checkpoint, user_dim=uf.shape[1], item_dim=mf.shape[1], device=device)
     test_users = list(gt.keys())
     t0 = time.time()
+    index_config, index_info = index_config_from_args(args), {}
     _, ids = generate_recommendations(model, test_users, train_items, uf, mf, top_k=max(k_values),
-                                      batch_size=args.batch_size, device=device, return_tensors=True)
+                                      batch_size=args.batch_size, device=device, return_tensors=True,
+                                      index_config=index_config, index_info=index_info)
     recs = recommendations_from_ids(ids, test_users)
     t_recs = time.time() - t0
+    retrieval = None
+    if index_config is not None:
+        # what the index costs: its lists against the exact ones, for the same users and exclusions
+        _, exact_ids = generate_recommendations(model, test_users, train_items, uf, mf, top_k=max(k_values),
+                                                batch_size=args.batch_size, device=device, return_tensors=True)
+        retrieval = {**index_info, **retrieval_recall(ids, exact_ids, k_values)}
     evaluator = Evaluator(k_values=k_values, num_items=mf.shape[0])
     metrics = evaluator.evaluate(recs, gt, exclude_items=train_items)
     results = metrics.to_dict()
@@ -100,6 +148,8 @@ def run(args) -> dict:
     results.update(beyond_accuracy(model, ids, mf, data.train_interactions["movie_idx"].to_numpy(), k=10))
     results.update({"num_test_users": len(test_users), "num_items": int(mf.shape[0]), "checkpoint": args.checkpoint,
                     "data": source, "recommendation_seconds": t_recs})
+    if retrieval is not None:
+        results["retrieval"] = retrieval
     out = Path(args.output)
     out.parent.mkdir(parents=True, exist_ok=True)
     out.write_text(json.dumps(results, indent=2))

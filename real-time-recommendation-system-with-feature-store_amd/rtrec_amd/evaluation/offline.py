@@ -28,7 +28,7 @@ checkpoint's weight shapes, ``weights_only=True``.
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Sequence
+from typing import Any, Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -46,14 +46,46 @@ def _dev(device) -> torch.device:
     return torch.device(device)
 
 
+def build_eval_index(item_emb: torch.Tensor, index_config: Dict[str, Any]):
+    """The item embeddings built into a registered index class (``index_type``,
+    default ``"hip_ivf"``; the other keys are the class's own: ``index_factory``,
+    ``nprobe``, ``storage_dtype`` ...). ``metric`` is forced to
+    ``"inner_product"``, so scores stay the towers' dot products, and
+    ``batch_min_queries`` defaults to 1: an evaluation searches thousands of
+    users in one call, the shape the list-major scan is for. Positions are the
+    item ids."""
+    from ..serving import retrieval
+    cfg = dict(index_config)
+    index_type = cfg.pop("index_type", "hip_ivf")
+    cls = retrieval._INDEX_TYPES.get(index_type)
+    if cls is None or not hasattr(cls, "search_tensors"):
+        raise ValueError(f"index_type={index_type!r}: not a registered device index "
+                         f"(one of {sorted(n for n, c in retrieval._INDEX_TYPES.items() if hasattr(c, 'search_tensors'))})")
+    cfg.setdefault("batch_min_queries", 1)
+    cfg["metric"] = "inner_product"
+    cfg["dimension"] = int(item_emb.shape[1])
+    index = cls(cfg)
+    index.build(item_emb, [str(i) for i in range(item_emb.shape[0])])
+    return index
+
+
 @torch.no_grad()
 def recommend_tensors(model: TwoTowerModel, user_features: torch.Tensor, item_features: torch.Tensor,
                       test_users: torch.Tensor, train_offsets: torch.Tensor, train_items: torch.Tensor,
-                      top_k: int = 100, batch_size: int = 256):
+                      top_k: int = 100, batch_size: int = 256, index_config: Optional[Dict[str, Any]] = None,
+                      index_info: Optional[Dict[str, Any]] = None):
     """Device-resident form: ``user_features`` [n_users, Fu] / ``item_features``
     [n_items, Fi] fp32 tables, ``test_users`` int64 [U], train items as a CSR
     over user rows. Returns (scores fp32 [U, top_k], item ids int64 [U, top_k]),
-    (-FLT_MAX, -1) where fewer than top_k items are eligible."""
+    (-FLT_MAX, -1) where fewer than top_k items are eligible.
+
+    ``index_config``: search through an index instead of exactly — the item
+    embeddings are built into :func:`build_eval_index`'s index and the users
+    searched with ``index.search_tensors(user_emb, top_k, exclude_bits=bits)``,
+    so the lists are what a deployment with that index (the default
+    ``"IVF1024,Flat"``, ``nprobe = 20``) would serve; ``top_k`` above the
+    index's limit raises the index's own error. ``index_info`` (a dict) is
+    filled with the index type, nlist and nprobe used."""
     item_emb = model.get_item_embeddings({"numerical": item_features, "categorical": {}})
     n_items = item_emb.shape[0]
     u_idx = test_users.to(torch.int64)
@@ -63,6 +95,14 @@ def recommend_tensors(model: TwoTowerModel, user_features: torch.Tensor, item_fe
         parts.append(model.get_user_embeddings({"numerical": uf, "categorical": {}}))
     user_emb = torch.cat(parts) if len(parts) != 1 else parts[0]
     bits = kernels.exclusion_bitmap_csr(train_offsets, train_items, n_items, rows=u_idx)
+    if index_config is not None:
+        index = build_eval_index(item_emb.contiguous(), index_config)
+        if index_info is not None:
+            fallback = getattr(index, "_flat", None) is not None   # a corpus too small for IVF lists
+            nlist = None if fallback else getattr(index, "nlist", None)
+            index_info.update({"index_type": index_config.get("index_type", "hip_ivf"), "nlist": nlist,
+                               "nprobe": None if nlist is None else index._n_probe()})
+        return index.search_tensors(user_emb.contiguous(), top_k, exclude_bits=bits)
     return kernels.flatip_topk(user_emb.contiguous(), item_emb.contiguous(), top_k, exclude_bits=bits)
 
 
@@ -86,11 +126,16 @@ def recommendations_from_ids(ids: torch.Tensor, users: Sequence[int]) -> Dict[in
 def generate_recommendations(model: TwoTowerModel, test_users: list, train_items: Dict[int, list],
                              user_features: np.ndarray, movie_features: np.ndarray, top_k: int = 100,
                              batch_size: int = 256, device: Optional[str] = None,
-                             return_tensors: bool = False, pad_excluded: bool = False):
+                             return_tensors: bool = False, pad_excluded: bool = False,
+                             index_config: Optional[Dict[str, Any]] = None,
+                             index_info: Optional[Dict[str, Any]] = None):
     """evaluate_model.py:162-234 → Dict[user_idx, List[movie_idx]] (or the
     device (scores, ids) with ``return_tensors``). ``pad_excluded``: lists of
     users with fewer than ``top_k`` eligible items are padded with their
-    excluded items as the reference pads them (see the module docstring)."""
+    excluded items as the reference pads them (see the module docstring).
+    ``index_config`` / ``index_info``: as :func:`recommend_tensors` — the lists
+    of an index (``{"index_type": "hip_ivf", "index_factory": "IVF1024,Flat",
+    "nprobe": 20}``) instead of the exact ones; without it nothing changes."""
     dev = _dev(device)
     uf = torch.as_tensor(np.asarray(user_features, np.float32)).to(dev)
     mf = torch.as_tensor(np.asarray(movie_features, np.float32)).to(dev)
@@ -102,7 +147,8 @@ def generate_recommendations(model: TwoTowerModel, test_users: list, train_items
             rows[int(u)] = its
     t_off, t_items = csr_from_sets(rows, dev)
     scores, ids = recommend_tensors(model, uf, mf, torch.tensor(users, dtype=torch.int64, device=dev), t_off,
-                                    t_items, top_k=top_k, batch_size=batch_size)
+                                    t_items, top_k=top_k, batch_size=batch_size, index_config=index_config,
+                                    index_info=index_info)
     if return_tensors:
         return scores, ids
     if not pad_excluded:

@@ -645,6 +645,115 @@ def ivf_topk(queries: torch.Tensor, rows: torch.Tensor, list_offsets: torch.Tens
     return scores, ids
 
 
+# Workspace one rt_ivf_topk_batch call may take; larger batches run in query
+# chunks. A policy default (the partial lists of a chunk stay inside the 256 MB
+# Infinity Cache), not a measured one.
+IVF_BATCH_WORKSPACE_BUDGET = 256 << 20
+
+
+def ivf_topk_batch_plan(nq: int, nprobe: int, nlist: int, max_list_rows: int, k: int
+                        ) -> Tuple[int, int, int, int, int]:
+    """Host-only plan of the list-major batch search (rt_ivf_topk_batch_plan):
+    ``(QT, rows per chunk, chunks per list, upper bound of the work items, scan
+    blocks launched)``. No device work."""
+    out = (ctypes.c_int64 * 5)()
+    call("rt_ivf_topk_batch_plan", int(nq), int(nprobe), int(nlist), int(max_list_rows), int(k),
+         ctypes.cast(out, ctypes.c_void_p))
+    return tuple(int(v) for v in out)
+
+
+def ivf_topk_batch_tuning(stages: int = 0) -> None:
+    """Which stages a batch call issues (1 grouping | 2 scan | 4 finish; 0 = all): for
+    measuring a stage alone over the workspace of an earlier whole call."""
+    call("rt_ivf_topk_batch_tuning", int(stages))
+
+
+def _ivf_batch_query_chunk(nq: int, nprobe: int, nlist: int, max_list_rows: int, k: int) -> int:
+    """Largest number of queries whose workspace fits IVF_BATCH_WORKSPACE_BUDGET
+    (at least one tile of 32; the workspace is monotone in nq)."""
+    size = native.lib().rt_ivf_topk_batch_workspace_bytes
+    if size(nq, nprobe, nlist, max_list_rows, k) <= IVF_BATCH_WORKSPACE_BUDGET:
+        return nq
+    lo, hi = 1, max(1, nq // 32)   # in tiles: lo always runs, hi does not fit
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        if size(32 * mid, nprobe, nlist, max_list_rows, k) <= IVF_BATCH_WORKSPACE_BUDGET:
+            lo = mid
+        else:
+            hi = mid
+    return min(nq, 32 * lo)
+
+
+def ivf_topk_batch(queries: torch.Tensor, rows: torch.Tensor, list_offsets: torch.Tensor, row_pos: torch.Tensor,
+                   probes: torch.Tensor, max_list_rows: int, k: int, exclude_bits: Optional[torch.Tensor] = None,
+                   out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                   workspace_buf: Optional[torch.Tensor] = None,
+                   list_len: Optional[torch.Tensor] = None, n_pos: Optional[int] = None,
+                   exclude_lists=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """:func:`ivf_topk` for large batches (rt_ivf_topk_batch): the same operands
+    and, bit for bit, the same (scores [nq, k] f32, original positions [nq, k]
+    int64) — but the work is grouped by LIST: a block scans a chunk of a list
+    once for a tile of 32 queries that probe it, on the fp32 MFMA, where
+    ``ivf_topk`` streams the list again for every (query, probe) pair.
+    ``list_len`` with ``n_pos``: lists stored with slack, as for ``ivf_topk``.
+    ``exclude_bits`` is indexed by original position. CSR ``exclude_lists`` are
+    not taken: use :func:`ivf_topk`, the small-call path, for those.
+    Queries run in chunks whose workspace stays within
+    ``IVF_BATCH_WORKSPACE_BUDGET`` (256 MiB by default: a policy default, not a
+    measured one); a ``workspace_buf`` must hold one whole call's workspace."""
+    if exclude_lists is not None:
+        raise ValueError("ivf_topk_batch takes exclude_bits only; CSR exclude_lists are read by ivf_topk")
+    native.require_device(queries, rows, list_offsets, row_pos, probes, exclude_bits, list_len, what="ivf_topk_batch")
+    if queries.dim() != 2 or rows.dim() != 2 or queries.shape[1] != rows.shape[1]:
+        raise ValueError(f"shape mismatch: queries {tuple(queries.shape)} rows {tuple(rows.shape)}")
+    if queries.dtype != rows.dtype:
+        raise TypeError("queries and rows must share a dtype")
+    if not 1 <= k <= IVF_MAX_K:
+        raise ValueError(f"k={k}: ivf_topk_batch returns 1..{IVF_MAX_K} results per query")
+    if not (queries.is_contiguous() and rows.is_contiguous() and probes.is_contiguous()
+            and list_offsets.is_contiguous() and row_pos.is_contiguous()):
+        raise ValueError("ivf_topk_batch expects contiguous operands")
+    nq, d = queries.shape
+    nx = rows.shape[0]
+    if list_offsets.dtype != torch.int64 or list_offsets.dim() != 1 or list_offsets.numel() < 2:
+        raise ValueError("list_offsets must be int64 [nlist + 1]")
+    if row_pos.dtype != torch.int32 or row_pos.numel() != nx:
+        raise ValueError("row_pos must be int32 [nx]")
+    if probes.dtype != torch.int64 or probes.dim() != 2 or probes.shape[0] != nq:
+        raise ValueError("probes must be int64 [nq, nprobe]")
+    nprobe = probes.shape[1]
+    if not 1 <= nprobe <= IVF_MAX_NPROBE:
+        raise ValueError(f"nprobe={nprobe}: 1..{IVF_MAX_NPROBE}")
+    nlist = list_offsets.numel() - 1
+    if list_len is not None:
+        if list_len.dtype != torch.int64 or list_len.numel() != nlist or not list_len.is_contiguous():
+            raise ValueError("list_len must be contiguous int64 [nlist]")
+        if n_pos is None or not 0 <= int(n_pos):
+            raise ValueError("list_len comes with n_pos >= 0, the number of valid positions")
+    elif n_pos is not None:
+        raise ValueError("n_pos comes with list_len")
+    dt = native.dtype_code(queries.dtype)
+    scores, ids = _topk_out(out, nq, k, queries.device)
+    words = _exclude_words(exclude_bits, nq, True)
+    mlr = int(max_list_rows)
+    size = native.lib().rt_ivf_topk_batch_workspace_bytes
+    if workspace_buf is not None:
+        step = nq
+    else:
+        step = _ivf_batch_query_chunk(nq, nprobe, nlist, mlr, k) if nq else 0
+    for a in range(0, nq, max(step, 1)):
+        b = min(nq, a + step)
+        ws = workspace_buf
+        if ws is None:
+            ws = workspace(queries.device, size(b - a, nprobe, nlist, mlr, k), "ivf_topk_batch")
+        call("rt_ivf_topk_batch", ptr(queries[a:b]), b - a, ptr(rows) if nx else None, nx, d, dt,
+             ptr(list_offsets), nlist, ptr(list_len) if list_len is not None else None,
+             int(n_pos) if list_len is not None else nx, ptr(row_pos) if nx else None, ptr(probes[a:b]), nprobe,
+             mlr, k, ptr(exclude_bits[a:b]) if exclude_bits is not None else None, words,
+             ptr(scores[a:b]), ptr(ids[a:b]), ptr(ws), ws.numel(), stream_of(queries))
+    return scores, ids
+
+
 def ivf_lists_update(rows: torch.Tensor, list_offsets: torch.Tensor, list_len: torch.Tensor, row_pos: torch.Tensor,
                      pos_slot: torch.Tensor, assign: torch.Tensor, positions: torch.Tensor, new_list: torch.Tensor,
                      new_rows: torch.Tensor, status: Optional[torch.Tensor] = None) -> torch.Tensor:

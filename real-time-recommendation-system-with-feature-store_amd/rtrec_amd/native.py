@@ -139,6 +139,11 @@ SIGNATURES = {
                                  c_int, vp, c_i64, vp, vp, vp, c_size, vp]),
     "rt_ivf_topk_lists_lens": (c_int, [vp, c_i64, vp, c_i64, c_int, c_int, vp, c_i64, vp, c_i64, vp, vp, c_int,
                                        c_i64, c_int, ctypes.POINTER(ExclusionLists), c_int, vp, vp, vp, c_size, vp]),
+    "rt_ivf_topk_batch_tuning": (c_int, [c_int]),
+    "rt_ivf_topk_batch_plan": (c_int, [c_i64, c_int, c_i64, c_i64, c_int, vp]),
+    "rt_ivf_topk_batch_workspace_bytes": (c_size, [c_i64, c_int, c_i64, c_i64, c_int]),
+    "rt_ivf_topk_batch": (c_int, [vp, c_i64, vp, c_i64, c_int, c_int, vp, c_i64, vp, c_i64, vp, vp, c_int, c_i64,
+                                  c_int, vp, c_i64, vp, vp, vp, c_size, vp]),
     "rt_segment_mean_f32": (c_int, [vp, c_i64, c_int, c_int, vp, c_i64, vp, c_int, vp, vp]),
     "rt_ivf_lists_update_workspace_bytes": (c_size, [c_i64, c_i64]),
     "rt_ivf_lists_update": (c_int, [vp, c_i64, c_int, c_int, vp, c_i64, vp, vp, vp, vp, vp, vp, vp, c_i64, vp, vp,

@@ -45,6 +45,22 @@ centroids and assignments), nprobe = 20.
           mutable side's p50 minus the other's is within 5 x the larger range of
           the two sides' p50 over the rounds.
 
+``--legs batch`` (not in the default list): the list-major batch search
+(rt_ivf_topk_batch, the ``batch_min_queries`` key) on 1M x 128 clustered rows,
+nlist 1024, nprobe 20, k 100, nq in {16, 64, 256, 1024, 4096}, device-resident
+queries. Three arms alternate call by call, 3 rounds with each arm first in
+turn, every call ending in a synchronise:
+  A  ``search_tensors`` on the per-query path (one scan block per query, probed
+     list and chunk: the only path before the key existed);
+  B  the same index with ``batch_min_queries = 1``;
+  C  ``kernels.flatip_topk`` over the flat corpus (the exact search).
+Per shape: the p50 per round and arm (with the number of calls), the hipEvent
+p50 of B's scan call alone, whole and split into grouping / scan / finish
+(rt_ivf_topk_batch_tuning), and one check that A and B agree bit for bit. The
+bar: at nq = 4096, both storages, B's p50 in every round is below the MINIMUM
+of A's p50 over its rounds; the crossover is the smallest measured nq from
+which that holds for both storages. B against C is reported, not barred.
+
 Prints one JSON line per case and a closing summary line; run it under a time
 limit, e.g. ``timeout 900 python tools/ivf_latency.py > profiles/ivf_latency.txt``.
 """
@@ -293,6 +309,88 @@ def leg_mutate(args, storage, rows, queries, dev):
     return out
 
 
+def leg_batch(args, storage, rows, queries, dev):
+    """The batch leg for one storage dtype: one JSON line per nq. ``queries``: fp32, on the device."""
+    n, d, k, nprobe = rows.shape[0], rows.shape[1], args.k, args.batch_nprobe
+    ivf = HipIVFFlatIndex({"dimension": d, "metric": "cosine", "storage_dtype": storage, "nprobe": nprobe,
+                           "index_factory": f"IVF{args.nlist},Flat", "train_iters": args.train_iters})
+    ivf.build(rows, [])
+    flat = HipFlatIPIndex({"dimension": d, "metric": "cosine", "storage_dtype": storage})
+    flat.build(rows, [])
+    torch.cuda.synchronize()
+    lens = torch.diff(ivf.list_offsets)
+    out = []
+    for nq in [int(x) for x in args.batch_nq.split(",")]:
+        q = queries[:nq].contiguous()
+        qs = ivf._prepare(q).to(ivf.storage_dtype)
+        calls = max(3, min(args.batch_calls, 20480 // nq))
+
+        def per_query():
+            ivf.batch_min_queries = None
+            r = ivf.search_tensors(q, k)
+            torch.cuda.synchronize()
+            return r
+
+        def batch():
+            ivf.batch_min_queries = 1
+            r = ivf.search_tensors(q, k)
+            torch.cuda.synchronize()
+            return r
+
+        def flat_scan():
+            r = kernels.flatip_topk(qs, flat.index[: flat.current_size], k)
+            torch.cuda.synchronize()
+            return r
+
+        a, b, c = per_query(), batch(), flat_scan()
+        agree = bool(torch.equal(a[1], b[1]) and torch.equal(a[0].view(torch.int32), b[0].view(torch.int32)))
+        if not agree:
+            raise SystemExit(f"batch leg {storage} nq={nq}: the per-query path and the batch path differ")
+        sides = {"A_per_query": per_query, "B_batch": batch, "C_flat": flat_scan}
+        names, rounds = list(sides), []
+        for r in range(3):
+            order = names[r:] + names[:r]
+            res = timed_alternating({name: sides[name] for name in order}, calls, 2)
+            rounds.append({"first": order[0], **res})
+        floor = min(r["A_per_query"]["p50_ms"] for r in rounds)
+        # B's launches alone, on prepared device operands: a whole call fills the workspace, then each
+        # stage is issued alone over it
+        _, probes = kernels.flatip_topk(ivf._prepare(q), ivf.centroids, nprobe)
+        ws = torch.empty(kernels.native.lib().rt_ivf_topk_batch_workspace_bytes(nq, nprobe, ivf.nlist,
+                                                                                ivf.max_list_rows, k),
+                         dtype=torch.uint8, device=dev)
+        res = (torch.empty((nq, k), dtype=torch.float32, device=dev), torch.empty((nq, k), dtype=torch.int64, device=dev))
+        scan = lambda: kernels.ivf_topk_batch(qs, ivf.index, ivf.list_offsets, ivf.row_pos, probes,  # noqa: E731
+                                              ivf.max_list_rows, k, out=res, workspace_buf=ws)
+        scan()
+        ev = {"whole": event_timed({"s": scan}, calls, 2)["s"]}
+        try:
+            for name, stages in (("grouping", 1), ("scan", 2), ("finish", 4)):
+                kernels.ivf_topk_batch_tuning(stages)
+                ev[name] = event_timed({"s": scan}, calls, 2)["s"]
+        finally:
+            kernels.ivf_topk_batch_tuning(0)
+        ev["coarse"] = event_timed({"s": lambda: kernels.flatip_topk(ivf._prepare(q), ivf.centroids, nprobe)}, calls,
+                                   2)["s"]
+        esz = 2 if storage == "float16" else 4
+        case = {"leg": "batch", "storage": storage, "nq": nq, "nprobe": nprobe, "k": k, "calls_per_round": calls,
+                "A_equals_B_bit_for_bit": agree, "rounds": rounds,
+                "bar": {"A_min_p50_ms": floor, "B_p50_ms": [r["B_batch"]["p50_ms"] for r in rounds],
+                        "A_p50_ms": [r["A_per_query"]["p50_ms"] for r in rounds],
+                        "C_p50_ms": [r["C_flat"]["p50_ms"] for r in rounds],
+                        "B_below_A_min_in_every_round": all(r["B_batch"]["p50_ms"] < floor for r in rounds)},
+                "B_event_p50_ms": ev,
+                "plan": dict(zip(("qt", "rows_per_chunk", "chunks", "items_bound", "blocks"),
+                                 kernels.ivf_topk_batch_plan(nq, nprobe, ivf.nlist, ivf.max_list_rows, k))),
+                "per_query_plan": kernels.ivf_topk_plan(min(nq, 32768), nprobe, ivf.max_list_rows),
+                "workspace_bytes": int(ws.numel()), "max_list_rows": ivf.max_list_rows,
+                "probed_row_bytes": int(lens[probes].sum().item()) * d * esz,
+                f"recall_at_{k}_vs_flat": round(recall(b[1].cpu().numpy(), c[1].cpu().numpy()), 4)}
+        print(json.dumps(case), flush=True)
+        out.append({"storage": storage, "nq": nq, **case["bar"]})
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=1_000_000)
@@ -310,6 +408,10 @@ def main():
     ap.add_argument("--mutate-sizes", default="1,64,1024", help="known rows per update call of the mutate leg")
     ap.add_argument("--mutate-calls", type=int, default=12, help="timed update calls per size (fewer for large sizes)")
     ap.add_argument("--exclude-nprobe", type=int, default=20)
+    ap.add_argument("--batch-nq", default="16,64,256,1024,4096", help="batch sizes of the batch leg")
+    ap.add_argument("--batch-nprobe", type=int, default=20)
+    ap.add_argument("--batch-calls", type=int, default=30,
+                    help="timed calls per arm and round of the batch leg (fewer for large batches: 20,480 / nq)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     n, d, k = args.rows, args.dim, args.k
@@ -317,9 +419,18 @@ def main():
     ids = []   # positions only: the id maps are not what is measured
     summary = {"rows": n, "dim": d, "k": k, "nlist": args.nlist, "cases": []}
     legs = args.legs.split(",")
-    if set(legs) - {"search", "exclude", "mutate"}:
+    if set(legs) - {"search", "exclude", "mutate", "batch"}:
         raise SystemExit(f"unknown leg in {args.legs!r}")
+    if "batch" in legs:
+        # the same rows (the generator draws them first) and as many queries as the largest batch
+        nq_max = max(int(x) for x in args.batch_nq.split(","))
+        batch_queries = torch.from_numpy(corpus(n, d, 4096, nq_max, dev)[1]).to(dev)
     for storage in args.storage.split(","):
+        if "batch" in legs:
+            summary.setdefault("batch", []).extend(leg_batch(args, storage, rows, batch_queries, dev))
+            torch.cuda.empty_cache()
+            if legs == ["batch"]:
+                continue
         if "mutate" in legs:
             summary.setdefault("mutate", []).extend(
                 {key: v for key, v in case.items() if key != "rounds"} for case in leg_mutate(args, storage, rows,
@@ -399,6 +510,18 @@ def main():
             summary.setdefault("exclude", []).extend(leg_exclude(args, storage, ivf, queries, dev))
         del s_flat, s_ivf, flat, ivf
         torch.cuda.empty_cache()
+    if "batch" in summary:
+        # the crossover: the smallest measured nq from which B is below A's minimum in every round, all storages
+        holds = {}
+        for case in summary["batch"]:
+            holds[case["nq"]] = holds.get(case["nq"], True) and case["B_below_A_min_in_every_round"]
+        crossover = None
+        for nq in sorted(holds, reverse=True):
+            if not holds[nq]:
+                break
+            crossover = nq
+        summary["batch_bar"] = {"holds_by_nq": {str(nq): holds[nq] for nq in sorted(holds)},
+                                "met_at_largest_nq": bool(holds and holds[max(holds)]), "crossover_nq": crossover}
     print(json.dumps(summary), flush=True)
 
 
