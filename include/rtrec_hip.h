@@ -391,6 +391,76 @@ int rt_ivf_topk_batch(const void* queries, int64_t nq, const void* rows, int64_t
                       float* out_scores, int64_t* out_ids, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Category filters: the request schema's filter_categories
+ * (src/api/schemas.py:21-34), tested by the scan itself.
+ *
+ * Every item carries `tags`, a 64-bit set: bit j = the item belongs to
+ * category j of a vocabulary of at most 64 names; 0 = untagged. A query
+ * carries two 64-bit masks. Item p is ELIGIBLE for query q iff
+ *     (any_of[q] == 0 || (tags[p] & any_of[q]) != 0) && (tags[p] & none_of[q]) == 0
+ * so an untagged item passes no non-zero any_of and fails no none_of, and
+ * any_of == none_of == 0 filters nothing. A filtered search is the existing
+ * search over the eligible items: the same score bits, the same (score desc,
+ * original position asc) order and (-FLT_MAX, -1) pads, exact over the rows
+ * scanned (k results whenever k eligible rows exist among them; for the IVF
+ * entry point the rows scanned are the probed lists). Exclusion lists compose
+ * by union of what is skipped.
+ *   RtTagFilter: device pointers, 8-byte aligned. item_tags is indexed by the
+ *   position the result ids name before id_offset: the local row for the Flat
+ *   scan, the ORIGINAL position (the space of row_pos values) for the IVF
+ *   scan, [nx] resp. [n_pos] words. any_of / none_of are [nq] or NULL (all 0).
+ * rt_flatip_topk_online_tags: rt_flatip_topk_online_lists plus `filter`.
+ *   filter == NULL: rt_flatip_topk_online_lists, bit for bit. Otherwise one
+ *   instantiation of the same scan serves the filter and 0..2 list sources: a
+ *   lane's 8 bytes of tags are one coalesced load per 256-row tile, issued a
+ *   tile ahead of the selection that reads them; the masks sit in LDS; an
+ *   ineligible row is never appended. Workspace, plan, limits and result rows
+ *   are rt_flatip_topk_online's.
+ *   Status, before any device work: RT_ERR_INVALID for filter != NULL with
+ *   item_tags == NULL while nx > 0 or with a pointer that is not 8-byte
+ *   aligned; then every refusal of rt_flatip_topk_online_lists.
+ * rt_ivf_topk_tags: rt_ivf_topk_lists_lens plus `filter`; list_len may be NULL
+ *   (lists without slack: n_pos is ignored in favour of nx, as
+ *   rt_ivf_topk_batch does). filter == NULL: rt_ivf_topk_lists (list_len ==
+ *   NULL) or rt_ivf_topk_lists_lens, bit for bit. Otherwise a lane gathers
+ *   item_tags[row_pos[row]] under the scores, and only for a position inside
+ *   [0, n_pos): the -1 of an empty slot reads nothing. The lists' layout and
+ *   rt_ivf_lists_update know nothing of the tags.
+ *   Status, before any device work: RT_ERR_INVALID for filter != NULL with
+ *   item_tags == NULL while positions exist (n_pos resp. nx > 0) or with a
+ *   pointer that is not 8-byte aligned; then every refusal of
+ *   rt_ivf_topk_lists(_lens).
+ * rt_tag_filter_bitmap: the filter as an exclusion bitmap uint32 [nq, words]
+ *   for the entry points that take exclude_bits (rt_flatip_topk,
+ *   rt_ivf_topk_batch, calls above the online limits): bit p of row q is set
+ *   for every INELIGIBLE p < n_items. accumulate != 0 ORs into what is there
+ *   (an exclude_ids bitmap composes); otherwise every word of the row is
+ *   overwritten, bits >= n_items zero. Coalesced tag loads, a wave's ballot is two
+ *   words, one word stored per thread; no [nq, n_items] intermediate. any_of / none_of may be NULL (all 0).
+ *   Status: RT_ERR_INVALID for a negative size, item_tags == NULL while
+ *   n_items > 0, bits == NULL while words exist, a pointer that is not 8-byte
+ *   (bits: 4-byte) aligned, words < ceil(n_items / 32). nq == 0: RT_OK.
+ * ------------------------------------------------------------------------ */
+typedef struct {
+    const uint64_t* item_tags;  /* [n_pos], by ORIGINAL position (Flat: local row), device */
+    const uint64_t* any_of;     /* [nq] or NULL (= all 0), device */
+    const uint64_t* none_of;    /* [nq] or NULL (= all 0), device */
+} RtTagFilter;
+
+int rt_flatip_topk_online_tags(const void* queries, int64_t nq, const void* items, int64_t nx, int d, int dtype,
+                               int k, const RtExclusionLists* lists, int n_lists, const RtTagFilter* filter,
+                               int64_t id_offset, float* out_scores, int64_t* out_ids, void* workspace,
+                               size_t workspace_bytes, void* stream);
+int rt_ivf_topk_tags(const void* queries, int64_t nq, const void* rows, int64_t nx, int d, int dtype,
+                     const int64_t* list_offsets, int64_t nlist, const int64_t* list_len, int64_t n_pos,
+                     const int32_t* row_pos, const int64_t* probes, int nprobe, int64_t max_list_rows, int k,
+                     const RtExclusionLists* lists, int n_lists, const RtTagFilter* filter, float* out_scores,
+                     int64_t* out_ids, void* workspace, size_t workspace_bytes, void* stream);
+int rt_tag_filter_bitmap(const uint64_t* item_tags, int64_t n_items, const uint64_t* any_of,
+                         const uint64_t* none_of, int64_t nq, uint32_t* bits, int64_t words, int accumulate,
+                         void* stream);
+
+/* ------------------------------------------------------------------------
  * In-place mutation of IVF lists stored with slack: the streaming item_update
  * path (RetrievalEngine.update_index, src/serving/retrieval.py:228-246,
  * 629-641) on the reference's default index.

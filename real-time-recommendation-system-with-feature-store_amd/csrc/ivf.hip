@@ -38,6 +38,12 @@
 // kListCap entries (else the search reads `items` in global memory): one
 // search routine over a generic pointer serves both.
 //
+// rt_ivf_topk_tags: the LISTS scan's TAGS instantiation (any number of sources,
+// none included). item_tags is indexed by ORIGINAL position, so the lists'
+// layout and rt_ivf_lists_update know nothing of it: the lane gathers
+// item_tags[pos] as soon as it holds pos, in flight under the scores, and only
+// for a pos inside [0, n_pos). Eligibility is one more term of `pass`.
+//
 // rt_ivf_topk_lens / rt_ivf_topk_lists_lens: the same kernels over lists stored
 // with slack (ivf_mutate.hip). Two more operands: list_len (the live rows of a
 // list are the first list_len[l] of its capacity) and n_pos (positions are valid
@@ -123,15 +129,15 @@ __device__ __forceinline__ bool list_has(const int32_t* items, int64_t lo, int64
 }
 
 // LISTS: the exclusions are `la`'s CSR lists (excl is not read); otherwise the
-// optional dense bitmap `excl`.
-template <typename T, bool LISTS>
+// optional dense bitmap `excl`. TAGS: `ta`'s tag filter on top.
+template <typename T, bool LISTS, bool TAGS = false>
 __global__ __launch_bounds__(on::kThreads, 2) void ivf_scan(
     const T* __restrict__ Q, const char* __restrict__ X, int64_t nx, int d, int k,
     const int64_t* __restrict__ list_offsets, int64_t nlist, const int64_t* __restrict__ list_len, int64_t n_pos,
     const int32_t* __restrict__ row_pos, const int64_t* __restrict__ probes, int nprobe, int chunks,
     int64_t rows_per_chunk,
     const uint32_t* __restrict__ excl, int64_t excl_words, uint64_t* __restrict__ partials,
-    const on::ListArgs<LISTS> la) {
+    const on::ListArgs<LISTS> la, const on::TagArgs<TAGS> ta) {
     constexpr int EPU = 16 / static_cast<int>(sizeof(T));
     constexpr int kThreads = on::kThreads, kTileRows = on::kTileRows, kStepUnits = on::kStepUnits;
     using L = on::Lds<1>;
@@ -187,6 +193,16 @@ __global__ __launch_bounds__(on::kThreads, 2) void ivf_scan(
 
     uint4 R[kStepUnits];
     on::load_step(R, w, 0, 0);
+    // TAGS: the query's masks (block-uniform), and the position of this lane's row
+    // one tile ahead, so that the gather of a tile's tags never waits for it
+    uint64_t any_of = 0ull, none_of = 0ull;
+    int32_t pos_next = -1;
+    if constexpr (TAGS) {
+        if (ta.any_of) any_of = ta.any_of[q];
+        if (ta.none_of) none_of = ta.none_of[q];
+        const int64_t row0 = w.row_begin + threadIdx.x;
+        if (row0 < w.row_end) pos_next = row_pos[row0];
+    }
     // the query's CSR row of every source: items xit[s][xlo[s], xhi[s]) (block-uniform)
     const int32_t* xit[on::kMaxSrc];
     int64_t xlo[on::kMaxSrc], xhi[on::kMaxSrc];
@@ -240,7 +256,16 @@ __global__ __launch_bounds__(on::kThreads, 2) void ivf_scan(
         const float th = thr;
         const int64_t row = w.row_begin + static_cast<int64_t>(t) * kTileRows + wave * 64 + lane;
         // original position of this lane's row: in flight under the scores
-        const int32_t pos = row < w.row_end ? row_pos[row] : -1;
+        int32_t pos;
+        uint64_t tg = 0ull;
+        if constexpr (TAGS) {
+            pos = pos_next;
+            // a position outside [0, n_pos) has no tags: no gather for it (it is dropped below)
+            if (pos >= 0 && static_cast<int64_t>(pos) < n_pos) tg = ta.item_tags[pos];
+            pos_next = (row + kTileRows) < w.row_end ? row_pos[row + kTileRows] : -1;
+        } else {
+            pos = row < w.row_end ? row_pos[row] : -1;
+        }
 
         float acc[1];
         on::score_tile<T, 1>(R, w, t, stage, qs, d, acc);
@@ -249,6 +274,7 @@ __global__ __launch_bounds__(on::kThreads, 2) void ivf_scan(
         // a position outside [0, n_pos) (a corrupt row_pos, an empty slot of a list with
         // slack) is dropped: it has no bit in the bitmap and no row in the caller's corpus
         bool pass = pos >= 0 && static_cast<int64_t>(pos) < n_pos && acc[0] >= th;
+        if constexpr (TAGS) pass = pass && on::tag_eligible(tg, any_of, none_of);
         if constexpr (LISTS) {
             if (__any(pass)) {  // wave-uniform
 #pragma unroll
@@ -366,8 +392,8 @@ static int ivf_search(const void* queries, int64_t nq, const void* rows, int64_t
                       const int64_t* list_offsets, int64_t nlist, const int64_t* list_len, int64_t n_pos,
                       const int32_t* row_pos, const int64_t* probes,
                       int nprobe, int64_t max_list_rows, int k, const uint32_t* exclude_bits, int64_t exclude_words,
-                      const ivon::ListArgs<true>* la, float* out_scores, int64_t* out_ids, void* workspace,
-                      size_t workspace_bytes, void* stream) {
+                      const ivon::ListArgs<true>* la, const ivon::TagSrc* tags, float* out_scores, int64_t* out_ids,
+                      void* workspace, size_t workspace_bytes, void* stream) {
     if (nq < 0 || nx < 0 || d <= 0 || k <= 0 || nlist <= 0 || nprobe <= 0 || max_list_rows < 0 || n_pos < 0)
         return RT_ERR_INVALID;
     if (nq == 0) return RT_OK;
@@ -389,11 +415,20 @@ static int ivf_search(const void* queries, int64_t nq, const void* rows, int64_t
     uint64_t* partials = static_cast<uint64_t*>(workspace);
     const dim3 grid(static_cast<unsigned>(lists), static_cast<unsigned>(nq)), block(ivon::kThreads);
     const char* x = static_cast<const char*>(rows);
-#define RT_IVF_LAUNCH(T, LISTS, LA)                                                                             \
-    hipLaunchKernelGGL((iv::ivf_scan<T, LISTS>), grid, block, 0, st, static_cast<const T*>(queries), x, nx, d, k, \
-                       list_offsets, nlist, list_len, n_pos, row_pos, probes, nprobe, p.chunks, p.rows_per_chunk, \
-                       exclude_bits, exclude_words, partials, LA)
-    if (la) {
+#define RT_IVF_LAUNCH_T(T, LISTS, TAGS, LA, TA)                                                                  \
+    hipLaunchKernelGGL((iv::ivf_scan<T, LISTS, TAGS>), grid, block, 0, st, static_cast<const T*>(queries), x, nx, \
+                       d, k, list_offsets, nlist, list_len, n_pos, row_pos, probes, nprobe, p.chunks,             \
+                       p.rows_per_chunk, exclude_bits, exclude_words, partials, LA, TA)
+#define RT_IVF_LAUNCH(T, LISTS, LA) RT_IVF_LAUNCH_T(T, LISTS, false, LA, ivon::TagArgs<false>())
+    if (tags) {  // with la, of any number of sources
+        ivon::TagArgs<true> ta;
+        static_cast<ivon::TagSrc&>(ta) = *tags;
+        switch (dtype) {
+            case RT_F32: RT_IVF_LAUNCH_T(float, true, true, *la, ta); break;
+            case RT_F16: RT_IVF_LAUNCH_T(__half, true, true, *la, ta); break;
+            default: RT_IVF_LAUNCH_T(__hip_bfloat16, true, true, *la, ta); break;
+        }
+    } else if (la) {
         switch (dtype) {
             case RT_F32: RT_IVF_LAUNCH(float, true, *la); break;
             case RT_F16: RT_IVF_LAUNCH(__half, true, *la); break;
@@ -408,6 +443,7 @@ static int ivf_search(const void* queries, int64_t nq, const void* rows, int64_t
         }
     }
 #undef RT_IVF_LAUNCH
+#undef RT_IVF_LAUNCH_T
     int rc = check_launch("ivf_scan");
     if (rc) return rc;
     return ivon::launch_finish(partials, lists, k, out_scores, out_ids, 0, nq, st);
@@ -419,7 +455,7 @@ extern "C" int rt_ivf_topk(const void* queries, int64_t nq, const void* rows, in
                            const uint32_t* exclude_bits, int64_t exclude_words, float* out_scores,
                            int64_t* out_ids, void* workspace, size_t workspace_bytes, void* stream) {
     return ivf_search(queries, nq, rows, nx, d, dtype, list_offsets, nlist, nullptr, nx, row_pos, probes, nprobe,
-                      max_list_rows, k, exclude_bits, exclude_words, nullptr, out_scores, out_ids, workspace,
+                      max_list_rows, k, exclude_bits, exclude_words, nullptr, nullptr, out_scores, out_ids, workspace,
                       workspace_bytes, stream);
 }
 
@@ -430,15 +466,24 @@ extern "C" int rt_ivf_topk_lens(const void* queries, int64_t nq, const void* row
                                 int64_t* out_ids, void* workspace, size_t workspace_bytes, void* stream) {
     if (!list_len && nq > 0) return RT_ERR_INVALID;
     return ivf_search(queries, nq, rows, nx, d, dtype, list_offsets, nlist, list_len, n_pos, row_pos, probes, nprobe,
-                      max_list_rows, k, exclude_bits, exclude_words, nullptr, out_scores, out_ids, workspace,
+                      max_list_rows, k, exclude_bits, exclude_words, nullptr, nullptr, out_scores, out_ids, workspace,
                       workspace_bytes, stream);
 }
 
 static int ivf_search_lists(const void* queries, int64_t nq, const void* rows, int64_t nx, int d, int dtype,
                             const int64_t* list_offsets, int64_t nlist, const int64_t* list_len, int64_t n_pos,
                             const int32_t* row_pos, const int64_t* probes, int nprobe, int64_t max_list_rows, int k,
-                            const RtExclusionLists* lists, int n_lists, float* out_scores, int64_t* out_ids,
-                            void* workspace, size_t workspace_bytes, void* stream) {
+                            const RtExclusionLists* lists, int n_lists, const RtTagFilter* filter,
+                            float* out_scores, int64_t* out_ids, void* workspace, size_t workspace_bytes,
+                            void* stream) {
+    ivon::TagSrc tags{};
+    if (filter) {
+        if (!filter->item_tags && n_pos > 0) return RT_ERR_INVALID;
+        if ((reinterpret_cast<uintptr_t>(filter->item_tags) | reinterpret_cast<uintptr_t>(filter->any_of) |
+             reinterpret_cast<uintptr_t>(filter->none_of)) & 7)
+            return RT_ERR_INVALID;
+        tags = ivon::TagSrc{filter->item_tags, filter->any_of, filter->none_of};
+    }
     if (n_lists < 0 || (n_lists > 0 && !lists)) return RT_ERR_INVALID;
     if (n_lists > RT_ONLINE_MAX_EXCL_SOURCES) return RT_ERR_UNSUPPORTED;
     ivon::ListArgs<true> la{};
@@ -448,10 +493,10 @@ static int ivf_search_lists(const void* queries, int64_t nq, const void* rows, i
         if (!L.offsets || L.n_rows < 0 || (L.n_rows > 0 && !L.items)) return RT_ERR_INVALID;
         la.src[s] = ivon::ListSrc{L.offsets, L.items, L.rows, L.n_rows};
     }
-    // no source: the plain scan, bit for bit rt_ivf_topk without a bitmap
+    // no source and no filter: the plain scan, bit for bit rt_ivf_topk without a bitmap
     return ivf_search(queries, nq, rows, nx, d, dtype, list_offsets, nlist, list_len, n_pos, row_pos, probes, nprobe,
-                      max_list_rows, k, nullptr, 0, n_lists ? &la : nullptr, out_scores, out_ids, workspace,
-                      workspace_bytes, stream);
+                      max_list_rows, k, nullptr, 0, (n_lists || filter) ? &la : nullptr, filter ? &tags : nullptr,
+                      out_scores, out_ids, workspace, workspace_bytes, stream);
 }
 
 extern "C" int rt_ivf_topk_lists(const void* queries, int64_t nq, const void* rows, int64_t nx, int d, int dtype,
@@ -460,7 +505,8 @@ extern "C" int rt_ivf_topk_lists(const void* queries, int64_t nq, const void* ro
                                  const RtExclusionLists* lists, int n_lists, float* out_scores, int64_t* out_ids,
                                  void* workspace, size_t workspace_bytes, void* stream) {
     return ivf_search_lists(queries, nq, rows, nx, d, dtype, list_offsets, nlist, nullptr, nx, row_pos, probes, nprobe,
-                            max_list_rows, k, lists, n_lists, out_scores, out_ids, workspace, workspace_bytes, stream);
+                            max_list_rows, k, lists, n_lists, nullptr, out_scores, out_ids, workspace, workspace_bytes,
+                            stream);
 }
 
 extern "C" int rt_ivf_topk_lists_lens(const void* queries, int64_t nq, const void* rows, int64_t nx, int d, int dtype,
@@ -471,8 +517,20 @@ extern "C" int rt_ivf_topk_lists_lens(const void* queries, int64_t nq, const voi
                                       void* stream) {
     if (!list_len && nq > 0) return RT_ERR_INVALID;
     return ivf_search_lists(queries, nq, rows, nx, d, dtype, list_offsets, nlist, list_len, n_pos, row_pos, probes,
-                            nprobe, max_list_rows, k, lists, n_lists, out_scores, out_ids, workspace, workspace_bytes,
-                            stream);
+                            nprobe, max_list_rows, k, lists, n_lists, nullptr, out_scores, out_ids, workspace,
+                            workspace_bytes, stream);
+}
+
+extern "C" int rt_ivf_topk_tags(const void* queries, int64_t nq, const void* rows, int64_t nx, int d, int dtype,
+                                const int64_t* list_offsets, int64_t nlist, const int64_t* list_len, int64_t n_pos,
+                                const int32_t* row_pos, const int64_t* probes, int nprobe, int64_t max_list_rows,
+                                int k, const RtExclusionLists* lists, int n_lists, const RtTagFilter* filter,
+                                float* out_scores, int64_t* out_ids, void* workspace, size_t workspace_bytes,
+                                void* stream) {
+    // list_len == NULL: lists without slack, positions are valid in [0, nx)
+    return ivf_search_lists(queries, nq, rows, nx, d, dtype, list_offsets, nlist, list_len, list_len ? n_pos : nx,
+                            row_pos, probes, nprobe, max_list_rows, k, lists, n_lists, filter, out_scores, out_ids,
+                            workspace, workspace_bytes, stream);
 }
 
 extern "C" int rt_segment_mean_f32(const void* rows, int64_t n, int d, int dtype, const int64_t* offsets,

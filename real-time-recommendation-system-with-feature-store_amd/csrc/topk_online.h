@@ -37,6 +37,11 @@
 //        (query, source) in LDS, a 256-bit window per query built one tile
 //        ahead, one wave-uniform LDS read per query in the selection. An
 //        excluded row is never appended: nothing below changes.
+//      * category filter (rt_flatip_topk_online_tags, the TAGS instantiation, on
+//        top of LISTS): 64 bits of tags per row, one coalesced 8-byte load per
+//        lane and tile issued a tile ahead with the row stream, tested against
+//        the query's any_of / none_of masks in LDS. An ineligible row is never
+//        appended either.
 //      * the block then writes each query's best min(k, rows) entries, sorted,
 //        as composite keys (score key << 32 | ~id; 0 = none) to
 //        partials[query][rank][block] — rank-major, so that the finish reads
@@ -103,7 +108,26 @@ struct ListArgs<true> {
     int n;
 };
 
-template <int NQ, bool LISTS = false>
+// Tag filter (rt_flatip_topk_online_tags, rt_ivf_topk_tags): every item carries a
+// 64-bit set of categories, a query an any_of and a none_of mask; a row is
+// ELIGIBLE iff (any_of == 0 || (tags & any_of) != 0) && (tags & none_of) == 0.
+// An ineligible row is never appended — one more term of `pass`, next to the
+// exclusions. any_of / none_of may be null (all 0).
+struct TagSrc {
+    const uint64_t* item_tags;
+    const uint64_t* any_of;
+    const uint64_t* none_of;
+};
+template <bool TAGS>
+struct TagArgs {};
+template <>
+struct TagArgs<true> : TagSrc {};
+
+__device__ __forceinline__ bool tag_eligible(uint64_t tags, uint64_t any_of, uint64_t none_of) {
+    return (any_of == 0ull || (tags & any_of) != 0ull) && (tags & none_of) == 0ull;
+}
+
+template <int NQ, bool LISTS = false, bool TAGS = false>
 struct Lds {
     static constexpr int kStage = kWavesS * kStageBytes;
     static constexpr int kCand = NQ * kCap * static_cast<int>(sizeof(Cand));
@@ -112,8 +136,11 @@ struct Lds {
     // lists: cursor + end (int64) and next item (int32) per (query, source); two windows
     static constexpr int kPairs = NQ * kMaxSrc;
     static constexpr int kLists = LISTS ? kPairs * (8 + 8 + 4) + 2 * NQ * kWinWords * 4 : 0;
-    static constexpr int kBytes = kStage + kCand + kQuery + kHist + kLists;
+    // tags: any_of and none_of per query (uint64), behind the list state
+    static constexpr int kTags = TAGS ? NQ * 16 : 0;
+    static constexpr int kBytes = kStage + kCand + kQuery + kHist + kLists + kTags;
     static_assert(kLists % 8 == 0, "online: the list state holds 8-byte words");
+    static_assert((kBytes - kTags) % 8 == 0, "online: the masks behind the list state are 8-byte words");
     static_assert(2 * (kBytes + 128) <= 163840, "online: two blocks per CU");
 };
 
@@ -363,14 +390,17 @@ __device__ __forceinline__ void write_block_list(Cand* buf, int n, int k, uint32
 }
 
 // LISTS: the exclusions are `la`'s CSR lists (excl is not read); otherwise the
-// optional dense bitmap `excl`.
-template <typename T, int NQ, bool LISTS>
+// optional dense bitmap `excl`. TAGS: `ta`'s tag filter on top (tags indexed by
+// row): the lane's 8 bytes are one coalesced load per tile, issued one tile
+// ahead in front of the tile's row stream — older than every load the tile
+// waits for, so the selection finds them in registers; the masks sit in LDS.
+template <typename T, int NQ, bool LISTS, bool TAGS = false>
 __global__ __launch_bounds__(kThreads, 2) void flatip_online_scan(
     const T* __restrict__ Q, int nq, const char* __restrict__ X, int64_t nx, int d, int k,
     const uint32_t* __restrict__ excl, int64_t excl_words, int64_t rows_per_block, int blocks,
-    uint64_t* __restrict__ partials, const ListArgs<LISTS> la) {
+    uint64_t* __restrict__ partials, const ListArgs<LISTS> la, const TagArgs<TAGS> ta) {
     constexpr int EPU = 16 / static_cast<int>(sizeof(T));
-    __shared__ __attribute__((aligned(16))) char lds[Lds<NQ, LISTS>::kBytes];
+    __shared__ __attribute__((aligned(16))) char lds[Lds<NQ, LISTS, TAGS>::kBytes];
     __shared__ int cnt[kMaxNq];
     __shared__ float thr[kMaxNq];
     char* const stage = lds + (threadIdx.x >> 6) * kStageBytes;
@@ -401,6 +431,19 @@ __global__ __launch_bounds__(kThreads, 2) void flatip_online_scan(
 
     uint4 R[kStepUnits];
     load_step(R, w, 0, 0);
+    // TAGS: the masks of query qi at tmask[2 qi], tmask[2 qi + 1]; tg_next = the
+    // tags of this lane's row of the tile after the one being scored
+    uint64_t* const tmask = reinterpret_cast<uint64_t*>(lds + Lds<NQ, LISTS>::kBytes);
+    uint64_t tg_next = 0ull;
+    if constexpr (TAGS) {
+        if (threadIdx.x < 2 * NQ) {
+            const int qi = threadIdx.x >> 1;
+            const uint64_t* m = (threadIdx.x & 1) ? ta.none_of : ta.any_of;
+            tmask[threadIdx.x] = (m && qi < nq) ? m[qi] : 0ull;
+        }
+        const int64_t row0 = w.row_begin + threadIdx.x;
+        if (row0 < w.row_end) tg_next = ta.item_tags[row0];
+    }
     ListState ls{};
     if constexpr (LISTS) {
         // while the first step is in flight: the cursors and tile 0's window
@@ -443,11 +486,17 @@ __global__ __launch_bounds__(kThreads, 2) void flatip_online_scan(
 #pragma unroll
         for (int qi = 0; qi < NQ; ++qi) th[qi] = thr[qi];
 
+        const int64_t row = w.row_begin + static_cast<int64_t>(t) * kTileRows + wave * 64 + lane;
+        const uint64_t tg = tg_next;
+        if constexpr (TAGS) {
+            tg_next = 0ull;
+            if (row + kTileRows < w.row_end) tg_next = ta.item_tags[row + kTileRows];
+        }
+
         float acc[NQ];
         score_tile<T, NQ>(R, w, t, stage, qs, d, acc);
 
         // ---- selection: appends of at most one entry per row and query ----
-        const int64_t row = w.row_begin + static_cast<int64_t>(t) * kTileRows + wave * 64 + lane;
         const bool valid = row < w.row_end;
         int mine_over = 0;
 #pragma unroll
@@ -464,6 +513,8 @@ __global__ __launch_bounds__(kThreads, 2) void flatip_online_scan(
                     // the per-lane global load `append` warns of: a call with
                     // exclude_bits loses the one-step-ahead streaming
                     pass = ((excl[qi * excl_words + (row >> 5)] >> (row & 31)) & 1u) == 0u;
+                if constexpr (TAGS)  // two wave-uniform 8-byte LDS reads
+                    pass = pass && tag_eligible(tg, tmask[2 * qi], tmask[2 * qi + 1]);
                 mine_over |= append<false>(pass, &cnt[qi], cand + qi * kCap, acc[qi], static_cast<uint32_t>(row));
             }
         }
@@ -618,16 +669,16 @@ inline size_t workspace_bytes(int64_t nq, int k, const OnlinePlan& p) {
     return static_cast<size_t>(nq) * k * p.blocks * sizeof(uint64_t);
 }
 
-template <typename T, bool LISTS = false>
+template <typename T, bool LISTS = false, bool TAGS = false>
 int launch_scan(const void* Q, int nq, const void* X, int64_t nx, int d, int k, const uint32_t* excl,
                 int64_t excl_words, const OnlinePlan& p, uint64_t* partials, hipStream_t st,
-                const ListArgs<LISTS>& la = ListArgs<LISTS>()) {
+                const ListArgs<LISTS>& la = ListArgs<LISTS>(), const TagArgs<TAGS>& ta = TagArgs<TAGS>()) {
     const dim3 grid(static_cast<unsigned>(p.blocks)), block(kThreads);
     const T* q = static_cast<const T*>(Q);
     const char* x = static_cast<const char*>(X);
 #define RT_ONLINE_LAUNCH(NQ)                                                                                       \
-    hipLaunchKernelGGL((flatip_online_scan<T, NQ, LISTS>), grid, block, 0, st, q, nq, x, nx, d, k, excl,           \
-                       excl_words, p.rows_per_block, p.blocks, partials, la)
+    hipLaunchKernelGGL((flatip_online_scan<T, NQ, LISTS, TAGS>), grid, block, 0, st, q, nq, x, nx, d, k, excl,     \
+                       excl_words, p.rows_per_block, p.blocks, partials, la, ta)
     if (nq <= 1) RT_ONLINE_LAUNCH(1);
     else if (nq <= 2) RT_ONLINE_LAUNCH(2);
     else if (nq <= 4) RT_ONLINE_LAUNCH(4);

@@ -1,5 +1,6 @@
 // C ABI of the online (small-batch) Flat-IP top-K: rt_flatip_topk_online,
-// rt_flatip_topk_online_lists, their plan and workspace queries. The kernels
+// rt_flatip_topk_online_lists, rt_flatip_topk_online_tags, their plan and
+// workspace queries. The kernels
 // and their launchers live in topk_online.h, which csrc/ivf.hip shares.
 #include "topk_online.h"
 
@@ -27,10 +28,11 @@ extern "C" size_t rt_flatip_topk_online_workspace_bytes(int64_t nq, int64_t nx, 
 
 static_assert(RT_ONLINE_MAX_EXCL_SOURCES == on::kMaxSrc, "rtrec_hip.h restates the kernel's limits");
 
-// both entry points: the dense bitmap (la == nullptr) or the lists
+// the entry points: the dense bitmap (la == nullptr) or the lists; tags != nullptr:
+// the tag filter on top of the lists (la != nullptr then, with any number of sources)
 static int online_search(const void* queries, int64_t nq, const void* items, int64_t nx, int d, int dtype, int k,
                          const uint32_t* exclude_bits, int64_t exclude_words, const on::ListArgs<true>* la,
-                         int64_t id_offset, float* out_scores, int64_t* out_ids, void* workspace,
+                         const on::TagSrc* tags, int64_t id_offset, float* out_scores, int64_t* out_ids, void* workspace,
                          size_t workspace_bytes, void* stream) {
     if (nq < 0 || nx < 0 || d <= 0 || k <= 0) return RT_ERR_INVALID;
     if (nq == 0) return RT_OK;
@@ -51,7 +53,15 @@ static int online_search(const void* queries, int64_t nq, const void* items, int
     if (nx > 0) {
         int rc;
         const int n = static_cast<int>(nq);
-        if (la) {
+        if (tags) {
+            on::TagArgs<true> ta;
+            static_cast<on::TagSrc&>(ta) = *tags;
+            switch (dtype) {
+                case RT_F32: rc = on::launch_scan<float, true, true>(queries, n, items, nx, d, k, nullptr, 0, p, partials, st, *la, ta); break;
+                case RT_F16: rc = on::launch_scan<__half, true, true>(queries, n, items, nx, d, k, nullptr, 0, p, partials, st, *la, ta); break;
+                default: rc = on::launch_scan<__hip_bfloat16, true, true>(queries, n, items, nx, d, k, nullptr, 0, p, partials, st, *la, ta); break;
+            }
+        } else if (la) {
             switch (dtype) {
                 case RT_F32: rc = on::launch_scan<float, true>(queries, n, items, nx, d, k, nullptr, 0, p, partials, st, *la); break;
                 case RT_F16: rc = on::launch_scan<__half, true>(queries, n, items, nx, d, k, nullptr, 0, p, partials, st, *la); break;
@@ -74,14 +84,23 @@ extern "C" int rt_flatip_topk_online(const void* queries, int64_t nq, const void
                                      int dtype, int k, const uint32_t* exclude_bits, int64_t exclude_words,
                                      int64_t id_offset, float* out_scores, int64_t* out_ids, void* workspace,
                                      size_t workspace_bytes, void* stream) {
-    return online_search(queries, nq, items, nx, d, dtype, k, exclude_bits, exclude_words, nullptr, id_offset,
+    return online_search(queries, nq, items, nx, d, dtype, k, exclude_bits, exclude_words, nullptr, nullptr, id_offset,
                          out_scores, out_ids, workspace, workspace_bytes, stream);
 }
 
-extern "C" int rt_flatip_topk_online_lists(const void* queries, int64_t nq, const void* items, int64_t nx, int d,
-                                           int dtype, int k, const RtExclusionLists* lists, int n_lists,
-                                           int64_t id_offset, float* out_scores, int64_t* out_ids, void* workspace,
-                                           size_t workspace_bytes, void* stream) {
+// the lists entry points: `filter` is null for rt_flatip_topk_online_lists
+static int online_search_lists(const void* queries, int64_t nq, const void* items, int64_t nx, int d, int dtype,
+                               int k, const RtExclusionLists* lists, int n_lists, const RtTagFilter* filter,
+                               int64_t id_offset, float* out_scores, int64_t* out_ids, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+    on::TagSrc tags{};
+    if (filter) {
+        if (!filter->item_tags && nx > 0) return RT_ERR_INVALID;
+        if ((reinterpret_cast<uintptr_t>(filter->item_tags) | reinterpret_cast<uintptr_t>(filter->any_of) |
+             reinterpret_cast<uintptr_t>(filter->none_of)) & 7)
+            return RT_ERR_INVALID;
+        tags = on::TagSrc{filter->item_tags, filter->any_of, filter->none_of};
+    }
     if (n_lists < 0 || (n_lists > 0 && !lists)) return RT_ERR_INVALID;
     if (n_lists > RT_ONLINE_MAX_EXCL_SOURCES) return RT_ERR_UNSUPPORTED;
     on::ListArgs<true> la{};
@@ -91,7 +110,23 @@ extern "C" int rt_flatip_topk_online_lists(const void* queries, int64_t nq, cons
         if (!L.offsets || L.n_rows < 0 || (L.n_rows > 0 && !L.items)) return RT_ERR_INVALID;
         la.src[s] = on::ListSrc{L.offsets, L.items, L.rows, L.n_rows};
     }
-    // no source: the plain scan, bit for bit rt_flatip_topk_online without a bitmap
-    return online_search(queries, nq, items, nx, d, dtype, k, nullptr, 0, n_lists ? &la : nullptr, id_offset,
-                         out_scores, out_ids, workspace, workspace_bytes, stream);
+    // no source and no filter: the plain scan, bit for bit rt_flatip_topk_online without a bitmap
+    return online_search(queries, nq, items, nx, d, dtype, k, nullptr, 0, (n_lists || filter) ? &la : nullptr,
+                         filter ? &tags : nullptr, id_offset, out_scores, out_ids, workspace, workspace_bytes, stream);
+}
+
+extern "C" int rt_flatip_topk_online_lists(const void* queries, int64_t nq, const void* items, int64_t nx, int d,
+                                           int dtype, int k, const RtExclusionLists* lists, int n_lists,
+                                           int64_t id_offset, float* out_scores, int64_t* out_ids, void* workspace,
+                                           size_t workspace_bytes, void* stream) {
+    return online_search_lists(queries, nq, items, nx, d, dtype, k, lists, n_lists, nullptr, id_offset, out_scores,
+                               out_ids, workspace, workspace_bytes, stream);
+}
+
+extern "C" int rt_flatip_topk_online_tags(const void* queries, int64_t nq, const void* items, int64_t nx, int d,
+                                          int dtype, int k, const RtExclusionLists* lists, int n_lists,
+                                          const RtTagFilter* filter, int64_t id_offset, float* out_scores,
+                                          int64_t* out_ids, void* workspace, size_t workspace_bytes, void* stream) {
+    return online_search_lists(queries, nq, items, nx, d, dtype, k, lists, n_lists, filter, id_offset, out_scores,
+                               out_ids, workspace, workspace_bytes, stream);
 }

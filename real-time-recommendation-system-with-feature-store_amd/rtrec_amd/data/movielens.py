@@ -146,6 +146,25 @@ def create_movie_features(movies: pd.DataFrame, movie_idx: np.ndarray, normalize
     return feats
 
 
+def movie_category_tags(movies: pd.DataFrame, movie_idx: np.ndarray) -> Tuple[List[str], np.ndarray]:
+    """``(vocabulary, tags)`` for the retrieval indexes' category filters (config key
+    ``categories``, ``build(..., item_categories=tags)``): the vocabulary is the
+    genre names of the ``genre_*`` columns ``load_movies`` builds, in column
+    order; ``tags`` is uint64 ``[len(movie_idx)]``, bit j set where the movie has
+    genre j (multi-hot: a movie belongs to several), 0 for an unknown movie."""
+    genre_cols = [c for c in movies.columns if c.startswith("genre_")]
+    if len(genre_cols) > 64:
+        raise ValueError(f"{len(genre_cols)} genre columns: the category filters take at most 64")
+    tags = np.zeros(len(movie_idx), dtype=np.uint64)
+    m = movies.set_index("movie_idx")
+    idx = np.asarray(movie_idx)
+    present = np.isin(idx, m.index.to_numpy())
+    bits = m.loc[idx[present]][genre_cols].to_numpy(np.uint64)
+    weights = np.uint64(1) << np.arange(len(genre_cols), dtype=np.uint64)
+    tags[present] = (bits * weights).sum(axis=1, dtype=np.uint64)
+    return [c[len("genre_"):] for c in genre_cols], tags
+
+
 def get_user_positive_items(interactions: pd.DataFrame) -> Dict[int, List[int]]:
     """movielens.py:469-485 (ALL interacted items, any label)."""
     return {int(u): g["movie_idx"].tolist() for u, g in interactions.groupby("user_idx")}

@@ -221,7 +221,7 @@ def flatip_topk_online(queries: torch.Tensor, items: torch.Tensor, k: int,
                        exclude_bits: Optional[torch.Tensor] = None, id_offset: int = 0,
                        out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
                        workspace_buf: Optional[torch.Tensor] = None,
-                       exclude_lists=None) -> Tuple[torch.Tensor, torch.Tensor]:
+                       exclude_lists=None, tag_filter=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """:func:`flatip_topk` for 1..8 queries and k <= 128 (rt_flatip_topk_online):
     the same results, from one streaming pass over the corpus — the shape of
     the serving path (one user per request, src/serving/retrieval.py:141-197).
@@ -234,10 +234,20 @@ def flatip_topk_online(queries: torch.Tensor, items: torch.Tensor, k: int,
     ``offsets`` int64 ``[n_rows + 1]``, ``items`` int32 corpus positions
     ascending within a row (duplicates allowed, positions >= nx ignored),
     ``rows`` optional int64 ``[nq]``: query q skips CSR row ``rows[q]`` (default
-    q; a row outside the CSR: nothing) of every source."""
+    q; a row outside the CSR: nothing) of every source.
+
+    ``tag_filter`` (rt_flatip_topk_online_tags; composes with ``exclude_lists``,
+    not with ``exclude_bits``): ``(item_tags, any_of, none_of)`` — 64-bit category
+    sets per row ``[nx]`` and per-query masks ``[nq]`` (either may be None: all
+    0), int64 or uint64 device tensors. Row p is eligible for query q iff
+    ``(any_of[q] == 0 or item_tags[p] & any_of[q]) and not item_tags[p] &
+    none_of[q]``; the result is the search over the eligible rows, exact."""
     if exclude_lists is not None and exclude_bits is not None:
         raise ValueError("exclude_bits and exclude_lists are mutually exclusive")
+    if tag_filter is not None and exclude_bits is not None:
+        raise ValueError("exclude_bits and tag_filter are mutually exclusive (tag_filter_bitmap composes them)")
     sources = _exclusion_sources(exclude_lists, queries)
+    tags = _tag_filter(tag_filter, queries, items.shape[0] if items.dim() == 2 else 0, "flatip_topk_online")
     native.require_device(queries, items, what="flatip_topk_online")
     if queries.dim() != 2 or items.dim() != 2 or queries.shape[1] != items.shape[1]:
         raise ValueError(f"shape mismatch: queries {tuple(queries.shape)} items {tuple(items.shape)}")
@@ -258,7 +268,7 @@ def flatip_topk_online(queries: torch.Tensor, items: torch.Tensor, k: int,
     if ws is None:
         ws = workspace(queries.device, native.lib().rt_flatip_topk_online_workspace_bytes(nq, nx, d, dt, k),
                        "topk_online")
-    if exclude_lists is not None:
+    if exclude_lists is not None or tags is not None:
         for src in sources:
             native.require_device(*src, what="flatip_topk_online")
         # a source without items excludes nothing (and has no items pointer to give)
@@ -266,6 +276,11 @@ def flatip_topk_online(queries: torch.Tensor, items: torch.Tensor, k: int,
         arr = (native.ExclusionLists * native.ONLINE_MAX_EXCL_SOURCES)()
         for a, (offsets, its, rows) in zip(arr, sources):
             a.offsets, a.items, a.n_rows, a.rows = ptr(offsets), ptr(its), offsets.numel() - 1, ptr(rows)
+        if tags is not None:
+            call("rt_flatip_topk_online_tags", ptr(queries), nq, ptr(items) if nx else None, nx, d, dt, k, arr,
+                 len(sources), ctypes.byref(tags), id_offset, ptr(scores), ptr(ids), ptr(ws), ws.numel(),
+                 stream_of(queries))
+            return scores, ids
         call("rt_flatip_topk_online_lists", ptr(queries), nq, ptr(items) if nx else None, nx, d, dt, k, arr,
              len(sources), id_offset, ptr(scores), ptr(ids), ptr(ws), ws.numel(), stream_of(queries))
         return scores, ids
@@ -302,6 +317,65 @@ def _exclusion_sources(exclude_lists, queries: torch.Tensor):
             if rows.dim() != 1 or rows.numel() < queries.shape[0] or not rows.is_contiguous():
                 raise ValueError(f"exclusion rows must be a contiguous [nq = {queries.shape[0]}] tensor")
         out.append((offsets, its, rows))
+    return out
+
+
+def _tag_filter(tag_filter, queries: torch.Tensor, n_pos: int, what: str):
+    """``tag_filter`` of :func:`flatip_topk_online` / :func:`ivf_topk` as a
+    ``native.TagFilter`` (None: no filter); ``ValueError`` / ``TypeError`` for a
+    malformed one. The struct holds raw pointers: the caller's tuple keeps the
+    tensors alive for the call."""
+    if tag_filter is None:
+        return None
+    if len(tag_filter) != 3:
+        raise ValueError("tag_filter is (item_tags, any_of, none_of)")
+    item_tags, any_of, none_of = tag_filter
+    if item_tags is None:
+        raise ValueError("tag_filter needs item_tags")
+    nq = queries.shape[0]
+    for name, t, n in (("item_tags", item_tags, n_pos), ("any_of", any_of, nq), ("none_of", none_of, nq)):
+        if t is None:
+            continue
+        if t.dtype not in (torch.int64, torch.uint64):
+            raise TypeError(f"tag_filter: {name} must be int64 or uint64 (64-bit category sets)")
+        if t.dim() != 1 or t.numel() < n or not t.is_contiguous():
+            raise ValueError(f"tag_filter: {name} must be a contiguous 1-d tensor of at least {n} words")
+    native.require_device(item_tags, any_of, none_of, what=what)
+    out = native.TagFilter()
+    out.item_tags, out.any_of, out.none_of = ptr(item_tags), ptr(any_of), ptr(none_of)
+    return out
+
+
+def tag_filter_bitmap(item_tags: torch.Tensor, any_of: Optional[torch.Tensor], none_of: Optional[torch.Tensor],
+                      nq: int, n_items: Optional[int] = None, out: Optional[torch.Tensor] = None,
+                      accumulate: bool = False) -> torch.Tensor:
+    """The tag filter as an exclusion bitmap (rt_tag_filter_bitmap): int32 ``[nq,
+    ceil(n_items / 32)]``, bit p of row q set for every item p < ``n_items`` that
+    is NOT eligible for query q — what ``exclude_bits`` of :func:`flatip_topk`,
+    :func:`ivf_topk` and :func:`ivf_topk_batch` takes. ``out`` with ``accumulate``:
+    OR into an existing bitmap (e.g. one of excluded ids); otherwise every word
+    is overwritten, pad bits zero. One thread per word, no ``[nq, n_items]``
+    intermediate."""
+    n_items = item_tags.numel() if n_items is None else int(n_items)
+    nq = int(nq)
+    for name, t, n in (("item_tags", item_tags, n_items), ("any_of", any_of, nq), ("none_of", none_of, nq)):
+        if t is None:
+            continue
+        if t.dtype not in (torch.int64, torch.uint64):
+            raise TypeError(f"tag_filter_bitmap: {name} must be int64 or uint64 (64-bit category sets)")
+        if t.dim() != 1 or t.numel() < n or not t.is_contiguous():
+            raise ValueError(f"tag_filter_bitmap: {name} must be a contiguous 1-d tensor of at least {n} words")
+    native.require_device(item_tags, any_of, none_of, out, what="tag_filter_bitmap")
+    words = (n_items + 31) // 32
+    if out is None:
+        if accumulate:
+            raise ValueError("tag_filter_bitmap: accumulate needs the bitmap to OR into (out)")
+        out = torch.empty((nq, words), dtype=torch.int32, device=item_tags.device)
+    elif out.dtype not in (torch.int32, torch.uint32) or out.dim() != 2 or out.shape[0] != nq \
+            or out.shape[1] < words or not out.is_contiguous():
+        raise ValueError(f"out must be contiguous int32/uint32 [{nq}, >= {words}]")
+    call("rt_tag_filter_bitmap", ptr(item_tags) if n_items else None, n_items, ptr(any_of), ptr(none_of), nq,
+         ptr(out), out.shape[1], 1 if accumulate else 0, stream_of(item_tags))
     return out
 
 
@@ -553,7 +627,7 @@ def ivf_topk(queries: torch.Tensor, rows: torch.Tensor, list_offsets: torch.Tens
              out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
              workspace_buf: Optional[torch.Tensor] = None,
              exclude_lists=None, list_len: Optional[torch.Tensor] = None,
-             n_pos: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+             n_pos: Optional[int] = None, tag_filter=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Top-k over the union of the probed lists (rt_ivf_topk): (scores [nq, k] f32,
     original positions [nq, k] int64) in (score desc, position asc) order,
     (-FLT_MAX, -1) pads. ``rows`` [nx, d] are stored list-contiguous, list l =
@@ -568,10 +642,19 @@ def ivf_topk(queries: torch.Tensor, rows: torch.Tensor, list_offsets: torch.Tens
     ``list_len[l]`` of its ``[list_offsets[l], list_offsets[l + 1])``, positions
     are valid in ``[0, n_pos)`` (the bitmap's width), ``max_list_rows`` bounds the
     largest capacity.
+    ``tag_filter`` (rt_ivf_topk_tags; composes with ``exclude_lists``, not with
+    ``exclude_bits``): ``(item_tags, any_of, none_of)`` as for
+    :func:`flatip_topk_online`, ``item_tags`` indexed by ORIGINAL position. The
+    result is exact over the eligible rows of the PROBED lists (as a filtered
+    Faiss IVF search is), not of the corpus.
     Batches above 32,768 queries run in chunks."""
     if exclude_lists is not None and exclude_bits is not None:
         raise ValueError("exclude_bits and exclude_lists are mutually exclusive")
+    if tag_filter is not None and exclude_bits is not None:
+        raise ValueError("exclude_bits and tag_filter are mutually exclusive (tag_filter_bitmap composes them)")
     sources = _exclusion_sources(exclude_lists, queries)
+    tags = _tag_filter(tag_filter, queries,
+                       int(n_pos) if n_pos is not None else (rows.shape[0] if rows.dim() == 2 else 0), "ivf_topk")
     native.require_device(queries, rows, list_offsets, row_pos, probes, exclude_bits, list_len, what="ivf_topk")
     for src in sources:
         native.require_device(*src, what="ivf_topk")
@@ -617,7 +700,7 @@ def ivf_topk(queries: torch.Tensor, rows: torch.Tensor, list_offsets: torch.Tens
         if ws is None:
             ws = workspace(queries.device,
                            native.lib().rt_ivf_topk_workspace_bytes(b - a, nprobe, int(max_list_rows), k), "ivf_topk")
-        if exclude_lists is not None:
+        if exclude_lists is not None or tags is not None:
             # query a + q of the chunk: rows[a + q] of a source with rows, else CSR row a + q —
             # the offsets advanced by a (a source the chunk lies past: dropped)
             arr = (native.ExclusionLists * native.ONLINE_MAX_EXCL_SOURCES)()
@@ -633,6 +716,16 @@ def ivf_topk(queries: torch.Tensor, rows: torch.Tensor, list_offsets: torch.Tens
                 s = arr[n_src]
                 s.offsets, s.items, s.n_rows, s.rows = ptr(offsets), ptr(its), n_rows, ptr(xrows)
                 n_src += 1
+            if tags is not None:
+                chunk = native.TagFilter()
+                chunk.item_tags = tags.item_tags
+                chunk.any_of = ptr(tag_filter[1][a:b]) if tag_filter[1] is not None else None
+                chunk.none_of = ptr(tag_filter[2][a:b]) if tag_filter[2] is not None else None
+                call("rt_ivf_topk_tags", ptr(queries[a:b]), b - a, ptr(rows) if nx else None, nx, d, dt,
+                     ptr(list_offsets), nlist, ptr(list_len), int(n_pos) if lens else nx,
+                     ptr(row_pos) if nx else None, ptr(probes[a:b]), nprobe, int(max_list_rows), k, arr, n_src,
+                     ctypes.byref(chunk), ptr(scores[a:b]), ptr(ids[a:b]), ptr(ws), ws.numel(), stream_of(queries))
+                continue
             call("rt_ivf_topk_lists" + suffix, ptr(queries[a:b]), b - a, ptr(rows) if nx else None, nx, d, dt,
                  ptr(list_offsets), nlist, *lens, ptr(row_pos) if nx else None, ptr(probes[a:b]), nprobe,
                  int(max_list_rows), k, arr, n_src, ptr(scores[a:b]), ptr(ids[a:b]), ptr(ws), ws.numel(),

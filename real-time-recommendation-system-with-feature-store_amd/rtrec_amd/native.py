@@ -104,6 +104,12 @@ class ExclusionLists(ctypes.Structure):
     _fields_ = [("offsets", vp), ("items", vp), ("n_rows", c_i64), ("rows", vp)]
 
 
+class TagFilter(ctypes.Structure):
+    """RtTagFilter: per-item category sets and per-query masks of rt_flatip_topk_online_tags /
+    rt_ivf_topk_tags (device pointers to uint64 words; any_of / none_of may be NULL)."""
+    _fields_ = [("item_tags", vp), ("any_of", vp), ("none_of", vp)]
+
+
 GRAD_FOLD_MAX = 8    # RT_GRAD_FOLD_MAX
 DW_JOINT_MAX = 6     # argument sets of one rt_linear_bwd_dw_f32_joint call
 
@@ -128,6 +134,13 @@ SIGNATURES = {
                                       c_size, vp]),
     "rt_flatip_topk_online_lists": (c_int, [vp, c_i64, vp, c_i64, c_int, c_int, c_int,
                                             ctypes.POINTER(ExclusionLists), c_int, c_i64, vp, vp, vp, c_size, vp]),
+    "rt_flatip_topk_online_tags": (c_int, [vp, c_i64, vp, c_i64, c_int, c_int, c_int,
+                                           ctypes.POINTER(ExclusionLists), c_int, ctypes.POINTER(TagFilter), c_i64,
+                                           vp, vp, vp, c_size, vp]),
+    "rt_ivf_topk_tags": (c_int, [vp, c_i64, vp, c_i64, c_int, c_int, vp, c_i64, vp, c_i64, vp, vp, c_int, c_i64,
+                                 c_int, ctypes.POINTER(ExclusionLists), c_int, ctypes.POINTER(TagFilter), vp, vp, vp,
+                                 c_size, vp]),
+    "rt_tag_filter_bitmap": (c_int, [vp, c_i64, vp, vp, c_i64, vp, c_i64, c_int, vp]),
     "rt_ivf_topk_tuning": (c_int, [c_int]),
     "rt_ivf_topk_plan": (c_int, [c_i64, c_int, c_i64, vp]),
     "rt_ivf_topk_workspace_bytes": (c_size, [c_i64, c_int, c_i64, c_int]),

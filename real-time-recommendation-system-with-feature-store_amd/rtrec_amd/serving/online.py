@@ -222,10 +222,12 @@ class OnlineRecommender:
         a.out = native.ptr(self._searcher._d_q32)
         kernels.tower_infer(a, native.stream_of(self._d_x))
 
-    def _sequence(self, nq: int, k: int, by_ids: bool, items: bool = False, seen: bool = False):
+    def _sequence(self, nq: int, k: int, by_ids: bool, items: bool = False, seen: bool = False,
+                  tags: bool = False):
         """The stream-ordered chain of one call (k = 0: embed only). ``items``: the
         per-request lists staged in the searcher's pinned CSR; ``seen``: the resident
-        seen-items CSR, its rows the device ids the tower gather reads."""
+        seen-items CSR, its rows the device ids the tower gather reads; ``tags``: the
+        category masks staged in the searcher's pinned mask buffer."""
         if by_ids:
             self._d_ids[:nq].copy_(self._h_ids[:nq], non_blocking=True)
         else:
@@ -240,7 +242,9 @@ class OnlineRecommender:
             if items:
                 self._searcher._upload_lists()
                 sources.append(self._searcher._list_source())
-            self._searcher._device_chain(nq, k, sources)
+            if tags:
+                self._searcher._d_tm.copy_(self._searcher._h_tm, non_blocking=True)
+            self._searcher._device_chain(nq, k, sources, tags=tags)
             self._searcher._download(nq, k)
 
     # -- seen items ----------------------------------------------------------------
@@ -325,7 +329,8 @@ class OnlineRecommender:
         flat = getattr(self.index, "_flat", None)
         return self.index if flat is None else flat
 
-    def _run(self, x: Optional[Rows], ids: Optional[np.ndarray], k: int, items: bool = False, seen: bool = False):
+    def _run(self, x: Optional[Rows], ids: Optional[np.ndarray], k: int, items: bool = False, seen: bool = False,
+             tags: bool = False):
         """Stage the rows, run / replay the chain, synchronise. Under ``lock``."""
         by_ids = ids is not None
         nq = len(ids) if by_ids else x.shape[0]
@@ -341,8 +346,11 @@ class OnlineRecommender:
         nprobe = getattr(self._searcher, "_nprobe", 0)   # OnlineIVFSearcher: read from the index at this call
         if k and nprobe:
             key = (nq, k, by_ids, items, seen, nprobe)
+        seq = (nq, k, by_ids, items, seen, tags)
+        if tags:   # one more flag, at the end: one graph serves every mask value
+            key = (nq, k, by_ids, items, seen) + key[5:] + ("tags",)
         if os.environ.get("RTREC_ONLINE_GRAPH", "1") == "0":
-            self._sequence(nq, k, by_ids, items, seen)
+            self._sequence(*seq)
         else:
             g = self._graphs.get(key)
             if g is not None:
@@ -350,11 +358,11 @@ class OnlineRecommender:
             else:
                 # as OnlineSearcher.search: the first call at a shape answers from an
                 # eager run, then the chain is captured (a capture executes nothing)
-                self._sequence(nq, k, by_ids, items, seen)
+                self._sequence(*seq)
                 stream.synchronize()
                 g = torch.cuda.CUDAGraph()
                 with _capture(g):
-                    self._sequence(nq, k, by_ids, items, seen)
+                    self._sequence(*seq)
                 while len(self._graphs) >= self.MAX_GRAPHS:
                     self._graphs.popitem(last=False)
                 self._graphs[key] = g
@@ -385,7 +393,8 @@ class OnlineRecommender:
             return self._embed_any(x, ids)
 
     def recommend(self, user_features: Optional[Features] = None, *, user_ids=None, k: int = 10,
-                  filter_ids: Optional[List[str]] = None, exclude_items=None, exclude_seen: bool = False
+                  filter_ids: Optional[List[str]] = None, exclude_items=None, exclude_seen: bool = False,
+                  filter_categories=None, exclude_categories=None
                   ) -> Tuple[List[List[str]], List[List[float]]]:
         """``(ids, scores)`` lists, as ``index.search(embed(...), k, filter_ids)``.
 
@@ -397,7 +406,11 @@ class OnlineRecommender:
         252-282); the scan reads the resident CSR through the device ids of the
         tower gather, so a request uploads no history. Both may be given: two
         sources of one scan. ``ValueError`` without ``user_ids`` or before
-        ``set_seen``."""
+        ``set_seen``.
+        ``filter_categories`` / ``exclude_categories`` (the request schema's
+        ``filter_categories``): as ``HipFlatIPIndex.search`` — tested by the same
+        scan, composing with both exclusion sources; one more fixed-size H2D copy
+        in the chain, one graph for every mask value."""
         x, ids = self._rows_of(user_features, user_ids)
         idx = self.index
         if idx.index is None:
@@ -411,6 +424,9 @@ class OnlineRecommender:
         if k_search <= 0 or nq == 0:
             return [[] for _ in range(nq)], [[] for _ in range(nq)]
         items = exclude_items is not None
+        masks = idx._query_masks(filter_categories, exclude_categories, nq)
+        cats = {} if masks is None else dict(filter_categories=filter_categories,
+                                             exclude_categories=exclude_categories)
         with self.lock:
             s = self._searcher
             resident = k_search <= OnlineSearcher.MAX_K and nq <= self.max_batch
@@ -423,7 +439,7 @@ class OnlineRecommender:
                     if exclude_seen:
                         for q, u in enumerate(ids):
                             excl[q].extend(self._history(int(u)))
-                return idx.search(self._embed_any(x, ids), k, filter_ids, exclude_ids=excl)
+                return idx.search(self._embed_any(x, ids), k, filter_ids, exclude_ids=excl, **cats)
             if s.index is not self._searched():
                 raise ValueError("the index switched between its lists and the Flat fallback (or was rebuilt "
                                  "onto another inner index) since this recommender was made: make a new one")
@@ -434,7 +450,9 @@ class OnlineRecommender:
                 self._map_seen()  # positions moved (remove / build / load): new tensors, no graph holds the old
                 for key in [key for key in self._graphs if len(key) > 3 and key[4]]:
                     del self._graphs[key]
-            self._run(x, ids, k_search, items, exclude_seen)
+            if masks is not None:
+                s._stage_tags(nq, masks)
+            self._run(x, ids, k_search, items, exclude_seen, tags=masks is not None)
             n = nq * k_search
             return _lists_from_positions(s._h_s_np[:n].reshape(nq, k_search), s._h_p_np[:n].reshape(nq, k_search),
                                          idx.id_map, k, filter_ids)

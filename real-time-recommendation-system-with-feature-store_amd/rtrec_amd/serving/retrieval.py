@@ -121,9 +121,162 @@ class _HbmIndex(IndexBase):
         self._reset_ids()
         self.current_size = 0
         self._generation = 0   # bumped by build / add / load / remove (OnlineSearcher validity)
+        self._init_categories()
 
     def _check_metric(self):
         """Raise for a metric (or a metric / storage pair) the class does not serve."""
+
+    # -- categories (the request schema's filter_categories, src/api/schemas.py:21-34) --
+    MAX_CATEGORIES = 64
+
+    def _init_categories(self):
+        """The ``categories`` option: the vocabulary (at most 64 names; category j is
+        bit j of an item's tags), or absent — the feature is off."""
+        names = self.config.get("categories")
+        self.categories: Optional[List[str]] = None if names is None else [str(c) for c in names]
+        # [capacity] int64 on the device, by position; the first current_size are valid.
+        # It moves (a new tensor) only where the generation is bumped too.
+        self._tags: Optional[torch.Tensor] = None
+        self._cat_bit: Dict[str, int] = {}
+        if self.categories is None:
+            return
+        if len(self.categories) > self.MAX_CATEGORIES or len(set(self.categories)) != len(self.categories):
+            raise ValueError(f"categories: at most {self.MAX_CATEGORIES} distinct names, got {len(self.categories)}")
+        self._check_categories()
+        self._cat_bit = {c: j for j, c in enumerate(self.categories)}
+
+    def _check_categories(self):
+        """Raise where the class (or its mode) does not serve category filters."""
+        if self._l2:
+            raise ValueError("categories: the filters are served for the inner-product metrics ('cosine', "
+                             "'inner_product'), not in the L2 mode")
+
+    def _need_categories(self, keyword: str):
+        if self.categories is None:
+            raise ValueError(f"{keyword}: this index has no category vocabulary — set the config key 'categories' "
+                             "(a list of at most 64 names)")
+
+    def _mask_of(self, names) -> int:
+        m = 0
+        for c in names:
+            bit = self._cat_bit.get(c)
+            if bit is None:
+                raise ValueError(f"unknown category {c!r} (config key 'categories': {self.categories})")
+            m |= 1 << bit
+        return m
+
+    def _item_tags(self, item_categories, n: int) -> np.ndarray:
+        """``item_categories`` of ``n`` items as uint64 masks: None = untagged; an
+        integer array of masks; or per item a sequence of category names."""
+        if item_categories is None:
+            return np.zeros(n, np.uint64)
+        self._need_categories("item_categories")
+        if isinstance(item_categories, torch.Tensor):
+            item_categories = item_categories.cpu().numpy()
+        if isinstance(item_categories, np.ndarray) and item_categories.dtype.kind in "iu":
+            masks = item_categories.reshape(-1).astype(np.int64, copy=False).view(np.uint64) \
+                if item_categories.dtype.kind == "i" else item_categories.reshape(-1).astype(np.uint64)
+        else:
+            item_categories = list(item_categories)
+            if item_categories and all(isinstance(c, (int, np.integer)) for c in item_categories):
+                masks = np.array([int(c) & 0xFFFFFFFFFFFFFFFF for c in item_categories], dtype=np.uint64)
+            else:
+                masks = np.array([self._mask_of([c] if isinstance(c, str) else c) for c in item_categories],
+                                 dtype=np.uint64).reshape(-1)
+        if masks.shape[0] != n:
+            raise ValueError(f"item_categories holds {masks.shape[0]} entries for {n} items")
+        if len(self.categories) < 64 and masks.size and int(masks.max()) >> len(self.categories):
+            raise ValueError(f"item_categories: a mask has bits past the {len(self.categories)} categories")
+        return masks
+
+    def _query_masks(self, filter_categories, exclude_categories, nq: int):
+        """(any_of, none_of) uint64 [nq] of a search's ``filter_categories`` /
+        ``exclude_categories`` — one list of names for all queries, or one list per
+        query — or None when neither is given."""
+        if filter_categories is None and exclude_categories is None:
+            return None
+        self._need_categories("filter_categories" if filter_categories is not None else "exclude_categories")
+        out = []
+        for names in (filter_categories, exclude_categories):
+            if names is None:
+                out.append(np.zeros(nq, np.uint64))
+                continue
+            if isinstance(names, str):
+                names = [names]
+            out.append(np.array([self._mask_of(per) for per in _per_query(names, nq)], dtype=np.uint64))
+        return out[0], out[1]
+
+    def _tags_store(self, start: int, masks: np.ndarray):
+        """Tags of the positions [start, start + len(masks)); grows like the rows."""
+        if self.categories is None:
+            return
+        n_new = start + len(masks)
+        if self._tags is None or self._tags.numel() < n_new:
+            cap = max(n_new, 2 * (self._tags.numel() if self._tags is not None else 0), 1024)
+            buf = torch.zeros(cap, dtype=torch.int64, device=self._dev())
+            if self._tags is not None and start:
+                buf[:start].copy_(self._tags[:start])
+            self._tags = buf
+        if len(masks):
+            self._tags[start:n_new].copy_(torch.from_numpy(np.ascontiguousarray(masks).view(np.int64)))
+
+    def _tags_write(self, positions: List[int], masks: np.ndarray):
+        """In place, by position: no pointer changes, captured graphs stay valid."""
+        if not len(positions):
+            return
+        dev = self._dev()
+        pos = torch.tensor(list(positions), dtype=torch.int64, device=dev)
+        with self._searcher_lock():
+            self._tags[pos] = torch.from_numpy(np.ascontiguousarray(masks).view(np.int64)).to(dev)
+
+    def set_item_categories(self, ids: List[str], item_categories):
+        """Replace the categories of known items (``item_categories`` as ``build``
+        takes it; None = untagged), in place in the resident tags tensor: no
+        generation bump, resident searchers keep their captured graphs and read
+        the new tags at their next replay. An unknown id raises."""
+        self._need_categories("set_item_categories")
+        if self._tags is None:
+            raise ValueError("Index not built yet")
+        ids = list(ids)
+        missing = [i for i in ids if i not in self.reverse_id_map]
+        if missing:
+            raise ValueError(f"set_item_categories: unknown ids {missing[:5]}")
+        self._tags_write([self.reverse_id_map[i] for i in ids], self._item_tags(item_categories, len(ids)))
+
+    def item_tags(self) -> np.ndarray:
+        """uint64 [current_size]: the tags by position."""
+        if self._tags is None:
+            return np.zeros(self.current_size, np.uint64)
+        return self._tags[: self.current_size].cpu().numpy().view(np.uint64)
+
+    def _tags_path(self, path: Path) -> Path:
+        return path.with_suffix(".tags.npz")
+
+    def _save_tags(self, path: Path):
+        """``<path>.tags.npz``: vocabulary and tags, beside the other files."""
+        f = self._tags_path(path)
+        if self.categories is None:
+            if f.exists():
+                f.unlink()   # a stale file of an earlier save under this name
+            return
+        np.savez(f, categories=np.array(self.categories, dtype=str), tags=self.item_tags())
+
+    def _load_tags(self, path: Path):
+        """After the rows and the config were loaded: the vocabulary (the file's, when
+        there is one) and the tags of the ``current_size`` positions."""
+        f = self._tags_path(path)
+        self._init_categories()
+        if not f.exists():
+            if self.categories is not None:
+                self._tags_store(0, np.zeros(self.current_size, np.uint64))
+            return
+        with np.load(f) as z:
+            self.categories = [str(c) for c in z["categories"]]
+            tags = z["tags"].astype(np.uint64)
+        self.config = dict(self.config, categories=list(self.categories))
+        self._cat_bit = {c: j for j, c in enumerate(self.categories)}
+        self._tags = None
+        self._tags_store(0, tags[: self.current_size])
 
     def _dimension_detail(self) -> str:
         """The class's own tail of the dimension error."""
@@ -196,7 +349,8 @@ class _HbmIndex(IndexBase):
 
     # -- search (the single-GPU indexes) -------------------------------------
     def search(self, query_embeddings: Array, k: int = 10, filter_ids: Optional[List[str]] = None,
-               exclude_ids=None) -> Tuple[List[List[str]], List[List[float]]]:
+               exclude_ids=None, filter_categories=None, exclude_categories=None
+               ) -> Tuple[List[List[str]], List[List[float]]]:
         """retrieval.py:141-197: normalise, top-k_search (2k when filtering), map
         positions to ids, drop -1 padding, apply the filter, stop at k.
 
@@ -207,7 +361,18 @@ class _HbmIndex(IndexBase):
         eligible items exist, in every configuration (a resident searcher that
         takes lists reads them in its scan; the other paths mask through a
         bitmap). With ``filter_ids`` as well, the allow-list then applies to the
-        2k over-fetch."""
+        2k over-fetch.
+
+        ``filter_categories`` / ``exclude_categories`` (the request schema's
+        ``filter_categories``; config key ``categories``): names of the vocabulary —
+        one list for every query, or one list per query; an unknown name raises.
+        An item is eligible iff it carries at least one of ``filter_categories``
+        (when given and not empty) and none of ``exclude_categories``. Like
+        ``exclude_ids`` the filter is applied IN the search and is exact over the
+        rows scanned (for an IVF index: the probed lists, as with Faiss), and it
+        composes with ``exclude_ids`` by union of what is skipped. Calls within
+        the online limits stay on the resident searcher (the scan tests the tags
+        itself); the others go through ``rt_tag_filter_bitmap``."""
         if self.index is None:
             raise ValueError("Index not built yet")
         k_search = min(k * 2, self.current_size) if filter_ids else k
@@ -215,16 +380,38 @@ class _HbmIndex(IndexBase):
         if k_search <= 0 or (self.mutable and self.current_size == 0):  # emptied by remove: nothing to scan
             return [[] for _ in range(nq)], [[] for _ in range(nq)]
         excl = None if exclude_ids is None else _exclude_positions(self.reverse_id_map, exclude_ids, nq)
+        masks = self._query_masks(filter_categories, exclude_categories, nq)
         if self.online_max_batch and not self._l2 and k_search <= OnlineSearcher.MAX_K \
                 and 1 <= nq <= self.online_max_batch and (excl is None or self._searcher_takes_exclude):
             if self._online is None:
                 self._online = self.online_searcher(self.online_max_batch)
             with self._online.lock:  # the returned buffers are the searcher's: read them under its lock
-                scores, pos = self._online.search(query_embeddings, k_search, exclude=excl)
+                scores, pos = self._online.search(query_embeddings, k_search, exclude=excl, tags=masks)
                 return _lists_from_positions(scores, pos, self.id_map, k, filter_ids)
         bits = None if excl is None else kernels.exclusion_bitmap(nq, self.current_size, excl, self._dev())
-        scores, pos = self.search_tensors(query_embeddings, k_search, exclude_bits=bits)
+        scores, pos = self.search_tensors(query_embeddings, k_search, exclude_bits=bits, tag_filter=masks)
         return _lists_from_positions(scores.cpu().numpy(), pos.cpu().numpy(), self.id_map, k, filter_ids)
+
+    def _filter_bits(self, tag_filter, nq: int, exclude_bits: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+        """``search_tensors``' ``tag_filter=(any_of, none_of)`` (uint64 / int64 masks
+        ``[nq]``, numpy or tensors; either may be None) as an exclusion bitmap:
+        ``rt_tag_filter_bitmap`` over the resident tags, accumulated onto
+        ``exclude_bits`` (a copy) when the call has one."""
+        if tag_filter is None:
+            return exclude_bits
+        self._need_categories("tag_filter")
+        if len(tag_filter) != 2:
+            raise ValueError("tag_filter is (any_of, none_of)")
+        any_of, none_of = (_mask_tensor(m, nq, self._dev()) for m in tag_filter)
+        n = self.current_size
+        words = (n + 31) // 32
+        out = None
+        if exclude_bits is not None:
+            if exclude_bits.shape[0] != nq or exclude_bits.shape[1] < words:
+                raise ValueError("exclude_bits has fewer words than ceil(n_items / 32)")
+            out = exclude_bits.contiguous().clone()
+        return kernels.tag_filter_bitmap(self._tags, any_of, none_of, nq, n_items=n, out=out,
+                                         accumulate=out is not None)
 
 
 class HipFlatIPIndex(_HbmIndex):
@@ -263,6 +450,18 @@ class HipFlatIPIndex(_HbmIndex):
     shift down, the corpus stays dense, and the index is indistinguishable
     from one built on the surviving rows (stored bits, positions, the
     lower-position-wins tie rule). Every metric and storage dtype.
+
+    ``categories`` (default absent = off): the vocabulary of the category
+    filters, at most 64 names (inner-product metrics). ``build`` / ``add`` /
+    ``update`` then take ``item_categories`` (per item a sequence of names, or
+    uint64 masks: an item belongs to several categories at once),
+    ``set_item_categories`` rewrites tags in place, and ``search`` takes
+    ``filter_categories`` / ``exclude_categories``: exact, applied by the scan
+    itself on the resident path (``rt_flatip_topk_online_tags``), through
+    ``rt_tag_filter_bitmap`` elsewhere; ``save`` adds ``<path>.tags.npz``.
+    Measured ("Category filters"; 1M x 128, k = 100, nq 1 and 8, float16 and
+    float32, 50 / 10 / 1 % of the items eligible; p50 of the resident call in us): 95-215
+    without a filter, 95-212 with it (-28 to 11 us), against 922-3536 through the bitmap route.
     """
 
     _searcher_takes_exclude = True   # OnlineSearcher: rt_flatip_topk_online_lists
@@ -317,14 +516,19 @@ class HipFlatIPIndex(_HbmIndex):
         self._to_storage(rows, out=self.index[self.current_size:n_new])
 
     # -- IndexBase ---------------------------------------------------------
-    def build(self, embeddings: Array, ids: List[str]):
-        """retrieval.py:70-139 (Flat path)."""
+    def build(self, embeddings: Array, ids: List[str], item_categories=None):
+        """retrieval.py:70-139 (Flat path). ``item_categories`` (config key
+        ``categories``): per item a sequence of category names, or an integer
+        array of 64-bit masks; None = untagged."""
         start = time.time()
         rows = self._prepare(embeddings)
+        tags = self._item_tags(item_categories, rows.shape[0])
         self.index = None
         self.current_size = 0
         self._reset_ids()
         self._store(rows)
+        self._tags = None
+        self._tags_store(0, tags)
         self._record_ids(0, ids, max(rows.shape[0], len(ids)))   # ids past the rows stay in _ids
         self.current_size = rows.shape[0]
         self._generation += 1
@@ -338,13 +542,17 @@ class HipFlatIPIndex(_HbmIndex):
         return OnlineSearcher(self, max_batch, max_exclude)
 
     def search_tensors(self, query_embeddings: Array, k: int,
-                       exclude_bits: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                       exclude_bits: Optional[torch.Tensor] = None, tag_filter=None
+                       ) -> Tuple[torch.Tensor, torch.Tensor]:
         """Device-level search: (scores [nq,k], positions [nq,k]) with -1 padding;
         scores are inner products (descending) or, in the L2 mode, squared L2
-        distances (ascending, IndexFlatL2.search)."""
+        distances (ascending, IndexFlatL2.search). ``tag_filter=(any_of, none_of)``:
+        per-query 64-bit category masks; the ineligible items join ``exclude_bits``
+        through ``rt_tag_filter_bitmap``."""
         if self.index is None:
             raise ValueError("Index not built yet")
         q = self._prepare(query_embeddings).to(self.storage_dtype)
+        exclude_bits = self._filter_bits(tag_filter, q.shape[0], exclude_bits)
         if self._l2:
             if k > MAX_K_L2:
                 raise ValueError(f"k={k} > {MAX_K_L2}: the MI355X IndexFlatL2 mode returns at most {MAX_K_L2} "
@@ -353,23 +561,29 @@ class HipFlatIPIndex(_HbmIndex):
                                        exclude_bits=exclude_bits)
         return kernels.flatip_topk(q, self.index[: self.current_size], k, exclude_bits=exclude_bits)
 
-    def add(self, embeddings: Array, ids: List[str]):
-        """retrieval.py:199-226: incremental append (Kafka item_update path)."""
+    def add(self, embeddings: Array, ids: List[str], item_categories=None):
+        """retrieval.py:199-226: incremental append (Kafka item_update path);
+        ``item_categories`` as ``build`` takes it."""
         if self.index is None:
             raise ValueError("Index not built yet")
-        self._append(self._prepare(embeddings), ids)
+        rows = self._prepare(embeddings)
+        self._append(rows, ids, self._item_tags(item_categories, rows.shape[0]))
 
-    def _append(self, rows: torch.Tensor, ids: List[str]):
-        """Append prepared rows and their ids (``add``; the unknown ids of ``update``)."""
+    def _append(self, rows: torch.Tensor, ids: List[str], tags: Optional[np.ndarray] = None):
+        """Append prepared rows, their ids and tags (``add``; the unknown ids of ``update``)."""
         self._store(rows)
+        self._tags_store(self.current_size, np.zeros(rows.shape[0], np.uint64) if tags is None else tags)
         self._record_ids(self.current_size, ids, max(rows.shape[0], len(ids)))
         self.current_size += rows.shape[0]
         self._generation += 1
         logger.info("Added %d items to index. Total size: %d", rows.shape[0], self.current_size)
 
-    def update(self, embeddings: Array, ids: List[str]):
+    def update(self, embeddings: Array, ids: List[str], item_categories=None):
         """retrieval.py:228-237: a no-op with a warning, like the reference, unless
-        the index is ``mutable``. Then an upsert: rows are prepared and stored as
+        the index is ``mutable``. ``item_categories``: as ``build`` takes it; None
+        keeps the tags of known ids (unknown ids are appended untagged); given,
+        a known id's tags are overwritten in place like its row.
+        Then an upsert: rows are prepared and stored as
         ``build`` would store them; a known id's row is overwritten in place (the
         last occurrence of an id given more than once wins; an id stored twice
         through ``add`` has its last row overwritten, the one ``reverse_id_map``
@@ -385,6 +599,7 @@ class HipFlatIPIndex(_HbmIndex):
         rows = self._prepare(embeddings)
         if rows.shape[0] != len(ids):
             raise ValueError(f"{rows.shape[0]} embeddings for {len(ids)} ids")
+        tags = None if item_categories is None else self._item_tags(item_categories, len(ids))
         known: Dict[str, int] = {}     # id -> its last row in the call (positions stay unique)
         unknown: Dict[str, int] = {}   # in order of first appearance, the last row wins too
         for i, item_id in enumerate(ids):
@@ -393,11 +608,13 @@ class HipFlatIPIndex(_HbmIndex):
             take = torch.tensor(list(known.values()), dtype=torch.int64, device=rows.device)
             pos = torch.tensor([self.reverse_id_map[i] for i in known], dtype=torch.int64, device=rows.device)
             new_rows = self._to_storage(rows[take])
-            with self._searcher_lock():
+            with self._searcher_lock():   # row and tags under one acquisition: a search sees both or neither
                 kernels.scatter_rows(new_rows, pos, self.index)
+                if tags is not None:
+                    self._tags_write([self.reverse_id_map[i] for i in known], tags[list(known.values())])
         if unknown:
             take = torch.tensor(list(unknown.values()), dtype=torch.int64, device=rows.device)
-            self._append(rows[take], list(unknown))
+            self._append(rows[take], list(unknown), None if tags is None else tags[list(unknown.values())])
         logger.info("Updated %d items in place, appended %d. Total size: %d", len(known), len(unknown),
                     self.current_size)
 
@@ -443,6 +660,10 @@ class HipFlatIPIndex(_HbmIndex):
             reverse_id_map = dict(zip(new_ids, range(len(new_ids))))
         with self._searcher_lock():
             kernels.rows_compact(self.index[:n], d_bits, buf)
+            if self._tags is not None:   # the tags shift down with the rows
+                kept = self._tags[:n][torch.from_numpy(keep).to(self._dev())]
+                self._tags = torch.zeros_like(self._tags)
+                self._tags[: kept.numel()] = kept
             self.index = buf
             self.current_size = len(new_ids)    # the host's own count: no device read
             self._ids, self.id_map, self.reverse_id_map = new_ids, id_map, reverse_id_map
@@ -464,6 +685,7 @@ class HipFlatIPIndex(_HbmIndex):
         path.parent.mkdir(parents=True, exist_ok=True)
         write_flat_index(path.with_suffix(".faiss"), self.vectors(), not self._l2)
         self._save_ids(path)
+        self._save_tags(path)
         logger.info("Saved index to %s", path)
 
     def load(self, path: str):
@@ -481,6 +703,7 @@ class HipFlatIPIndex(_HbmIndex):
         self._store(torch.from_numpy(vecs).to(self._dev()))
         self.current_size = int(data["current_size"])
         self._load_ids(data, self.current_size)
+        self._load_tags(path)
         self._generation += 1
         self._online = None  # load may change the dimension and the metric
         logger.info("Loaded index from %s with %d items", path, self.current_size)
@@ -608,6 +831,11 @@ class OnlineSearcher:
         self._h_xo_np, self._h_xi_np = self._h_xo.numpy(), self._h_xi.numpy()
         self._d_xo = torch.zeros(mb + 1, dtype=torch.int64, device=dev)
         self._d_xi = torch.zeros(max(self.max_exclude, 1), dtype=torch.int32, device=dev)
+        # the per-call category masks: any_of [mb] then none_of [mb], one fixed-size H2D copy
+        self._h_tm = torch.zeros(2 * mb, dtype=torch.int64).pin_memory()
+        self._h_tm_np = self._h_tm.numpy()
+        self._d_tm = torch.zeros(2 * mb, dtype=torch.int64, device=dev)
+        self._item_tags: Optional[torch.Tensor] = None   # the index's resident tags (per generation)
         # keys (nq, k) without lists — as before lists existed — and (nq, k, True) with
         self._graphs: "OrderedDict[tuple, torch.cuda.CUDAGraph]" = OrderedDict()
         self._generation = -1
@@ -643,12 +871,30 @@ class OnlineSearcher:
         """The per-call lists as a source of ``kernels.flatip_topk_online(exclude_lists=...)``."""
         return (self._d_xo, self._d_xi)
 
-    def _device_chain(self, nq: int, k: int, sources=None):
+    def _tag_filter(self, nq: int):
+        """The per-call masks over the index's resident tags, as ``tag_filter`` of the kernels."""
+        mb = self.max_batch
+        return (self._item_tags, self._d_tm[:nq], self._d_tm[mb:mb + nq])
+
+    def _stage_tags(self, nq: int, tags):
+        """Write ``tags = (any_of, none_of)`` into the pinned mask buffer."""
+        if self.index.categories is None or self._item_tags is None:
+            self.index._need_categories("tags")
+            raise ValueError("the index holds no tags yet")
+        if len(tags) != 2:
+            raise ValueError("tags is (any_of, none_of)")
+        mb = self.max_batch
+        for at, m in zip((0, mb), tags):
+            w = _mask_words(m, nq)
+            self._h_tm_np[at:at + nq] = 0 if w is None else w
+
+    def _device_chain(self, nq: int, k: int, sources=None, tags: bool = False):
         """``_d_q32[:nq]`` (fp32 device rows, however they got there: ``_upload``,
         or a kernel that wrote them — :class:`rtrec_amd.serving.online.OnlineRecommender`)
         -> ``l2_renorm`` for the cosine metric (in place) -> storage-dtype cast ->
         ``rt_flatip_topk_online`` (``sources``: ``rt_flatip_topk_online_lists`` with
-        these exclusion sources) into the device scores / positions."""
+        these exclusion sources; ``tags``: ``rt_flatip_topk_online_tags`` with the
+        uploaded masks too) into the device scores / positions."""
         n = nq * k
         q32 = self._d_q32[:nq]
         if self.index.metric == "cosine":
@@ -657,7 +903,8 @@ class OnlineSearcher:
         if q.data_ptr() != q32.data_ptr():
             q.copy_(q32)
         kernels.flatip_topk_online(q, self._rows, k, out=(self._d_s[:n].view(nq, k), self._d_p[:n].view(nq, k)),
-                                   workspace_buf=self._ws, exclude_lists=sources or None)
+                                   workspace_buf=self._ws, exclude_lists=sources or None,
+                                   tag_filter=self._tag_filter(nq) if tags else None)
 
     def _download(self, nq: int, k: int):
         """D2H copies of scores and positions into the pinned result buffers."""
@@ -665,16 +912,18 @@ class OnlineSearcher:
         self._h_s[:n].copy_(self._d_s[:n], non_blocking=True)
         self._h_p[:n].copy_(self._d_p[:n], non_blocking=True)
 
-    def _sequence(self, nq: int, k: int, lists: bool = False):
+    def _sequence(self, nq: int, k: int, lists: bool = False, tags: bool = False):
         """The stream-ordered chain of one call, on torch's current stream."""
         self._upload(nq)
         if lists:
             self._upload_lists()
-        self._device_chain(nq, k, [self._list_source()] if lists else None)
+        if tags:
+            self._d_tm.copy_(self._h_tm, non_blocking=True)   # whole buffer: the masks are data
+        self._device_chain(nq, k, [self._list_source()] if lists else None, tags=tags)
         self._download(nq, k)
 
     def _graph_key(self, nq: int, k: int, lists: bool) -> tuple:
-        """What one captured graph serves."""
+        """What one captured graph serves (a call with category masks: this key + ("tags",))."""
         return (nq, k, True) if lists else (nq, k)
 
     def _revalidate(self) -> bool:
@@ -690,10 +939,11 @@ class OnlineSearcher:
             raise ValueError("the index changed its dimension, metric or storage dtype since this "
                              "searcher was made: obtain a new one (index.online_searcher)")
         self._rows = idx.index[: idx.current_size]
+        self._item_tags = idx._tags
         self._generation = idx._generation
         return True
 
-    def search(self, query_embeddings: Array, k: int, exclude=None) -> Tuple[np.ndarray, np.ndarray]:
+    def search(self, query_embeddings: Array, k: int, exclude=None, tags=None) -> Tuple[np.ndarray, np.ndarray]:
         """(scores [nq, k] f32, positions [nq, k] int64, (-FLT_MAX, -1) padded) as
         numpy views of the searcher's pinned buffers: valid until the next call.
 
@@ -705,7 +955,13 @@ class OnlineSearcher:
         per call. A call with more takes the non-resident path — a dense bitmap
         and ``search_tensors(..., exclude_bits=...)`` — and returns the same result
         in fresh arrays. ``exclude=None`` replays the graphs of a searcher without
-        lists."""
+        lists.
+
+        ``tags=(any_of, none_of)``: per-query 64-bit category masks (uint64 / int64
+        ``[nq]``; either may be None) over the index's resident tags; the scan
+        tests eligibility itself. The masks travel through one more fixed-size
+        H2D copy, and one graph per (nq, k, lists, tags) serves every mask value
+        and, the tags being read at replay, every in-place tag change."""
         idx = self.index
         if idx.index is None:
             raise ValueError("Index not built yet")
@@ -724,18 +980,21 @@ class OnlineSearcher:
             if len(exclude) != nq:
                 raise ValueError(f"exclude holds {len(exclude)} lists for {nq} queries")
             exclude = [_sorted_positions(e, idx.current_size) for e in exclude]
+        tagged = tags is not None
         with self.lock:
             self._revalidate()
+            if tagged:
+                self._stage_tags(nq, tags)
             if lists and not self._stage_lists(nq, exclude):
                 # more entries than the resident buffers hold: the dense bitmap of the default path
                 bits = kernels.exclusion_bitmap(nq, idx.current_size, exclude, self._d_s.device)
-                s, p = idx.search_tensors(t, k, exclude_bits=bits)
+                s, p = idx.search_tensors(t, k, exclude_bits=bits, tag_filter=tags)
                 return s.cpu().numpy(), p.cpu().numpy()
             self._h_q[:nq].copy_(t)
-            key = self._graph_key(nq, k, lists)
+            key = self._graph_key(nq, k, lists) + (("tags",) if tagged else ())
             stream = torch.cuda.current_stream(self._d_s.device)
             if os.environ.get("RTREC_ONLINE_GRAPH", "1") == "0":
-                self._sequence(nq, k, lists)
+                self._sequence(nq, k, lists, tagged)
             else:
                 g = self._graphs.get(key)
                 if g is not None:
@@ -744,13 +1003,13 @@ class OnlineSearcher:
                     # the first call at this shape: its answer comes from an eager run
                     # (which also loads every kernel), then the chain is captured —
                     # a capture executes nothing, the host buffers keep the answer
-                    self._sequence(nq, k, lists)
+                    self._sequence(nq, k, lists, tagged)
                     stream.synchronize()
                     g = torch.cuda.CUDAGraph()
                     # thread_local: CUDA work of other threads (an allocation, a default-path
                     # search) during the capture neither enters it nor invalidates it
                     with _capture(g):
-                        self._sequence(nq, k, lists)
+                        self._sequence(nq, k, lists, tagged)
                     while len(self._graphs) >= self.MAX_GRAPHS:
                         self._graphs.popitem(last=False)
                     self._graphs[key] = g
@@ -820,6 +1079,15 @@ class HipShardedFlatIPIndex(_HbmIndex):
         if self._l2:
             raise ValueError("the sharded index serves the inner-product metrics ('cosine', 'inner_product'); "
                              "IndexFlatL2 is the single-GPU HipFlatIPIndex")
+
+    _NO_CATEGORIES = ("the sharded index does not serve category filters: use a single-GPU index "
+                      "(HipFlatIPIndex, HipIVFFlatIndex, HipMutableIVFFlatIndex)")
+
+    def _check_categories(self):
+        raise ValueError("categories: " + self._NO_CATEGORIES)
+
+    def set_item_categories(self, ids, item_categories):
+        raise ValueError(self._NO_CATEGORIES)
 
     # -- hooks (the CPU orchestration tests substitute these, and the base's _dev
     # and _renorm_) -----------------------------------------------------------
@@ -966,8 +1234,12 @@ class HipShardedFlatIPIndex(_HbmIndex):
         return torch.cat(parts_s), torch.cat(parts_i)
 
     def search(self, query_embeddings: Array, k: int = 10,
-               filter_ids: Optional[List[str]] = None) -> Tuple[List[List[str]], List[List[float]]]:
-        """retrieval.py:141-197 on every rank (collective)."""
+               filter_ids: Optional[List[str]] = None, filter_categories=None, exclude_categories=None
+               ) -> Tuple[List[List[str]], List[List[float]]]:
+        """retrieval.py:141-197 on every rank (collective). Category filters are not
+        served here: ``filter_categories`` / ``exclude_categories`` raise."""
+        if filter_categories is not None or exclude_categories is not None:
+            raise ValueError(self._NO_CATEGORIES)
         if self.shard is None:
             raise ValueError("Index not built yet")
         k_search = min(k * 2, self.current_size) if filter_ids else k
@@ -1078,6 +1350,32 @@ def _sorted_positions(positions, n: int) -> np.ndarray:
         raise TypeError("excluded positions must be integers")
     a = np.unique(a.astype(np.int64, copy=False))
     return a[(a >= 0) & (a < n)].astype(np.int32)
+
+
+def _mask_words(m, nq: int) -> Optional[np.ndarray]:
+    """Per-query 64-bit masks (numpy or tensor, uint64 or int64; None stays None) as
+    int64 words [nq] on the host."""
+    if m is None:
+        return None
+    if isinstance(m, torch.Tensor):
+        if m.dtype not in (torch.int64, torch.uint64):
+            raise TypeError("category masks are 64-bit words (int64 or uint64)")
+        m = m.cpu().view(torch.int64).numpy()
+    m = np.asarray(m).reshape(-1)
+    if m.dtype not in (np.dtype(np.int64), np.dtype(np.uint64)):
+        raise TypeError("category masks are 64-bit words (int64 or uint64)")
+    if m.shape[0] != nq:
+        raise ValueError(f"{m.shape[0]} category masks for {nq} queries")
+    return np.ascontiguousarray(m).view(np.int64)
+
+
+def _mask_tensor(m, nq: int, device) -> Optional[torch.Tensor]:
+    """:func:`_mask_words` on ``device`` (a device tensor of the right form is passed on)."""
+    if isinstance(m, torch.Tensor) and m.device.type == "cuda" and m.dtype == torch.int64 and m.numel() == nq \
+            and m.dim() == 1 and m.is_contiguous():
+        return m
+    w = _mask_words(m, nq)
+    return None if w is None else torch.from_numpy(w.copy()).to(device)
 
 
 def _per_query(ids, nq: int) -> List:
@@ -1193,6 +1491,17 @@ class HipIVFFlatIndex(_HbmIndex):
     about 1M rows for float32 storage or 8-query calls and, extrapolated, from
     1.5-2M rows for single float16 queries; below that ``HipFlatIPIndex`` with
     ``online_max_batch`` is as fast and exact.
+
+    ``categories``: as :class:`HipFlatIPIndex`. The tags are kept by ORIGINAL
+    position (the lists know nothing of them); a filtered search is exact over
+    the eligible rows of the PROBED lists — k results whenever k eligible rows
+    exist among them, as a filtered Faiss IVF search — not over the corpus: a
+    narrow filter may need a larger ``nprobe``. The resident path tests the tags
+    in the probed-list scan (``rt_ivf_topk_tags``); larger calls, the
+    ``batch_min_queries`` route included, take ``rt_tag_filter_bitmap``.
+    Measured ("Category filters"; 1M x 128, k = 100, nlist 1024, nprobe 20, nq 1 and
+    8, float16 and float32, 50 / 10 / 1 % eligible; p50 of the resident call in us): 120-164
+    without a filter, 85-150 with it (-48 to -8 us), against 158-212 through the bitmap route.
     """
 
     _searcher_takes_exclude = True   # OnlineIVFSearcher: rt_ivf_topk_lists
@@ -1237,7 +1546,7 @@ class HipIVFFlatIndex(_HbmIndex):
 
     def _flat_config(self) -> Dict[str, Any]:
         cfg = {k: v for k, v in self.config.items()
-               if k in ("dimension", "metric", "storage_dtype", "device", "online_max_batch")}
+               if k in ("dimension", "metric", "storage_dtype", "device", "online_max_batch", "categories")}
         cfg["index_factory"] = "Flat"
         return cfg
 
@@ -1304,19 +1613,23 @@ class HipIVFFlatIndex(_HbmIndex):
         self.id_map, self.reverse_id_map, self._ids = f.id_map, f.reverse_id_map, f._ids
         self.current_size = f.current_size
         self.index = f.index
+        self._tags = f._tags
         self._generation += 1
 
     # -- IndexBase ---------------------------------------------------------
-    def build(self, embeddings: Array, ids: List[str]):
+    def build(self, embeddings: Array, ids: List[str], item_categories=None):
         """retrieval.py:70-139: normalise (cosine), train the coarse quantiser
-        (``index.train``), add every row to its list (``index.add``)."""
+        (``index.train``), add every row to its list (``index.add``).
+        ``item_categories`` as :meth:`HipFlatIPIndex.build` takes it; the tags are
+        kept by ORIGINAL position, so the lists know nothing of them."""
         start = time.time()
         n = len(embeddings)
         self._online = None
+        tags = self._item_tags(item_categories, n)
         if n < IVF_MIN_ITEMS or n < self.nlist:
             logger.info("Dataset too small (%d) for IVF, using Flat index", n)
             self._flat = HipFlatIPIndex(self._flat_config())
-            self._flat.build(embeddings, ids)
+            self._flat.build(embeddings, ids, item_categories=item_categories)
             self.centroids = self.list_offsets = self.row_pos = self.assign = None
             self._sync_flat()
             return
@@ -1325,6 +1638,8 @@ class HipIVFFlatIndex(_HbmIndex):
         self.centroids = self._train(rows)
         assign = self._assign_rows(rows, self.centroids)
         self._regroup(rows.to(self.storage_dtype), None, assign)
+        self._tags = None
+        self._tags_store(0, tags)
         self._reset_ids()
         self._record_ids(0, ids, max(n, len(ids)))   # ids past the rows stay in _ids, as in the Flat index
         self._generation += 1
@@ -1346,18 +1661,21 @@ class HipIVFFlatIndex(_HbmIndex):
         return np_
 
     def search_tensors(self, query_embeddings: Array, k: int, exclude_bits: Optional[torch.Tensor] = None,
-                       nprobe: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                       nprobe: Optional[int] = None, tag_filter=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """Device-level search: (scores [nq, k], original positions [nq, k]) with
         (-FLT_MAX, -1) padding, like the Flat index. The coarse search runs on the
-        fp32 queries, before the storage cast."""
+        fp32 queries, before the storage cast. ``tag_filter=(any_of, none_of)``: as
+        :meth:`HipFlatIPIndex.search_tensors` (a bitmap by original position, for
+        the list-major batch scan too); exact over the PROBED lists."""
         if self.index is None:
             raise ValueError("Index not built yet")
         if self._flat is not None:
-            return self._flat.search_tensors(query_embeddings, k, exclude_bits=exclude_bits)
+            return self._flat.search_tensors(query_embeddings, k, exclude_bits=exclude_bits, tag_filter=tag_filter)
         if not 1 <= k <= kernels.IVF_MAX_K:
             raise ValueError(f"k={k}: the MI355X IVF index returns 1..{kernels.IVF_MAX_K} results per query")
         np_ = self._n_probe(nprobe)
         q32 = self._prepare(query_embeddings)
+        exclude_bits = self._filter_bits(tag_filter, q32.shape[0], exclude_bits)
         if q32.shape[0] <= kernels.ONLINE_MAX_NQ:
             _, probes = kernels.flatip_topk_online(q32, self.centroids, np_)
         else:
@@ -1370,17 +1688,22 @@ class HipIVFFlatIndex(_HbmIndex):
                     self.max_list_rows, k, exclude_bits=exclude_bits, **self._scan_operands())
 
     def search(self, query_embeddings: Array, k: int = 10, filter_ids: Optional[List[str]] = None,
-               exclude_ids=None) -> Tuple[List[List[str]], List[List[float]]]:
+               exclude_ids=None, filter_categories=None, exclude_categories=None
+               ) -> Tuple[List[List[str]], List[List[float]]]:
         """retrieval.py:141-197, as :meth:`HipFlatIPIndex.search`: the 2k over-fetch
         for ``filter_ids``, exact ``exclude_ids`` in the search (over the probed
         lists). With ``online_max_batch`` a small call with ``exclude_ids`` stays on
         the resident searcher, whose scan reads the lists (``rt_ivf_topk_lists``);
-        the other calls mask through a bitmap."""
+        the other calls mask through a bitmap. ``filter_categories`` /
+        ``exclude_categories``: as :meth:`HipFlatIPIndex.search`, exact over the
+        PROBED lists (k results whenever k eligible rows exist among them), as a
+        filtered Faiss IVF search is — not over the corpus."""
+        cats = dict(filter_categories=filter_categories, exclude_categories=exclude_categories)
         if self.index is not None and self._flat is not None:
-            return self._flat.search(query_embeddings, k, filter_ids, exclude_ids=exclude_ids)
-        return super().search(query_embeddings, k, filter_ids, exclude_ids=exclude_ids)
+            return self._flat.search(query_embeddings, k, filter_ids, exclude_ids=exclude_ids, **cats)
+        return super().search(query_embeddings, k, filter_ids, exclude_ids=exclude_ids, **cats)
 
-    def add(self, embeddings: Array, ids: List[str]):
+    def add(self, embeddings: Array, ids: List[str], item_categories=None):
         """retrieval.py:199-226. The new rows are assigned to the existing centroids
         (no retraining), then every list is regrouped by a stable sort of all
         assignments and one gather: O(n) per call in the size of the index, not
@@ -1389,11 +1712,12 @@ class HipIVFFlatIndex(_HbmIndex):
         if self.index is None:
             raise ValueError("Index not built yet")
         if self._flat is not None:
-            self._flat.add(embeddings, ids)
+            self._flat.add(embeddings, ids, item_categories=item_categories)
             self._sync_flat()
             return
         rows = self._prepare(embeddings)
         n_old, m = self.current_size, rows.shape[0]
+        tags = self._item_tags(item_categories, m)
         dev = rows.device
         inv = torch.empty(n_old, dtype=torch.int64, device=dev)
         inv[self.row_pos.long()] = torch.arange(n_old, dtype=torch.int64, device=dev)
@@ -1402,12 +1726,14 @@ class HipIVFFlatIndex(_HbmIndex):
         src = torch.cat([self.index, rows.to(self.storage_dtype)])
         with self._searcher_lock():
             self._regroup(src, src_index, assign)
+            self._tags_store(n_old, tags)
             self._record_ids(n_old, ids, max(m, len(ids)))
             self._generation += 1
         logger.info("Added %d items to index. Total size: %d", m, self.current_size)
 
-    def update(self, embeddings: Array, ids: List[str]):
-        """retrieval.py:228-237: a no-op with a warning, like the reference."""
+    def update(self, embeddings: Array, ids: List[str], item_categories=None):
+        """retrieval.py:228-237: a no-op with a warning, like the reference
+        (``set_item_categories`` changes tags alone)."""
         logger.warning("IVF index doesn't support direct updates. Consider periodic rebuilds.")
 
     def remove(self, ids: List[str]):
@@ -1433,7 +1759,7 @@ class HipIVFFlatIndex(_HbmIndex):
             raise ValueError("No index to save")
         path = Path(path)
         if self._flat is not None:
-            self._flat.save(str(path))
+            self._flat.save(str(path))   # its .tags.npz too
             ivf = path.with_suffix(".ivf.npz")
             if ivf.exists():
                 ivf.unlink()   # a stale file of an earlier IVF save under this name
@@ -1445,6 +1771,7 @@ class HipIVFFlatIndex(_HbmIndex):
         np.savez(path.with_suffix(".ivf.npz"), centroids=self.centroids.cpu().numpy(),
                  assign=self._live_assign().cpu().numpy(), config=np.array(json.dumps(cfg)), seed=np.int64(self.seed),
                  nlist=np.int64(self.nlist))
+        self._save_tags(path)
         logger.info("Saved index to %s", path)
 
     def load(self, path: str):
@@ -1458,6 +1785,7 @@ class HipIVFFlatIndex(_HbmIndex):
             self._flat.load(str(path))
             self.dimension, self.metric = self._flat.dimension, self._flat.metric
             self.centroids = self.list_offsets = self.row_pos = self.assign = None
+            self.categories, self._cat_bit = self._flat.categories, self._flat._cat_bit
             self._sync_flat()
             return
         vecs, _ip = read_flat_index(path.with_suffix(".faiss"))
@@ -1475,6 +1803,7 @@ class HipIVFFlatIndex(_HbmIndex):
         self.centroids = torch.from_numpy(centroids).to(dev)
         self._regroup(torch.from_numpy(vecs).to(dev).to(self.storage_dtype), None, torch.from_numpy(assign).to(dev))
         self._load_ids(data, self.current_size)
+        self._load_tags(path)
         self._generation += 1
         logger.info("Loaded index from %s with %d items", path, self.current_size)
 
@@ -1524,13 +1853,15 @@ class OnlineIVFSearcher(OnlineSearcher):
             raise ValueError("the index changed its dimension, storage dtype or fell back to Flat since this "
                              "searcher was made: obtain a new one (index.online_searcher)")
         self._rows = idx.index
+        self._item_tags = idx._tags
         self._lists = (idx.list_offsets, idx.row_pos, idx.centroids, idx.max_list_rows)
         self._scan_operands = idx._scan_operands()   # a mutable index: list_len and n_pos, fixed per generation
         self._generation = idx._generation
         return True
 
-    def _device_chain(self, nq: int, k: int, sources=None):
-        """As the base class's, over the lists: ``l2_renorm`` (cosine) -> coarse search
+    def _device_chain(self, nq: int, k: int, sources=None, tags: bool = False):
+        """As the base class's, over the lists (``tags``: ``rt_ivf_topk_tags``, the
+        resident tags indexed by ORIGINAL position): ``l2_renorm`` (cosine) -> coarse search
         -> storage-dtype cast -> ``rt_ivf_topk`` (``sources``: ``rt_ivf_topk_lists`` with
         these exclusion sources, positions in ORIGINAL order); over a
         :class:`HipMutableIVFFlatIndex` their ``_lens`` forms, which read ``list_len``."""
@@ -1547,7 +1878,8 @@ class OnlineIVFSearcher(OnlineSearcher):
             q.copy_(q32)
         kernels.ivf_topk(q, self._rows, offsets, row_pos, probes, max_list_rows, k,
                          out=(self._d_s[:n].view(nq, k), self._d_p[:n].view(nq, k)), workspace_buf=self._ws,
-                         exclude_lists=sources or None, **self._scan_operands)
+                         exclude_lists=sources or None, tag_filter=self._tag_filter(nq) if tags else None,
+                         **self._scan_operands)
 
 
 class HipMutableIVFFlatIndex(HipIVFFlatIndex):
@@ -1687,42 +2019,46 @@ class HipMutableIVFFlatIndex(HipIVFFlatIndex):
         return True
 
     # -- IndexBase ---------------------------------------------------------
-    def add(self, embeddings: Array, ids: List[str]):
+    def add(self, embeddings: Array, ids: List[str], item_categories=None):
         """retrieval.py:199-226 in O(batch): the new rows are assigned to the existing
         centroids and join their lists in place (see the class docstring)."""
         if self.index is None:
             raise ValueError("Index not built yet")
         if self._flat is not None:
-            self._flat.add(embeddings, ids)
+            self._flat.add(embeddings, ids, item_categories=item_categories)
             self._sync_flat()
             return
-        self._append(self._prepare(embeddings), ids)
+        rows = self._prepare(embeddings)
+        self._append(rows, ids, self._item_tags(item_categories, rows.shape[0]))
 
-    def _append(self, rows: torch.Tensor, ids: List[str]):
+    def _append(self, rows: torch.Tensor, ids: List[str], tags: Optional[np.ndarray] = None):
         n_old, m = self.current_size, rows.shape[0]
         positions = torch.arange(n_old, n_old + m, dtype=torch.int64, device=rows.device)
         new_list = self._assign_rows(rows, self.centroids) if m else positions
         with self._searcher_lock():
             if m:
                 self._mutate(positions, new_list, rows.to(self.storage_dtype), n_old + m)
+            self._tags_store(n_old, np.zeros(m, np.uint64) if tags is None else tags)
             self.current_size = n_old + m
             self._record_ids(n_old, ids, max(m, len(ids)))
             self._generation += 1
         logger.info("Added %d items to index. Total size: %d", m, self.current_size)
 
-    def update(self, embeddings: Array, ids: List[str]):
+    def update(self, embeddings: Array, ids: List[str], item_categories=None):
         """An upsert (see the class docstring): known ids in place, without a
-        generation bump; unknown ids appended as by ``add``."""
+        generation bump; unknown ids appended as by ``add``. ``item_categories``:
+        None keeps the tags of known ids; given, they are overwritten in place."""
         if self.index is None:
             raise ValueError("Index not built yet")
         if self._flat is not None:
-            self._flat.update(embeddings, ids)
+            self._flat.update(embeddings, ids, item_categories=item_categories)
             self._sync_flat()
             return
         ids = list(ids)
         rows = self._prepare(embeddings)
         if rows.shape[0] != len(ids):
             raise ValueError(f"{rows.shape[0]} embeddings for {len(ids)} ids")
+        tags = None if item_categories is None else self._item_tags(item_categories, len(ids))
         known: Dict[str, int] = {}     # id -> its last row in the call (positions stay unique)
         unknown: Dict[str, int] = {}   # in order of first appearance, the last row wins too
         for i, item_id in enumerate(ids):
@@ -1732,11 +2068,13 @@ class HipMutableIVFFlatIndex(HipIVFFlatIndex):
             pos = torch.tensor([self.reverse_id_map[i] for i in known], dtype=torch.int64, device=rows.device)
             new = rows[take]
             new_list = self._assign_rows(new, self.centroids)
-            with self._searcher_lock():
+            with self._searcher_lock():   # row and tags under one acquisition: a search sees both or neither
                 self._mutate(pos, new_list, new.to(self.storage_dtype), self.current_size)
+                if tags is not None:
+                    self._tags_write([self.reverse_id_map[i] for i in known], tags[list(known.values())])
         if unknown:
             take = torch.tensor(list(unknown.values()), dtype=torch.int64, device=rows.device)
-            self._append(rows[take], list(unknown))
+            self._append(rows[take], list(unknown), None if tags is None else tags[list(unknown.values())])
         logger.info("Updated %d items in place, appended %d. Total size: %d", len(known), len(unknown),
                     self.current_size)
 
@@ -1775,6 +2113,8 @@ class HipMutableIVFFlatIndex(HipIVFFlatIndex):
                 self.assign[dst] = self.assign[src]
                 self.pos_slot[src] = -1
                 self.assign[src] = -1
+                if self._tags is not None:   # the tags follow their items to the positions they fill
+                    self._tags[dst] = self._tags[src]
             for p in removed:
                 item_id = self.id_map.pop(p, None)
                 if item_id is not None and self.reverse_id_map.get(item_id) == p:
@@ -1840,20 +2180,28 @@ class RetrievalEngine:
             raise ValueError(f"Unknown index type: {self.index_type}")
         return cls(index_config)
 
-    def build_index(self, embeddings: Array, ids: List[str]):
-        self.index.build(embeddings, ids)
+    def build_index(self, embeddings: Array, ids: List[str], item_categories=None):
+        """``item_categories``: as ``HipFlatIPIndex.build`` (config key ``categories`` of the index)."""
+        if item_categories is None:
+            self.index.build(embeddings, ids)
+        else:
+            self.index.build(embeddings, ids, item_categories=item_categories)
         self.cache.clear()
         logger.info("Built index with %d items", len(embeddings))
 
     def retrieve(self, query_embeddings: Array, k: Optional[int] = None,
-                 filter_ids: Optional[List[str]] = None, use_cache: bool = True, exclude_ids=None
+                 filter_ids: Optional[List[str]] = None, use_cache: bool = True, exclude_ids=None,
+                 filter_categories=None, exclude_categories=None
                  ) -> Tuple[List[List[str]], List[List[float]], Dict[str, Any]]:
         """``exclude_ids``: as ``HipFlatIPIndex.search``; like ``filter_ids`` it keeps
-        the call out of the query cache (neither read nor filled)."""
+        the call out of the query cache (neither read nor filled), and so do
+        ``filter_categories`` / ``exclude_categories`` (as ``HipFlatIPIndex.search``)."""
         start = time.time()
         k = k or self.top_k
         cache_key = None
-        if use_cache and filter_ids is None and exclude_ids is None:
+        cats = {key: v for key, v in (("filter_categories", filter_categories),
+                                      ("exclude_categories", exclude_categories)) if v is not None}
+        if use_cache and filter_ids is None and exclude_ids is None and not cats:
             qb = query_embeddings.detach().cpu().numpy().tobytes() if isinstance(query_embeddings, torch.Tensor) \
                 else np.asarray(query_embeddings).tobytes()
             cache_key = hashlib.md5(qb).hexdigest()
@@ -1865,9 +2213,9 @@ class RetrievalEngine:
                 self.total_latency += latency
                 return entry["ids"], entry["scores"], {"latency_ms": latency * 1000, "cache_hit": True}
         if exclude_ids is None:
-            item_ids, scores = self.index.search(query_embeddings, k, filter_ids)
+            item_ids, scores = self.index.search(query_embeddings, k, filter_ids, **cats)
         else:  # HipFlatIPIndex (the sharded index does not take exclusions)
-            item_ids, scores = self.index.search(query_embeddings, k, filter_ids, exclude_ids=exclude_ids)
+            item_ids, scores = self.index.search(query_embeddings, k, filter_ids, exclude_ids=exclude_ids, **cats)
         if use_cache and cache_key:
             self.cache[cache_key] = {"ids": item_ids, "scores": scores, "timestamp": time.time()}
             if time.time() - self.last_cache_clear > self.cache_ttl:

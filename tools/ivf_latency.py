@@ -218,6 +218,57 @@ def leg_exclude(args, storage, ivf, queries, dev):
     return cases
 
 
+def leg_filter(args, storage, rows, queries, dev):
+    """Category filter on the resident IVF search path (tools/filter_leg.py: the
+    sides and the checks): nprobe = --exclude-nprobe, k = --k; a request filters
+    on a category that about 50 %, 10 % or 1 % of the items carry. Both host
+    sides end in rt_ivf_topk's scan, so they must agree bit for bit. One JSON
+    line per (nq, share)."""
+    import filter_leg as fl
+    n, k, nprobe = rows.shape[0], args.k, args.exclude_nprobe
+    ivf = HipIVFFlatIndex({"dimension": args.dim, "metric": "cosine", "storage_dtype": storage, "nprobe": nprobe,
+                           "index_factory": f"IVF{args.nlist},Flat", "train_iters": args.train_iters,
+                           "categories": [name for name, _ in fl.FILTER_SHARES]})
+    ivf.build(rows, [], item_categories=fl.filter_tags(n))
+    s = ivf.online_searcher(8)
+    cases = []
+    for nq in [int(x) for x in args.nq.split(",")]:
+        for j, (name, share) in enumerate(fl.FILTER_SHARES):
+            masks = (np.full(nq, 1 << j, np.uint64), np.zeros(nq, np.uint64))
+            state = {"i": 0}
+
+            def request():
+                state["i"] += 1
+                o = (state["i"] * nq) % (len(queries) - nq)
+                return queries[o:o + nq]
+
+            def none():
+                sc, pos = s.search(request(), k)
+                return sc.copy(), pos.copy()
+
+            def tags():
+                sc, pos = s.search(request(), k, tags=masks)
+                return sc.copy(), pos.copy()
+
+            def bitmap():
+                sc, pos = ivf.search_tensors(request(), k, tag_filter=masks)
+                return sc.cpu().numpy(), pos.cpu().numpy()
+
+            for _ in range(max(1, (len(queries) - nq) // max(1, nq))):   # every request window
+                got = tags()
+                state["i"] -= 1   # the same request again
+                want = bitmap()
+                fl.same_scan_or_stop([torch.from_numpy(a.copy()) for a in got], [torch.from_numpy(a) for a in want],
+                                     f"{storage} nq={nq} {name}")
+            rounds, bar = fl.run_sides(timed_alternating, {"none": none, "tags": tags, "bitmap": bitmap},
+                                       args.calls, args.warmup)
+            case = {"leg": "filter", "index": "ivf", "storage": storage, "nq": nq, "nprobe": nprobe, "eligible": name,
+                    "filled": float((got[1] >= 0).mean()), "rounds": rounds, "bar": bar}
+            print(json.dumps(case), flush=True)
+            cases.append({key: case[key] for key in ("index", "storage", "nq", "eligible", "filled", "bar")})
+    return cases
+
+
 def leg_mutate(args, storage, rows, queries, dev):
     """The mutate leg for one storage dtype: one JSON line per update size and per nq."""
     n, d, k = rows.shape[0], rows.shape[1], args.k
@@ -404,7 +455,7 @@ def main():
     ap.add_argument("--nq", default="1,8")
     ap.add_argument("--chunk-tiles", default="", help="comma list of chunk floors (256-row tiles) for the scan alone")
     ap.add_argument("--train-iters", type=int, default=10)
-    ap.add_argument("--legs", default="search", help="comma list of: search (the default), exclude, mutate")
+    ap.add_argument("--legs", default="search", help="comma list of: search (the default), exclude, mutate, batch, filter")
     ap.add_argument("--mutate-sizes", default="1,64,1024", help="known rows per update call of the mutate leg")
     ap.add_argument("--mutate-calls", type=int, default=12, help="timed update calls per size (fewer for large sizes)")
     ap.add_argument("--exclude-nprobe", type=int, default=20)
@@ -419,7 +470,7 @@ def main():
     ids = []   # positions only: the id maps are not what is measured
     summary = {"rows": n, "dim": d, "k": k, "nlist": args.nlist, "cases": []}
     legs = args.legs.split(",")
-    if set(legs) - {"search", "exclude", "mutate", "batch"}:
+    if set(legs) - {"search", "exclude", "mutate", "batch", "filter"}:
         raise SystemExit(f"unknown leg in {args.legs!r}")
     if "batch" in legs:
         # the same rows (the generator draws them first) and as many queries as the largest batch
@@ -430,6 +481,11 @@ def main():
             summary.setdefault("batch", []).extend(leg_batch(args, storage, rows, batch_queries, dev))
             torch.cuda.empty_cache()
             if legs == ["batch"]:
+                continue
+        if "filter" in legs:
+            summary.setdefault("filter", []).extend(leg_filter(args, storage, rows, queries, dev))
+            torch.cuda.empty_cache()
+            if legs == ["filter"]:
                 continue
         if "mutate" in legs:
             summary.setdefault("mutate", []).extend(

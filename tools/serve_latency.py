@@ -555,6 +555,66 @@ def leg_exclude(args):
     return out
 
 
+def leg_filter(args):
+    """Category filter on the resident Flat search path (tools/filter_leg.py: the
+    sides and the checks): N = --rows, d = 128, k = 100, float16 and float32
+    rows, nq = 1 and 8; a request filters on a category that about 50 %, 10 % or
+    1 % of the items carry."""
+    import filter_leg as fl
+    n, d, k = args.rows, 128, 100
+    out = {}
+    qs = np.random.default_rng(3).standard_normal((64, d)).astype(np.float32)
+    tags_np = fl.filter_tags(n)
+    for storage in ("float16", "float32"):
+        g = torch.Generator(device="cuda").manual_seed(1)
+        ix = HipFlatIPIndex({"dimension": d, "metric": "cosine", "storage_dtype": storage,
+                             "categories": [name for name, _ in fl.FILTER_SHARES]})
+        ix.build(torch.randn((n, d), generator=g, device="cuda"), [], item_categories=tags_np)
+        s = ix.online_searcher(8)
+        rows = ix.index[: ix.current_size]
+        for nq in (1, 8):
+            for j, (name, share) in enumerate(fl.FILTER_SHARES):
+                masks = (np.full(nq, 1 << j, np.uint64), np.zeros(nq, np.uint64))
+                state = {"i": 0}
+
+                def request():
+                    state["i"] += 1
+                    o = (state["i"] * nq) % (64 - nq)
+                    return qs[o:o + nq]
+
+                def none():
+                    sc, pos = s.search(request(), k)
+                    return sc.copy(), pos.copy()
+
+                def tags():
+                    sc, pos = s.search(request(), k, tags=masks)
+                    return sc.copy(), pos.copy()
+
+                def bitmap():
+                    sc, pos = ix.search_tensors(request(), k, tag_filter=masks)
+                    return sc.cpu().numpy(), pos.cpu().numpy()
+
+                # the scan's own filter against the same scan reading the filter's bitmap: every
+                # one of the 64 - nq request windows, bit for bit
+                d_any, d_none = (torch.from_numpy(m.view(np.int64).copy()).cuda() for m in masks)
+                bits = kernels.tag_filter_bitmap(ix._tags, d_any, d_none, nq, n_items=n)
+                for o in range(0, 64 - nq, max(1, nq)):
+                    dq = torch.nn.functional.normalize(torch.from_numpy(qs[o:o + nq]).cuda(), dim=1).to(ix.storage_dtype)
+                    fl.same_scan_or_stop(kernels.flatip_topk_online(dq, rows, k, tag_filter=(ix._tags, d_any, d_none)),
+                                         kernels.flatip_topk_online(dq, rows, k, exclude_bits=bits),
+                                         f"{storage} nq={nq} {name} window {o}")
+                got = tags()
+                state["i"] -= 1  # the same request again
+                agree = fl.compare_sides(got, bitmap())
+                rounds, bar = fl.run_sides(timed_alternating, {"none": none, "tags": tags, "bitmap": bitmap},
+                                           args.calls, args.warmup)
+                out[f"{storage}_nq{nq}_{name}"] = {"rounds": rounds, "bar": bar, "sides_agree": agree,
+                                                   "filled": float((got[1] >= 0).mean())}
+        del s, ix, rows
+        torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--baseline", action="store_true", help="only the API of the commit before the online path")
@@ -574,7 +634,7 @@ def main():
            "lib": os.environ.get("RTREC_HIP_LIB", "in-tree"), "device": torch.cuda.get_device_name(0)}
     legs = {"serve_q1_ref": leg_serve_q1_ref, "corpus_1m": leg_corpus_1m, "embed_b1": leg_embed_b1,
             "serve_e2e": leg_serve_e2e, "tower_kernel": leg_tower_kernel, "mutate": leg_mutate,
-            "exclude": leg_exclude}
+            "exclude": leg_exclude, "filter": leg_filter}
     for name in args.legs.split(","):
         if name not in legs:
             ap.error(f"unknown leg {name!r}")
