@@ -461,6 +461,64 @@ int rt_tag_filter_bitmap(const uint64_t* item_tags, int64_t n_items, const uint6
                          void* stream);
 
 /* ------------------------------------------------------------------------
+ * MMR re-ranking of retrieved candidates: the ranking stage of the request
+ * path (src/serving/service.py:204-228 retrieves num_recommendations * 10
+ * candidates and hands them to a second stage that keeps num_recommendations;
+ * with no ranker installed it truncates). Maximal Marginal Relevance
+ * (Carbonell & Goldstein, SIGIR 1998) needs nothing but the candidates' own
+ * stored rows, which are resident.
+ *
+ * rt_mmr_rerank: per query, a greedy choice of k of its n_cand candidates.
+ *   cand_scores / cand_ids [nq, n_cand], contiguous: what rt_flatip_topk,
+ *   rt_flatip_topk_online* and rt_ivf_topk* write — scores are the relevance,
+ *   ids ORIGINAL corpus positions, pads (-FLT_MAX, -1). rows [n_rows, d] of
+ *   `dtype`, 16-byte aligned, d / dtype limits of rt_flatip_topk_online (f32:
+ *   d % 4 == 0, f16/bf16: d % 8 == 0, d <= 256). pos_slot: optional int32
+ *   [n_pos] (device): the stored row of position p, -1 = none (the array
+ *   rt_ivf_lists_update keeps); NULL = the identity (a Flat corpus).
+ *   A candidate is ABSENT, wherever it stands in its row, if its id is < 0 or
+ *   >= n_pos or its slot is < 0 or >= n_rows; an absent candidate is never
+ *   read and never chosen.
+ *   lambda: fp32 [nq] on the DEVICE, one value per query, clamped to [0, 1] by
+ *   the kernel — data, not a launch argument: one captured graph serves every
+ *   lambda.
+ *   sim(i, j): normalize == 0: the inner product of the two stored rows,
+ *   widened to fp32 (the cosine metric, whose rows are stored unit-norm);
+ *   normalize != 0: that inner product times 1/sqrt(|i|^2) times 1/sqrt(|j|^2);
+ *   a zero row has similarity 0 to everything (the inner_product metric).
+ *   Selection, t = 0 .. k - 1, over the present candidates not yet chosen:
+ *   obj(i) = lambda * score_i - (1 - lambda) * m_i, m_i = the maximum of
+ *   sim(i, j) over the chosen j (0 while nothing is chosen); the largest obj
+ *   is chosen, ties go to the LOWEST CANDIDATE INDEX (the input order).
+ *   Duplicate positions among the candidates are legal: each is a candidate
+ *   of its own.
+ *   out_scores / out_ids [nq, k]: the chosen candidates' ORIGINAL scores and
+ *   positions in selection order (the list is no longer score-sorted);
+ *   (-FLT_MAX, -1) fills the slots past the number of present candidates.
+ *   The outputs must not overlap the inputs.
+ *   Determinism: a query's result depends only on its candidate row, the
+ *   stored values of those rows, its lambda and normalize — not on nq, its row
+ *   index, the grid, or whether pos_slot was given. A dot product is four
+ *   sequential fmaf chains (lane l of a candidate takes the 16-byte chunks
+ *   l, l + 4, ... of the row, elements ascending) folded as (p0 + p1) + (p2 +
+ *   p3); the order depends on (d, dtype) only; no floating-point atomics.
+ *   One launch (one workgroup per query, rows staged once in LDS in storage
+ *   dtype), no workspace, no host read: stream-ordered and capturable.
+ *   Status, before any device work: RT_ERR_INVALID for a NULL operand (rows
+ *   may be NULL only when n_rows == 0; pos_slot may always be NULL), k <= 0,
+ *   n_cand <= 0, d <= 0, a negative size, an unknown dtype, rows not 16-byte
+ *   aligned (the other operands: their element size), out_* overlapping
+ *   cand_* or each other; RT_ERR_UNSUPPORTED for n_cand > RT_MMR_MAX_CAND,
+ *   k > n_cand, a refused d / dtype pair, n_pos >= 2^31 - 1. nq == 0: RT_OK.
+ * ------------------------------------------------------------------------ */
+#define RT_MMR_MAX_CAND 128      /* = RT_ONLINE_MAX_K = RT_IVF_MAX_K */
+int rt_mmr_rerank(const float* cand_scores, const int64_t* cand_ids, int64_t nq, int n_cand,
+                  const void* rows, int64_t n_rows, int d, int dtype,
+                  const int32_t* pos_slot, int64_t n_pos,
+                  const float* lambda, int normalize, int k,
+                  float* out_scores, int64_t* out_ids, void* stream);
+
+/* ------------------------------------------------------------------------
  * In-place mutation of IVF lists stored with slack: the streaming item_update
  * path (RetrievalEngine.update_index, src/serving/retrieval.py:228-246,
  * 629-641) on the reference's default index.

@@ -19,6 +19,13 @@ index is ``"IVF1024,Flat"`` with ``nprobe = 20`` — and adds a ``retrieval`` bl
 to the results: index type, nlist, nprobe and recall@k of the index's lists
 against the exact lists for every k of ``--k-values``.
 
+``--mmr-lambda`` (with ``--mmr-candidates``) evaluates the lists the MMR
+re-rank would serve — the ranking stage of the request path
+(src/serving/service.py:204-228): the device-resident top ``mmr_candidates`` are
+re-ranked into the max(k) lists by ``rt_mmr_rerank`` before any metric, and both
+values are recorded in the results next to ``diversity@10`` / ``novelty@10``.
+Off by default: without the flags the results are what they were.
+
     python -m rtrec_amd.evaluate_model --checkpoint models/checkpoints/two_tower_best.pth
 """
 from __future__ import annotations
@@ -49,6 +56,11 @@ def build_parser() -> argparse.ArgumentParser:
                         "recommendations are that index's, and the results gain a 'retrieval' block")
     p.add_argument("--index-factory", type=str, default=None, help="the index's factory string (hip_ivf: IVF1024,Flat)")
     p.add_argument("--nprobe", type=int, default=None, help="lists probed per user (hip_ivf: 20)")
+    p.add_argument("--mmr-lambda", type=float, default=None,
+                   help="re-rank the top --mmr-candidates into the max(k) lists by Maximal Marginal Relevance "
+                        "(0..1: the weight of the score against the similarity to what is already chosen); off by default")
+    p.add_argument("--mmr-candidates", type=int, default=None,
+                   help="candidates per user of the re-rank (default min(10 * max(k), 128, items); at most 128)")
     return p
 
 
@@ -130,16 +142,20 @@ def run(args) -> dict:
     test_users = list(gt.keys())
     t0 = time.time()
     index_config, index_info = index_config_from_args(args), {}
+    mmr = {}
+    if getattr(args, "mmr_lambda", None) is not None or getattr(args, "mmr_candidates", None) is not None:
+        mmr = {"mmr_lambda": args.mmr_lambda, "mmr_candidates": args.mmr_candidates}
     _, ids = generate_recommendations(model, test_users, train_items, uf, mf, top_k=max(k_values),
                                       batch_size=args.batch_size, device=device, return_tensors=True,
-                                      index_config=index_config, index_info=index_info)
+                                      index_config=index_config, index_info=index_info, **mmr)
     recs = recommendations_from_ids(ids, test_users)
     t_recs = time.time() - t0
     retrieval = None
     if index_config is not None:
         # what the index costs: its lists against the exact ones, for the same users and exclusions
         _, exact_ids = generate_recommendations(model, test_users, train_items, uf, mf, top_k=max(k_values),
-                                                batch_size=args.batch_size, device=device, return_tensors=True)
+                                                batch_size=args.batch_size, device=device, return_tensors=True,
+                                                **mmr)
         retrieval = {**index_info, **retrieval_recall(ids, exact_ids, k_values)}
     evaluator = Evaluator(k_values=k_values, num_items=mf.shape[0])
     metrics = evaluator.evaluate(recs, gt, exclude_items=train_items)
@@ -148,6 +164,11 @@ def run(args) -> dict:
     results.update(beyond_accuracy(model, ids, mf, data.train_interactions["movie_idx"].to_numpy(), k=10))
     results.update({"num_test_users": len(test_users), "num_items": int(mf.shape[0]), "checkpoint": args.checkpoint,
                     "data": source, "recommendation_seconds": t_recs})
+    if mmr:   # next to diversity@10 / novelty@10, which they move
+        from .evaluation.offline import _mmr_candidates
+        results.update({"mmr_lambda": float(args.mmr_lambda),
+                        "mmr_candidates": _mmr_candidates(max(k_values), args.mmr_lambda, args.mmr_candidates,
+                                                          int(mf.shape[0]))})
     if retrieval is not None:
         results["retrieval"] = retrieval
     out = Path(args.output)

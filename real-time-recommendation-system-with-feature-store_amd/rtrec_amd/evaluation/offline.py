@@ -73,7 +73,8 @@ def build_eval_index(item_emb: torch.Tensor, index_config: Dict[str, Any]):
 def recommend_tensors(model: TwoTowerModel, user_features: torch.Tensor, item_features: torch.Tensor,
                       test_users: torch.Tensor, train_offsets: torch.Tensor, train_items: torch.Tensor,
                       top_k: int = 100, batch_size: int = 256, index_config: Optional[Dict[str, Any]] = None,
-                      index_info: Optional[Dict[str, Any]] = None):
+                      index_info: Optional[Dict[str, Any]] = None, mmr_lambda: Optional[float] = None,
+                      mmr_candidates: Optional[int] = None):
     """Device-resident form: ``user_features`` [n_users, Fu] / ``item_features``
     [n_items, Fi] fp32 tables, ``test_users`` int64 [U], train items as a CSR
     over user rows. Returns (scores fp32 [U, top_k], item ids int64 [U, top_k]),
@@ -85,7 +86,16 @@ def recommend_tensors(model: TwoTowerModel, user_features: torch.Tensor, item_fe
     so the lists are what a deployment with that index (the default
     ``"IVF1024,Flat"``, ``nprobe = 20``) would serve; ``top_k`` above the
     index's limit raises the index's own error. ``index_info`` (a dict) is
-    filled with the index type, nlist and nprobe used."""
+    filled with the index type, nlist and nprobe used.
+
+    ``mmr_lambda`` (None = off; in [0, 1]) / ``mmr_candidates`` (default
+    ``min(10 * top_k, 128, n_items)``; top_k <= mmr_candidates <= 128): the lists
+    are the MMR re-rank (``rt_mmr_rerank``, cosine similarities of the item
+    embeddings) of the device-resident top ``mmr_candidates`` — exact, or the
+    index's — into ``top_k``, in selection order with the original scores; with
+    and without ``index_config``."""
+    n_cand = _mmr_candidates(top_k, mmr_lambda, mmr_candidates, int(item_features.shape[0]))
+    k_search = n_cand or top_k
     item_emb = model.get_item_embeddings({"numerical": item_features, "categorical": {}})
     n_items = item_emb.shape[0]
     u_idx = test_users.to(torch.int64)
@@ -102,8 +112,30 @@ def recommend_tensors(model: TwoTowerModel, user_features: torch.Tensor, item_fe
             nlist = None if fallback else getattr(index, "nlist", None)
             index_info.update({"index_type": index_config.get("index_type", "hip_ivf"), "nlist": nlist,
                                "nprobe": None if nlist is None else index._n_probe()})
-        return index.search_tensors(user_emb.contiguous(), top_k, exclude_bits=bits)
-    return kernels.flatip_topk(user_emb.contiguous(), item_emb.contiguous(), top_k, exclude_bits=bits)
+        scores, ids = index.search_tensors(user_emb.contiguous(), k_search, exclude_bits=bits)
+        return index.mmr_rerank_tensors(scores, ids, top_k, mmr_lambda) if n_cand else (scores, ids)
+    item_emb = item_emb.contiguous()
+    scores, ids = kernels.flatip_topk(user_emb.contiguous(), item_emb, k_search, exclude_bits=bits)
+    if n_cand:
+        return kernels.mmr_rerank(scores, ids, item_emb, top_k, mmr_lambda, normalize=True)
+    return scores, ids
+
+
+def _mmr_candidates(top_k: int, mmr_lambda: Optional[float], mmr_candidates: Optional[int], n_items: int) -> int:
+    """The candidates per user of a re-ranked evaluation (0: off), with the bounds of
+    ``HipFlatIPIndex.search``: 0 <= mmr_lambda <= 1, top_k <= mmr_candidates <= 128."""
+    if mmr_lambda is None:
+        if mmr_candidates is not None:
+            raise ValueError("mmr_candidates without mmr_lambda: the re-rank is off (mmr_lambda=None)")
+        return 0
+    if not 0.0 <= float(mmr_lambda) <= 1.0:
+        raise ValueError(f"mmr_lambda={mmr_lambda}: 0 <= mmr_lambda <= 1")
+    cap = kernels.MMR_MAX_CAND
+    if mmr_candidates is None:
+        mmr_candidates = max(min(10 * top_k, cap, n_items), min(top_k, cap))
+    if not top_k <= int(mmr_candidates) <= cap:
+        raise ValueError(f"mmr_candidates={mmr_candidates}: top_k <= mmr_candidates <= {cap} (top_k={top_k})")
+    return int(mmr_candidates)
 
 
 def _pad_like_reference(ids_row: np.ndarray, scores_row: np.ndarray, n_items: int, top_k: int) -> List[int]:
@@ -128,14 +160,17 @@ def generate_recommendations(model: TwoTowerModel, test_users: list, train_items
                              batch_size: int = 256, device: Optional[str] = None,
                              return_tensors: bool = False, pad_excluded: bool = False,
                              index_config: Optional[Dict[str, Any]] = None,
-                             index_info: Optional[Dict[str, Any]] = None):
+                             index_info: Optional[Dict[str, Any]] = None, mmr_lambda: Optional[float] = None,
+                             mmr_candidates: Optional[int] = None):
     """evaluate_model.py:162-234 → Dict[user_idx, List[movie_idx]] (or the
     device (scores, ids) with ``return_tensors``). ``pad_excluded``: lists of
     users with fewer than ``top_k`` eligible items are padded with their
     excluded items as the reference pads them (see the module docstring).
     ``index_config`` / ``index_info``: as :func:`recommend_tensors` — the lists
     of an index (``{"index_type": "hip_ivf", "index_factory": "IVF1024,Flat",
-    "nprobe": 20}``) instead of the exact ones; without it nothing changes."""
+    "nprobe": 20}``) instead of the exact ones; without it nothing changes.
+    ``mmr_lambda`` / ``mmr_candidates``: as :func:`recommend_tensors` — the lists are
+    the MMR re-rank of the top ``mmr_candidates`` into ``top_k``; off by default."""
     dev = _dev(device)
     uf = torch.as_tensor(np.asarray(user_features, np.float32)).to(dev)
     mf = torch.as_tensor(np.asarray(movie_features, np.float32)).to(dev)
@@ -148,7 +183,7 @@ def generate_recommendations(model: TwoTowerModel, test_users: list, train_items
     t_off, t_items = csr_from_sets(rows, dev)
     scores, ids = recommend_tensors(model, uf, mf, torch.tensor(users, dtype=torch.int64, device=dev), t_off,
                                     t_items, top_k=top_k, batch_size=batch_size, index_config=index_config,
-                                    index_info=index_info)
+                                    index_info=index_info, mmr_lambda=mmr_lambda, mmr_candidates=mmr_candidates)
     if return_tensors:
         return scores, ids
     if not pad_excluded:

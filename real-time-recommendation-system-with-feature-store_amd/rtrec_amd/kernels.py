@@ -600,6 +600,63 @@ def topk_merge(scores: torch.Tensor, ids: torch.Tensor, k_out: int
     return os_, oi
 
 
+MMR_MAX_CAND = 128   # RT_MMR_MAX_CAND
+
+
+def mmr_rerank(scores: torch.Tensor, positions: torch.Tensor, rows: torch.Tensor, k: int, lam,
+               pos_slot: Optional[torch.Tensor] = None, n_pos: Optional[int] = None, normalize: bool = False,
+               out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Maximal Marginal Relevance over retrieved candidates (rt_mmr_rerank): per
+    query a greedy choice of ``k`` of the ``n_cand <= 128`` candidates
+    ``(scores, positions)`` ``[nq, n_cand]`` a search returned, maximising
+    ``lam * score - (1 - lam) * max similarity to what is already chosen``; ties go
+    to the lower candidate index. Returns the chosen candidates' original
+    (scores, positions) ``[nq, k]`` in selection order, ``(-FLT_MAX, -1)`` past the
+    number of present candidates.
+
+    ``rows`` ``[n_rows, d]``: the stored embeddings (fp32 / fp16 / bf16).
+    ``pos_slot``: optional int32 ``[n_pos]``, the stored row of a position (-1:
+    none); None: the identity. ``n_pos``: positions are valid in ``[0, n_pos)``
+    (default: ``len(pos_slot)``, else ``len(rows)``). ``lam``: a float, or an fp32
+    device tensor ``[nq]`` (one value per query; read by the kernel, so a captured
+    call follows a value changed in place). ``normalize``: similarities are
+    cosines of the stored rows instead of their inner products."""
+    native.require_device(scores, positions, rows, pos_slot, lam if isinstance(lam, torch.Tensor) else None,
+                          what="mmr_rerank")
+    if scores.dim() != 2 or positions.shape != scores.shape or rows.dim() != 2:
+        raise ValueError(f"shape mismatch: scores {tuple(scores.shape)} positions {tuple(positions.shape)} "
+                         f"rows {tuple(rows.shape)}")
+    if scores.dtype != torch.float32 or positions.dtype != torch.int64:
+        raise TypeError("mmr_rerank expects fp32 scores and int64 positions")
+    if not (scores.is_contiguous() and positions.is_contiguous() and rows.is_contiguous()):
+        raise ValueError("mmr_rerank expects contiguous scores, positions and rows")
+    nq, n_cand = scores.shape
+    if not 0 < k <= n_cand:
+        raise ValueError(f"mmr_rerank: need 0 < k <= n_cand, got k={k}, n_cand={n_cand}")
+    if n_cand > MMR_MAX_CAND:
+        raise ValueError(f"mmr_rerank: at most {MMR_MAX_CAND} candidates per query, got {n_cand}")
+    if pos_slot is not None and (pos_slot.dtype != torch.int32 or pos_slot.dim() != 1
+                                 or not pos_slot.is_contiguous()):
+        raise TypeError("mmr_rerank: pos_slot must be a contiguous int32 vector")
+    if n_pos is None:
+        n_pos = pos_slot.numel() if pos_slot is not None else rows.shape[0]
+    if n_pos < 0 or (pos_slot is not None and n_pos > pos_slot.numel()):
+        raise ValueError("mmr_rerank: n_pos outside pos_slot")
+    if isinstance(lam, torch.Tensor):
+        if lam.dtype != torch.float32 or lam.dim() != 1 or lam.numel() < nq or not lam.is_contiguous():
+            raise ValueError("mmr_rerank: lam must be a float or a contiguous fp32 tensor [nq]")
+    else:
+        lam = torch.full((max(nq, 1),), float(lam), dtype=torch.float32, device=scores.device)
+    os_, oi = _topk_out(out, nq, k, scores.device)
+    if nq == 0:
+        return os_, oi
+    n_rows, d = rows.shape
+    call("rt_mmr_rerank", ptr(scores), ptr(positions), nq, n_cand, ptr(rows) if n_rows else None, n_rows, d,
+         native.dtype_code(rows.dtype), ptr(pos_slot), int(n_pos), ptr(lam), int(bool(normalize)), int(k),
+         ptr(os_), ptr(oi), stream_of(scores))
+    return os_, oi
+
+
 # ---------------------------------------------------------------------------
 # IVF-Flat (faiss "IVF<nlist>,Flat" + nprobe, src/serving/retrieval.py:60-62,101-133)
 # ---------------------------------------------------------------------------

@@ -161,6 +161,8 @@ SIGNATURES = {
     "rt_ivf_lists_update_workspace_bytes": (c_size, [c_i64, c_i64]),
     "rt_ivf_lists_update": (c_int, [vp, c_i64, c_int, c_int, vp, c_i64, vp, vp, vp, vp, vp, vp, vp, c_i64, vp, vp,
                                     c_size, vp]),
+    "rt_mmr_rerank": (c_int, [vp, vp, c_i64, c_int, vp, c_i64, c_int, c_int, vp, c_i64, vp, c_int, c_int, vp, vp,
+                              vp]),
     "rt_topk_merge": (c_int, [vp, vp, c_i64, c_int, c_int, c_int, vp, vp, vp]),
     "rt_flatip_topk_tuning": (c_int, [c_int, c_int, c_int]),
     "rt_flatip_topk_shard_workspace_bytes": (c_size, [c_i64, c_i64, c_int, c_int, c_int]),

@@ -83,6 +83,11 @@ class OnlineRecommender:
     are keyed ``(nq, k_search, by_ids, items, seen)``; over IVF lists every
     search graph is keyed ``(nq, k_search, by_ids, items, seen, nprobe)``.
 
+    MMR re-rank (``recommend(mmr_lambda=..., mmr_candidates=...)``): the scan
+    retrieves the candidates and ``rt_mmr_rerank`` — one more launch at the end of
+    the same chain — chooses k of them; lambda travels as data, so those graphs'
+    keys only gain ``("mmr", k)`` at their end and one graph serves every lambda.
+
     Staleness. Index: ``build`` / ``add`` / ``load`` bump its generation and
     the search graphs are dropped and captured again. Model: the graphs hold the live
     parameter and buffer tensors, so in-place changes (optimiser steps,
@@ -223,11 +228,13 @@ class OnlineRecommender:
         kernels.tower_infer(a, native.stream_of(self._d_x))
 
     def _sequence(self, nq: int, k: int, by_ids: bool, items: bool = False, seen: bool = False,
-                  tags: bool = False):
+                  tags: bool = False, mmr_k: int = 0):
         """The stream-ordered chain of one call (k = 0: embed only). ``items``: the
         per-request lists staged in the searcher's pinned CSR; ``seen``: the resident
         seen-items CSR, its rows the device ids the tower gather reads; ``tags``: the
-        category masks staged in the searcher's pinned mask buffer."""
+        category masks staged in the searcher's pinned mask buffer; ``mmr_k``: the k
+        results of the scan are re-ranked into ``mmr_k`` (``rt_mmr_rerank``, lambda
+        staged in the searcher's pinned buffer)."""
         if by_ids:
             self._d_ids[:nq].copy_(self._h_ids[:nq], non_blocking=True)
         else:
@@ -244,8 +251,14 @@ class OnlineRecommender:
                 sources.append(self._searcher._list_source())
             if tags:
                 self._searcher._d_tm.copy_(self._searcher._h_tm, non_blocking=True)
+            if mmr_k:
+                self._searcher._d_lam.copy_(self._searcher._h_lam, non_blocking=True)
             self._searcher._device_chain(nq, k, sources, tags=tags)
-            self._searcher._download(nq, k)
+            if mmr_k:
+                self._searcher._device_mmr(nq, k, mmr_k)
+                self._searcher._download(nq, mmr_k, True)
+            else:
+                self._searcher._download(nq, k)
 
     # -- seen items ----------------------------------------------------------------
     def set_seen(self, histories) -> None:
@@ -330,7 +343,7 @@ class OnlineRecommender:
         return self.index if flat is None else flat
 
     def _run(self, x: Optional[Rows], ids: Optional[np.ndarray], k: int, items: bool = False, seen: bool = False,
-             tags: bool = False):
+             tags: bool = False, mmr_k: int = 0):
         """Stage the rows, run / replay the chain, synchronise. Under ``lock``."""
         by_ids = ids is not None
         nq = len(ids) if by_ids else x.shape[0]
@@ -346,9 +359,11 @@ class OnlineRecommender:
         nprobe = getattr(self._searcher, "_nprobe", 0)   # OnlineIVFSearcher: read from the index at this call
         if k and nprobe:
             key = (nq, k, by_ids, items, seen, nprobe)
-        seq = (nq, k, by_ids, items, seen, tags)
+        seq = (nq, k, by_ids, items, seen, tags, mmr_k)
         if tags:   # one more flag, at the end: one graph serves every mask value
             key = (nq, k, by_ids, items, seen) + key[5:] + ("tags",)
+        if mmr_k:  # at the very end, lambda being data: one graph serves every value
+            key = key + ("mmr", mmr_k)
         if os.environ.get("RTREC_ONLINE_GRAPH", "1") == "0":
             self._sequence(*seq)
         else:
@@ -394,7 +409,8 @@ class OnlineRecommender:
 
     def recommend(self, user_features: Optional[Features] = None, *, user_ids=None, k: int = 10,
                   filter_ids: Optional[List[str]] = None, exclude_items=None, exclude_seen: bool = False,
-                  filter_categories=None, exclude_categories=None
+                  filter_categories=None, exclude_categories=None,
+                  mmr_lambda: Optional[float] = None, mmr_candidates: Optional[int] = None
                   ) -> Tuple[List[List[str]], List[List[float]]]:
         """``(ids, scores)`` lists, as ``index.search(embed(...), k, filter_ids)``.
 
@@ -410,9 +426,16 @@ class OnlineRecommender:
         ``filter_categories`` / ``exclude_categories`` (the request schema's
         ``filter_categories``): as ``HipFlatIPIndex.search`` — tested by the same
         scan, composing with both exclusion sources; one more fixed-size H2D copy
-        in the chain, one graph for every mask value."""
+        in the chain, one graph for every mask value.
+        ``mmr_lambda`` / ``mmr_candidates``: as ``HipFlatIPIndex.search`` — the
+        ranking stage of the request path (src/serving/service.py:204-228): the top
+        ``mmr_candidates`` (default ``min(10 * k, 128, index size)``) are re-ranked
+        into k by ``rt_mmr_rerank``, one more launch at the end of the same chain;
+        lambda is data (one fixed-size H2D copy), so the graph key gains only
+        ``("mmr", k)`` and one graph serves every lambda. Not with ``filter_ids``."""
         x, ids = self._rows_of(user_features, user_ids)
         idx = self.index
+        n_cand = idx._mmr_args(k, mmr_lambda, mmr_candidates, filter_ids)
         if idx.index is None:
             raise ValueError("Index not built yet")
         if exclude_seen and ids is None:
@@ -420,13 +443,15 @@ class OnlineRecommender:
         if exclude_seen and self._seen_ids is None:
             raise ValueError("exclude_seen needs set_seen(histories) first")
         nq = len(ids) if ids is not None else x.shape[0]
-        k_search = min(k * 2, idx.current_size) if filter_ids else k
+        k_search = n_cand if n_cand else (min(k * 2, idx.current_size) if filter_ids else k)
         if k_search <= 0 or nq == 0:
             return [[] for _ in range(nq)], [[] for _ in range(nq)]
         items = exclude_items is not None
         masks = idx._query_masks(filter_categories, exclude_categories, nq)
         cats = {} if masks is None else dict(filter_categories=filter_categories,
                                              exclude_categories=exclude_categories)
+        if n_cand:
+            cats.update(mmr_lambda=mmr_lambda, mmr_candidates=n_cand)
         with self.lock:
             s = self._searcher
             resident = k_search <= OnlineSearcher.MAX_K and nq <= self.max_batch
@@ -452,7 +477,10 @@ class OnlineRecommender:
                     del self._graphs[key]
             if masks is not None:
                 s._stage_tags(nq, masks)
-            self._run(x, ids, k_search, items, exclude_seen, tags=masks is not None)
-            n = nq * k_search
-            return _lists_from_positions(s._h_s_np[:n].reshape(nq, k_search), s._h_p_np[:n].reshape(nq, k_search),
+            if n_cand:
+                s._stage_mmr(nq, mmr_lambda)
+            self._run(x, ids, k_search, items, exclude_seen, tags=masks is not None, mmr_k=k if n_cand else 0)
+            k_got = k if n_cand else k_search
+            n = nq * k_got
+            return _lists_from_positions(s._h_s_np[:n].reshape(nq, k_got), s._h_p_np[:n].reshape(nq, k_got),
                                          idx.id_map, k, filter_ids)

@@ -347,9 +347,59 @@ class _HbmIndex(IndexBase):
         self.reverse_id_map = data["reverse_id_map"]
         self._ids = [self.id_map.get(i) for i in range(n)]
 
+    # -- MMR re-ranking (the ranking stage of the request path, src/serving/service.py:204-228) --
+    MMR_MAX_CANDIDATES = kernels.MMR_MAX_CAND
+
+    def _check_mmr(self):
+        """Raise where the class (or its mode) does not serve the MMR re-rank."""
+        if self._l2:
+            raise ValueError("mmr_lambda: the MMR re-rank is served for the inner-product metrics ('cosine', "
+                             "'inner_product'), not in the L2 mode")
+
+    def _mmr_args(self, k: int, mmr_lambda: Optional[float], mmr_candidates: Optional[int],
+                  filter_ids=None) -> Optional[int]:
+        """The candidates per query of a re-ranked search (None: ``mmr_lambda`` is None,
+        the re-rank is off). The default is the reference's 10x over-fetch
+        (service.py:206) clamped to the kernel's cap and to the corpus:
+        ``min(10 * k, 128, current_size)``, and never below ``min(k, 128)``."""
+        if mmr_lambda is None:
+            if mmr_candidates is not None:
+                raise ValueError("mmr_candidates without mmr_lambda: the re-rank is off (mmr_lambda=None)")
+            return None
+        self._check_mmr()
+        if not 0.0 <= float(mmr_lambda) <= 1.0:   # a NaN fails too
+            raise ValueError(f"mmr_lambda={mmr_lambda}: 0 <= mmr_lambda <= 1")
+        if filter_ids is not None:
+            raise ValueError("filter_ids together with mmr_lambda: the allow-list is a host post-filter over a 2k "
+                             "over-fetch; combining it with the re-rank is out of scope")
+        cap = self.MMR_MAX_CANDIDATES
+        if mmr_candidates is None:
+            mmr_candidates = max(min(10 * k, cap, self.current_size), min(k, cap))
+        if not k <= int(mmr_candidates) <= cap:
+            raise ValueError(f"mmr_candidates={mmr_candidates}: k <= mmr_candidates <= {cap} (k={k})")
+        return int(mmr_candidates)
+
+    def _mmr_operands(self) -> Tuple[torch.Tensor, Optional[torch.Tensor], int]:
+        """(rows, pos_slot, n_pos) of ``kernels.mmr_rerank`` over this index: the stored
+        rows, the stored row of a position (None: the identity) and the number of positions."""
+        raise NotImplementedError
+
+    def mmr_rerank_tensors(self, scores: torch.Tensor, positions: torch.Tensor, k: int, mmr_lambda
+                           ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Re-rank what ``search_tensors`` returned — (scores, positions) ``[nq, n_cand]``
+        on the device, n_cand <= 128 — into the MMR choice of ``k`` per query
+        (``rt_mmr_rerank`` over the index's own stored rows; similarities are cosines
+        unless the metric is ``"cosine"``, whose rows are stored unit-norm): device
+        (scores, positions) ``[nq, k]`` in selection order, original scores."""
+        self._check_mmr()
+        rows, pos_slot, n_pos = self._mmr_operands()
+        return kernels.mmr_rerank(scores.contiguous(), positions.contiguous(), rows, k, mmr_lambda, pos_slot=pos_slot,
+                                  n_pos=n_pos, normalize=self.metric != "cosine")
+
     # -- search (the single-GPU indexes) -------------------------------------
     def search(self, query_embeddings: Array, k: int = 10, filter_ids: Optional[List[str]] = None,
-               exclude_ids=None, filter_categories=None, exclude_categories=None
+               exclude_ids=None, filter_categories=None, exclude_categories=None,
+               mmr_lambda: Optional[float] = None, mmr_candidates: Optional[int] = None
                ) -> Tuple[List[List[str]], List[List[float]]]:
         """retrieval.py:141-197: normalise, top-k_search (2k when filtering), map
         positions to ids, drop -1 padding, apply the filter, stop at k.
@@ -372,10 +422,25 @@ class _HbmIndex(IndexBase):
         rows scanned (for an IVF index: the probed lists, as with Faiss), and it
         composes with ``exclude_ids`` by union of what is skipped. Calls within
         the online limits stay on the resident searcher (the scan tests the tags
-        itself); the others go through ``rt_tag_filter_bitmap``."""
+        itself); the others go through ``rt_tag_filter_bitmap``.
+
+        ``mmr_lambda`` (None = off; 0 <= mmr_lambda <= 1) / ``mmr_candidates``
+        (default ``min(10 * k, 128, current_size)``; k <= mmr_candidates <= 128):
+        the ranking stage of the request path (src/serving/service.py:204-228) as
+        Maximal Marginal Relevance — the top ``mmr_candidates`` are retrieved as
+        above, exclusions and category filters included, and ``rt_mmr_rerank``
+        chooses k of them greedily by ``mmr_lambda * score - (1 - mmr_lambda) * max
+        similarity to what is already chosen`` over the index's own stored rows
+        (similarities are cosines). The lists come in selection order with the
+        original scores, so they are no longer score-sorted. Calls within the
+        online limits stay resident (one more launch in the captured chain, lambda
+        is data: one graph serves every value); the others re-rank the device
+        tensors of ``search_tensors`` and copy k results per query to the host.
+        Not with ``filter_ids``, not in the L2 mode: ``ValueError``."""
+        n_cand = self._mmr_args(k, mmr_lambda, mmr_candidates, filter_ids)
         if self.index is None:
             raise ValueError("Index not built yet")
-        k_search = min(k * 2, self.current_size) if filter_ids else k
+        k_search = n_cand if n_cand else (min(k * 2, self.current_size) if filter_ids else k)
         nq = 1 if np.ndim(query_embeddings) == 1 else len(query_embeddings)
         if k_search <= 0 or (self.mutable and self.current_size == 0):  # emptied by remove: nothing to scan
             return [[] for _ in range(nq)], [[] for _ in range(nq)]
@@ -386,10 +451,16 @@ class _HbmIndex(IndexBase):
             if self._online is None:
                 self._online = self.online_searcher(self.online_max_batch)
             with self._online.lock:  # the returned buffers are the searcher's: read them under its lock
-                scores, pos = self._online.search(query_embeddings, k_search, exclude=excl, tags=masks)
+                if n_cand:
+                    scores, pos = self._online.search(query_embeddings, k_search, exclude=excl, tags=masks,
+                                                      mmr=(k, mmr_lambda))
+                else:
+                    scores, pos = self._online.search(query_embeddings, k_search, exclude=excl, tags=masks)
                 return _lists_from_positions(scores, pos, self.id_map, k, filter_ids)
         bits = None if excl is None else kernels.exclusion_bitmap(nq, self.current_size, excl, self._dev())
         scores, pos = self.search_tensors(query_embeddings, k_search, exclude_bits=bits, tag_filter=masks)
+        if n_cand:
+            scores, pos = self.mmr_rerank_tensors(scores, pos, k, mmr_lambda)
         return _lists_from_positions(scores.cpu().numpy(), pos.cpu().numpy(), self.id_map, k, filter_ids)
 
     def _filter_bits(self, tag_filter, nq: int, exclude_bits: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
@@ -462,6 +533,13 @@ class HipFlatIPIndex(_HbmIndex):
     Measured ("Category filters"; 1M x 128, k = 100, nq 1 and 8, float16 and
     float32, 50 / 10 / 1 % of the items eligible; p50 of the resident call in us): 95-215
     without a filter, 95-212 with it (-28 to 11 us), against 922-3536 through the bitmap route.
+
+    ``search(..., mmr_lambda=, mmr_candidates=)`` (default off): the ranking stage of
+    the request path (src/serving/service.py:204-228) as an MMR re-rank of the top
+    ``mmr_candidates`` into k over the stored rows (``rt_mmr_rerank``); resident
+    within the online limits (one more launch in the chain, lambda as data), on the
+    device tensors of ``search_tensors`` otherwise (``mmr_rerank_tensors``).
+    Inner-product metrics, not with ``filter_ids`` ("MMR re-ranking").
     """
 
     _searcher_takes_exclude = True   # OnlineSearcher: rt_flatip_topk_online_lists
@@ -560,6 +638,9 @@ class HipFlatIPIndex(_HbmIndex):
             return kernels.flatl2_topk(kernels.l2_augment(q, 0), self.index[: self.current_size], self.dimension, k,
                                        exclude_bits=exclude_bits)
         return kernels.flatip_topk(q, self.index[: self.current_size], k, exclude_bits=exclude_bits)
+
+    def _mmr_operands(self):
+        return self.index[: self.current_size], None, self.current_size   # position p is stored row p
 
     def add(self, embeddings: Array, ids: List[str], item_categories=None):
         """retrieval.py:199-226: incremental append (Kafka item_update path);
@@ -785,6 +866,13 @@ class OnlineSearcher:
     fixed-size H2D copies of them in front of ``rt_flatip_topk_online_lists``
     — the lists are data, so one graph serves every list length.
 
+    MMR re-rank (``search(q, k, mmr=(k_out, lam))``): a second device pair for the
+    re-ranked scores / positions and a pinned ``[max_batch]`` lambda buffer with
+    its device twin are allocated here too; such a call replays a graph whose key
+    ends in ``("mmr", k_out)`` and whose chain carries one fixed-size H2D copy of
+    lambda and, after the scan, ``rt_mmr_rerank`` — lambda is data, so one graph
+    serves every value; the keys of calls without ``mmr`` are unchanged.
+
     The searcher holds the index's row pointer and size: ``build`` / ``add`` /
     ``load`` / ``remove`` bump the index's generation, and a searcher that finds
     its generation stale drops its graphs and captures again. An in-place
@@ -836,6 +924,14 @@ class OnlineSearcher:
         self._h_tm_np = self._h_tm.numpy()
         self._d_tm = torch.zeros(2 * mb, dtype=torch.int64, device=dev)
         self._item_tags: Optional[torch.Tensor] = None   # the index's resident tags (per generation)
+        # the MMR re-rank: its output pair (the scan's stays its input), and lambda [mb] — data,
+        # one fixed-size H2D copy, so one graph serves every value
+        self._d_s2 = torch.empty(mb * self.MAX_K, dtype=torch.float32, device=dev)
+        self._d_p2 = torch.empty(mb * self.MAX_K, dtype=torch.int64, device=dev)
+        self._h_lam = torch.zeros(mb, dtype=torch.float32).pin_memory()
+        self._h_lam_np = self._h_lam.numpy()
+        self._d_lam = torch.zeros(mb, dtype=torch.float32, device=dev)
+        self._mmr_ops = None   # (rows, pos_slot, n_pos) of the index, per generation, made at the first re-ranked call
         # keys (nq, k) without lists — as before lists existed — and (nq, k, True) with
         self._graphs: "OrderedDict[tuple, torch.cuda.CUDAGraph]" = OrderedDict()
         self._generation = -1
@@ -906,21 +1002,51 @@ class OnlineSearcher:
                                    workspace_buf=self._ws, exclude_lists=sources or None,
                                    tag_filter=self._tag_filter(nq) if tags else None)
 
-    def _download(self, nq: int, k: int):
-        """D2H copies of scores and positions into the pinned result buffers."""
-        n = nq * k
-        self._h_s[:n].copy_(self._d_s[:n], non_blocking=True)
-        self._h_p[:n].copy_(self._d_p[:n], non_blocking=True)
+    def _stage_mmr(self, nq: int, lam):
+        """Write lambda (one float, or one per query) into the pinned buffer, and make
+        the index's re-rank operands when this generation has none yet. Under ``lock``,
+        after ``_revalidate``."""
+        lam = np.asarray(lam, dtype=np.float32).reshape(-1)
+        if lam.size not in (1, nq):
+            raise ValueError(f"{lam.size} mmr lambdas for {nq} queries")
+        if not bool(np.all((lam >= 0) & (lam <= 1))):
+            raise ValueError(f"mmr lambda {lam.tolist()}: 0 <= lambda <= 1")
+        self._h_lam_np[:nq] = lam
+        if self._mmr_ops is None:
+            self._mmr_ops = self.index._mmr_operands()
 
-    def _sequence(self, nq: int, k: int, lists: bool = False, tags: bool = False):
-        """The stream-ordered chain of one call, on torch's current stream."""
+    def _device_mmr(self, nq: int, k: int, k_out: int):
+        """``rt_mmr_rerank`` of the device scores / positions ``[nq, k]`` the chain wrote
+        into the second device pair ``[nq, k_out]``, lambda from ``_d_lam``."""
+        n, m = nq * k, nq * k_out
+        rows, pos_slot, n_pos = self._mmr_ops
+        kernels.mmr_rerank(self._d_s[:n].view(nq, k), self._d_p[:n].view(nq, k), rows, k_out, self._d_lam,
+                           pos_slot=pos_slot, n_pos=n_pos, normalize=self.index.metric != "cosine",
+                           out=(self._d_s2[:m].view(nq, k_out), self._d_p2[:m].view(nq, k_out)))
+
+    def _download(self, nq: int, k: int, mmr: bool = False):
+        """D2H copies of scores and positions into the pinned result buffers (``mmr``:
+        of the re-ranked pair)."""
+        n = nq * k
+        self._h_s[:n].copy_((self._d_s2 if mmr else self._d_s)[:n], non_blocking=True)
+        self._h_p[:n].copy_((self._d_p2 if mmr else self._d_p)[:n], non_blocking=True)
+
+    def _sequence(self, nq: int, k: int, lists: bool = False, tags: bool = False, mmr_k: int = 0):
+        """The stream-ordered chain of one call, on torch's current stream (``mmr_k``:
+        then ``rt_mmr_rerank`` of the k candidates into ``mmr_k`` results)."""
         self._upload(nq)
         if lists:
             self._upload_lists()
         if tags:
             self._d_tm.copy_(self._h_tm, non_blocking=True)   # whole buffer: the masks are data
+        if mmr_k:
+            self._d_lam.copy_(self._h_lam, non_blocking=True)   # whole buffer: lambda is data
         self._device_chain(nq, k, [self._list_source()] if lists else None, tags=tags)
-        self._download(nq, k)
+        if mmr_k:
+            self._device_mmr(nq, k, mmr_k)
+            self._download(nq, mmr_k, True)
+        else:
+            self._download(nq, k)
 
     def _graph_key(self, nq: int, k: int, lists: bool) -> tuple:
         """What one captured graph serves (a call with category masks: this key + ("tags",))."""
@@ -940,10 +1066,12 @@ class OnlineSearcher:
                              "searcher was made: obtain a new one (index.online_searcher)")
         self._rows = idx.index[: idx.current_size]
         self._item_tags = idx._tags
+        self._mmr_ops = None
         self._generation = idx._generation
         return True
 
-    def search(self, query_embeddings: Array, k: int, exclude=None, tags=None) -> Tuple[np.ndarray, np.ndarray]:
+    def search(self, query_embeddings: Array, k: int, exclude=None, tags=None, mmr=None
+               ) -> Tuple[np.ndarray, np.ndarray]:
         """(scores [nq, k] f32, positions [nq, k] int64, (-FLT_MAX, -1) padded) as
         numpy views of the searcher's pinned buffers: valid until the next call.
 
@@ -961,7 +1089,20 @@ class OnlineSearcher:
         ``[nq]``; either may be None) over the index's resident tags; the scan
         tests eligibility itself. The masks travel through one more fixed-size
         H2D copy, and one graph per (nq, k, lists, tags) serves every mask value
-        and, the tags being read at replay, every in-place tag change."""
+        and, the tags being read at replay, every in-place tag change.
+
+        ``mmr=(k_out, lam)``: the k results of the scan are candidates, and
+        ``rt_mmr_rerank`` — one more launch at the end of the chain, over the index's
+        stored rows — chooses ``k_out <= k`` of them into a second pre-allocated
+        device pair, which is what is downloaded: the returned views are
+        ``[nq, k_out]``, in selection order, with the original scores. ``lam`` (one
+        float or one per query, in [0, 1]) travels through a pinned ``[max_batch]``
+        buffer and one fixed-size H2D copy; the graph key gains ``("mmr", k_out)`` at
+        its end, so one graph serves every lambda. The position-to-row map: none for
+        a Flat index, the resident ``pos_slot`` of a :class:`HipMutableIVFFlatIndex`
+        (an in-place ``update`` keeps the graph; the replay reads the new row and the
+        new slot), and for a :class:`HipIVFFlatIndex` the inverse of ``row_pos``,
+        made once per generation at the first re-ranked call."""
         idx = self.index
         if idx.index is None:
             raise ValueError("Index not built yet")
@@ -981,20 +1122,29 @@ class OnlineSearcher:
                 raise ValueError(f"exclude holds {len(exclude)} lists for {nq} queries")
             exclude = [_sorted_positions(e, idx.current_size) for e in exclude]
         tagged = tags is not None
+        mmr_k = 0
+        if mmr is not None:
+            mmr_k, lam = int(mmr[0]), mmr[1]
+            if not 1 <= mmr_k <= k:
+                raise ValueError(f"mmr: {mmr_k} results of {k} candidates: 1 <= k_out <= k")
         with self.lock:
             self._revalidate()
             if tagged:
                 self._stage_tags(nq, tags)
+            if mmr_k:
+                self._stage_mmr(nq, lam)
             if lists and not self._stage_lists(nq, exclude):
                 # more entries than the resident buffers hold: the dense bitmap of the default path
                 bits = kernels.exclusion_bitmap(nq, idx.current_size, exclude, self._d_s.device)
                 s, p = idx.search_tensors(t, k, exclude_bits=bits, tag_filter=tags)
+                if mmr_k:
+                    s, p = idx.mmr_rerank_tensors(s, p, mmr_k, self._d_lam.copy_(self._h_lam))
                 return s.cpu().numpy(), p.cpu().numpy()
             self._h_q[:nq].copy_(t)
-            key = self._graph_key(nq, k, lists) + (("tags",) if tagged else ())
+            key = self._graph_key(nq, k, lists) + (("tags",) if tagged else ()) + (("mmr", mmr_k) if mmr_k else ())
             stream = torch.cuda.current_stream(self._d_s.device)
             if os.environ.get("RTREC_ONLINE_GRAPH", "1") == "0":
-                self._sequence(nq, k, lists, tagged)
+                self._sequence(nq, k, lists, tagged, mmr_k)
             else:
                 g = self._graphs.get(key)
                 if g is not None:
@@ -1003,17 +1153,18 @@ class OnlineSearcher:
                     # the first call at this shape: its answer comes from an eager run
                     # (which also loads every kernel), then the chain is captured —
                     # a capture executes nothing, the host buffers keep the answer
-                    self._sequence(nq, k, lists, tagged)
+                    self._sequence(nq, k, lists, tagged, mmr_k)
                     stream.synchronize()
                     g = torch.cuda.CUDAGraph()
                     # thread_local: CUDA work of other threads (an allocation, a default-path
                     # search) during the capture neither enters it nor invalidates it
                     with _capture(g):
-                        self._sequence(nq, k, lists, tagged)
+                        self._sequence(nq, k, lists, tagged, mmr_k)
                     while len(self._graphs) >= self.MAX_GRAPHS:
                         self._graphs.popitem(last=False)
                     self._graphs[key] = g
             stream.synchronize()
+            k = mmr_k or k
             return self._h_s_np[:nq * k].reshape(nq, k), self._h_p_np[:nq * k].reshape(nq, k)
 
 
@@ -1233,13 +1384,23 @@ class HipShardedFlatIPIndex(_HbmIndex):
             return parts_s[0], parts_i[0]
         return torch.cat(parts_s), torch.cat(parts_i)
 
+    _NO_MMR = ("the sharded index does not serve the MMR re-rank (a candidate's row may live on another rank): "
+               "use a single-GPU index (HipFlatIPIndex, HipIVFFlatIndex, HipMutableIVFFlatIndex)")
+
+    def _check_mmr(self):
+        raise ValueError("mmr_lambda: " + self._NO_MMR)
+
     def search(self, query_embeddings: Array, k: int = 10,
-               filter_ids: Optional[List[str]] = None, filter_categories=None, exclude_categories=None
+               filter_ids: Optional[List[str]] = None, filter_categories=None, exclude_categories=None,
+               mmr_lambda: Optional[float] = None, mmr_candidates: Optional[int] = None
                ) -> Tuple[List[List[str]], List[List[float]]]:
         """retrieval.py:141-197 on every rank (collective). Category filters are not
-        served here: ``filter_categories`` / ``exclude_categories`` raise."""
+        served here: ``filter_categories`` / ``exclude_categories`` raise, and so do
+        ``mmr_lambda`` / ``mmr_candidates``."""
         if filter_categories is not None or exclude_categories is not None:
             raise ValueError(self._NO_CATEGORIES)
+        if mmr_lambda is not None or mmr_candidates is not None:
+            raise ValueError(self._NO_MMR)
         if self.shard is None:
             raise ValueError("Index not built yet")
         k_search = min(k * 2, self.current_size) if filter_ids else k
@@ -1602,6 +1763,7 @@ class HipIVFFlatIndex(_HbmIndex):
         order, offsets, counts = self._group(assign)
         self.index = kernels.gather_rows(src, order if src_index is None else src_index[order])
         self.row_pos = order.to(torch.int32)
+        self._inv_row_pos = None   # the re-rank's inverse of row_pos: made again when next needed
         self.list_offsets = offsets
         self.assign = assign
         self.max_list_rows = int(counts.max().item()) if assign.numel() else 0
@@ -1687,8 +1849,22 @@ class HipIVFFlatIndex(_HbmIndex):
         return scan(q32.to(self.storage_dtype), self.index, self.list_offsets, self.row_pos, probes,
                     self.max_list_rows, k, exclude_bits=exclude_bits, **self._scan_operands())
 
+    def _mmr_operands(self):
+        """The lists' rows and the stored row of every position: the inverse of
+        ``row_pos``, one torch scatter per generation, made at the first re-ranked
+        search and dropped with the generation."""
+        if self._flat is not None:
+            return self._flat._mmr_operands()
+        made = getattr(self, "_inv_row_pos", None)
+        if made is None or made[0] != self._generation:
+            inv = torch.full((self.current_size,), -1, dtype=torch.int32, device=self.row_pos.device)
+            inv[self.row_pos.long()] = torch.arange(self.row_pos.numel(), dtype=torch.int32, device=inv.device)
+            made = self._inv_row_pos = (self._generation, inv)
+        return self.index, made[1], self.current_size
+
     def search(self, query_embeddings: Array, k: int = 10, filter_ids: Optional[List[str]] = None,
-               exclude_ids=None, filter_categories=None, exclude_categories=None
+               exclude_ids=None, filter_categories=None, exclude_categories=None,
+               mmr_lambda: Optional[float] = None, mmr_candidates: Optional[int] = None
                ) -> Tuple[List[List[str]], List[List[float]]]:
         """retrieval.py:141-197, as :meth:`HipFlatIPIndex.search`: the 2k over-fetch
         for ``filter_ids``, exact ``exclude_ids`` in the search (over the probed
@@ -1697,8 +1873,14 @@ class HipIVFFlatIndex(_HbmIndex):
         the other calls mask through a bitmap. ``filter_categories`` /
         ``exclude_categories``: as :meth:`HipFlatIPIndex.search`, exact over the
         PROBED lists (k results whenever k eligible rows exist among them), as a
-        filtered Faiss IVF search is — not over the corpus."""
+        filtered Faiss IVF search is — not over the corpus. ``mmr_lambda`` /
+        ``mmr_candidates``: as :meth:`HipFlatIPIndex.search`; the candidates are the
+        top ``mmr_candidates`` of the probed lists, and the re-rank depends on the
+        candidates and their stored values only, so with every list probed the
+        lists are the Flat index's."""
         cats = dict(filter_categories=filter_categories, exclude_categories=exclude_categories)
+        if mmr_lambda is not None or mmr_candidates is not None:
+            cats.update(mmr_lambda=mmr_lambda, mmr_candidates=mmr_candidates)
         if self.index is not None and self._flat is not None:
             return self._flat.search(query_embeddings, k, filter_ids, exclude_ids=exclude_ids, **cats)
         return super().search(query_embeddings, k, filter_ids, exclude_ids=exclude_ids, **cats)
@@ -1856,6 +2038,7 @@ class OnlineIVFSearcher(OnlineSearcher):
         self._item_tags = idx._tags
         self._lists = (idx.list_offsets, idx.row_pos, idx.centroids, idx.max_list_rows)
         self._scan_operands = idx._scan_operands()   # a mutable index: list_len and n_pos, fixed per generation
+        self._mmr_ops = None
         self._generation = idx._generation
         return True
 
@@ -1958,6 +2141,12 @@ class HipMutableIVFFlatIndex(HipIVFFlatIndex):
 
     def _live_assign(self) -> torch.Tensor:
         return self.assign[: self.current_size]
+
+    def _mmr_operands(self):
+        if self._flat is not None:
+            return self._flat._mmr_operands()
+        # the resident pos_slot: an in-place update rewrites rows and slots where they lie
+        return self.index, self.pos_slot, self.current_size
 
     def _regroup(self, src: torch.Tensor, src_index: Optional[torch.Tensor], assign: torch.Tensor):
         """The base class's regroup into lists with slack: position p (``assign[p]``
@@ -2191,16 +2380,23 @@ class RetrievalEngine:
 
     def retrieve(self, query_embeddings: Array, k: Optional[int] = None,
                  filter_ids: Optional[List[str]] = None, use_cache: bool = True, exclude_ids=None,
-                 filter_categories=None, exclude_categories=None
+                 filter_categories=None, exclude_categories=None,
+                 mmr_lambda: Optional[float] = None, mmr_candidates: Optional[int] = None
                  ) -> Tuple[List[List[str]], List[List[float]], Dict[str, Any]]:
         """``exclude_ids``: as ``HipFlatIPIndex.search``; like ``filter_ids`` it keeps
         the call out of the query cache (neither read nor filled), and so do
-        ``filter_categories`` / ``exclude_categories`` (as ``HipFlatIPIndex.search``)."""
+        ``filter_categories`` / ``exclude_categories`` (as ``HipFlatIPIndex.search``)
+        and ``mmr_lambda`` / ``mmr_candidates`` — the ranking stage of the request
+        path (src/serving/service.py:204-228) as an MMR re-rank of the top
+        ``mmr_candidates`` (default ``min(10 * k, 128, index size)``) into k, as
+        ``HipFlatIPIndex.search`` describes it."""
         start = time.time()
         k = k or self.top_k
         cache_key = None
         cats = {key: v for key, v in (("filter_categories", filter_categories),
-                                      ("exclude_categories", exclude_categories)) if v is not None}
+                                      ("exclude_categories", exclude_categories),
+                                      ("mmr_lambda", mmr_lambda), ("mmr_candidates", mmr_candidates))
+                if v is not None}
         if use_cache and filter_ids is None and exclude_ids is None and not cats:
             qb = query_embeddings.detach().cpu().numpy().tobytes() if isinstance(query_embeddings, torch.Tensor) \
                 else np.asarray(query_embeddings).tobytes()

@@ -61,6 +61,14 @@ bar: at nq = 4096, both storages, B's p50 in every round is below the MINIMUM
 of A's p50 over its rounds; the crossover is the smallest measured nq from
 which that holds for both storages. B against C is reported, not barred.
 
+``--legs mmr`` (not in the default list): what the MMR re-rank adds to the resident
+IVF search (tools/mmr_leg.py, as ``tools/serve_latency.py --legs mmr``): nprobe =
+20, nq in {1, 8}, HipIVFFlatIndex and HipMutableIVFFlatIndex. Side ``plain`` is
+``search(q, 100)``, side ``mmr`` the same search plus ``rt_mmr_rerank`` to k = 10 at
+lambda 0.5; alternating call by call, 6 rounds with each side first in turn. p50 /
+p99 per side and round, the added p50, the ratio, and the re-rank launch alone by
+hipEvent pairs. No bar.
+
 Prints one JSON line per case and a closing summary line; run it under a time
 limit, e.g. ``timeout 900 python tools/ivf_latency.py > profiles/ivf_latency.txt``.
 """
@@ -269,6 +277,30 @@ def leg_filter(args, storage, rows, queries, dev):
     return cases
 
 
+def leg_mmr(args, storage, rows, queries, dev):
+    """The MMR re-rank on the resident IVF search path (tools/mmr_leg.py: the sides):
+    nprobe = --exclude-nprobe, side A the plain search of k = --k, side B the same
+    search plus the re-rank to k = 10 at lambda 0.5; the immutable index (the inverse
+    of row_pos) and the mutable one (its resident pos_slot). One JSON line per
+    (index, nq)."""
+    import mmr_leg
+    cases = []
+    for name, cls in (("ivf", HipIVFFlatIndex), ("ivf_mutable", HipMutableIVFFlatIndex)):
+        ivf = cls({"dimension": args.dim, "metric": "cosine", "storage_dtype": storage, "nprobe": args.exclude_nprobe,
+                   "index_factory": f"IVF{args.nlist},Flat", "train_iters": args.train_iters})
+        ivf.build(rows, [])
+        s = ivf.online_searcher(8)
+        for nq in [int(x) for x in args.nq.split(",")]:
+            case = {"leg": "mmr", "index": name, "storage": storage, "nq": nq, "nprobe": args.exclude_nprobe,
+                    **mmr_leg.measure(s, queries, nq, args.k, 10, 0.5, timed_alternating, args.calls, args.warmup)}
+            print(json.dumps(case), flush=True)
+            cases.append({key: case[key] for key in ("index", "storage", "nq", "added_p50_us", "mmr_over_plain_p50",
+                                                     "rerank_event_ms")})
+        del s, ivf
+        torch.cuda.empty_cache()
+    return cases
+
+
 def leg_mutate(args, storage, rows, queries, dev):
     """The mutate leg for one storage dtype: one JSON line per update size and per nq."""
     n, d, k = rows.shape[0], rows.shape[1], args.k
@@ -455,7 +487,7 @@ def main():
     ap.add_argument("--nq", default="1,8")
     ap.add_argument("--chunk-tiles", default="", help="comma list of chunk floors (256-row tiles) for the scan alone")
     ap.add_argument("--train-iters", type=int, default=10)
-    ap.add_argument("--legs", default="search", help="comma list of: search (the default), exclude, mutate, batch, filter")
+    ap.add_argument("--legs", default="search", help="comma list of: search (the default), exclude, mutate, batch, filter, mmr")
     ap.add_argument("--mutate-sizes", default="1,64,1024", help="known rows per update call of the mutate leg")
     ap.add_argument("--mutate-calls", type=int, default=12, help="timed update calls per size (fewer for large sizes)")
     ap.add_argument("--exclude-nprobe", type=int, default=20)
@@ -470,7 +502,7 @@ def main():
     ids = []   # positions only: the id maps are not what is measured
     summary = {"rows": n, "dim": d, "k": k, "nlist": args.nlist, "cases": []}
     legs = args.legs.split(",")
-    if set(legs) - {"search", "exclude", "mutate", "batch", "filter"}:
+    if set(legs) - {"search", "exclude", "mutate", "batch", "filter", "mmr"}:
         raise SystemExit(f"unknown leg in {args.legs!r}")
     if "batch" in legs:
         # the same rows (the generator draws them first) and as many queries as the largest batch
@@ -481,6 +513,11 @@ def main():
             summary.setdefault("batch", []).extend(leg_batch(args, storage, rows, batch_queries, dev))
             torch.cuda.empty_cache()
             if legs == ["batch"]:
+                continue
+        if "mmr" in legs:
+            summary.setdefault("mmr", []).extend(leg_mmr(args, storage, rows, queries, dev))
+            torch.cuda.empty_cache()
+            if legs == ["mmr"]:
                 continue
         if "filter" in legs:
             summary.setdefault("filter", []).extend(leg_filter(args, storage, rows, queries, dev))

@@ -56,6 +56,15 @@ Legs
                 sides return different ids (``sides_agree`` also records whether their
                 scores are equal; the bitmap side runs the batch kernel).
 
+  mmr           (not in the default list) the MMR re-rank on the resident search
+                (tools/mmr_leg.py): N = --rows, d = 128, float16 and float32, nq in
+                {1, 8}. Side ``plain`` is ``OnlineSearcher.search(q, 100)``, side
+                ``mmr`` the same search plus ``rt_mmr_rerank`` to k = 10 at lambda
+                0.5 (``search(q, 100, mmr=(10, 0.5))``); they alternate call by call,
+                6 rounds with each side first in turn. Reported: p50 / p99 per side
+                and round, the added p50 and the ratio, and the re-rank launch alone
+                by hipEvent pairs. No bar.
+
 The first two legs are timed with ``online_max_batch`` off and on, alternating
 call by call in one process (two indexes over the same rows, so neither finds
 its corpus in the Infinity Cache). The ``on`` side of serve_q1_ref and the
@@ -615,6 +624,27 @@ def leg_filter(args):
     return out
 
 
+def leg_mmr(args):
+    """The MMR re-rank on the resident Flat search path (tools/mmr_leg.py: the sides):
+    N = --rows, d = 128, float16 and float32 rows, nq = 1 and 8; side A the plain
+    search of k = 100, side B the same search plus the re-rank to k = 10, lambda 0.5."""
+    import mmr_leg
+    n, d = args.rows, 128
+    out = {}
+    qs = np.random.default_rng(3).standard_normal((64, d)).astype(np.float32)
+    for storage in ("float16", "float32"):
+        g = torch.Generator(device="cuda").manual_seed(1)
+        ix = HipFlatIPIndex({"dimension": d, "metric": "cosine", "storage_dtype": storage})
+        ix.build(torch.randn((n, d), generator=g, device="cuda"), [])
+        s = ix.online_searcher(8)
+        for nq in (1, 8):
+            out[f"{storage}_nq{nq}"] = mmr_leg.measure(s, qs, nq, 100, 10, 0.5, timed_alternating, args.calls,
+                                                       args.warmup)
+        del s, ix
+        torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--baseline", action="store_true", help="only the API of the commit before the online path")
@@ -634,7 +664,7 @@ def main():
            "lib": os.environ.get("RTREC_HIP_LIB", "in-tree"), "device": torch.cuda.get_device_name(0)}
     legs = {"serve_q1_ref": leg_serve_q1_ref, "corpus_1m": leg_corpus_1m, "embed_b1": leg_embed_b1,
             "serve_e2e": leg_serve_e2e, "tower_kernel": leg_tower_kernel, "mutate": leg_mutate,
-            "exclude": leg_exclude, "filter": leg_filter}
+            "exclude": leg_exclude, "filter": leg_filter, "mmr": leg_mmr}
     for name in args.legs.split(","):
         if name not in legs:
             ap.error(f"unknown leg {name!r}")
