@@ -324,6 +324,69 @@ int rt_segment_mean_f32(const void* rows, int64_t n, int d, int dtype, const int
                         const float* prev, int normalize, float* out, void* stream);
 
 /* ------------------------------------------------------------------------
+ * IVF-PQ (faiss.index_factory(d, "IVF1024,PQ16"): the factory string of
+ * src/serving/retrieval.py:96-110 with product-quantised lists). A stored row
+ * is M bytes: code m names one of the 256 codewords of subspace m, the
+ * elements [m dsub, (m + 1) dsub) of a row, dsub = d / M.
+ * Limits of both entry points: M % 4 == 0, 4 <= M <= RT_PQ_MAX_M; d % M == 0;
+ * dsub % 2 == 0, dsub <= 32 (d = 128 takes M up to 64); 8 bits per code.
+ *
+ * rt_pq_encode: codes[i][m] (uint8 [n, M]) = the codeword of subspace m
+ *   nearest to row i. rows [n, d] of `dtype` (the d / dtype limits of
+ *   rt_ivf_topk, 16-byte aligned); codebooks fp32 [M][256][dsub] (16-byte
+ *   aligned). centroids (fp32 [nlist, d], 16-byte aligned) and assign (int64
+ *   [n]) come together or are both NULL: with them the kernel encodes the
+ *   residual r = to_f32(x) - centroid[assign[i]] (one fp32 subtraction per
+ *   element), without them — or for a row whose assign is outside [0, nlist)
+ *   — the widened row itself. code = argmin over c of sum_j (r[m dsub + j] -
+ *   cb[m][c][j])^2, the sum a sequential fp32 fmaf chain over j ascending from
+ *   0, the lowest c winning ties. One launch, stream-ordered.
+ *   Status, before any device work: RT_ERR_INVALID for a NULL rows /
+ *   codebooks / codes (n > 0), centroids without assign or the reverse,
+ *   centroids with nlist <= 0, n < 0, d <= 0, M <= 0, an unknown dtype, a
+ *   misaligned rows / codebooks / centroids; RT_ERR_UNSUPPORTED for M or d
+ *   outside the limits above or a refused d / dtype pair. n == 0: RT_OK.
+ * rt_ivf_pq_topk: rt_ivf_topk over lists of codes, by asymmetric distance
+ *   computation: the query stays exact, a row's score is
+ *     bias[q][p] + sum_m lut[q][m][code_m],  m ascending, fp32,
+ *   with lut[q][m][c] = sum_j queries[q][m dsub + j] cb[m][c][j] (a sequential
+ *   fmaf chain over j ascending from 0) and p the entry of the query's probe
+ *   row that names the row's list. bias (fp32 [nq, nprobe], device; NULL = 0):
+ *   for codes of residuals the query's inner product with the list's centroid
+ *   — what the coarse search over the centroids returns as scores — so that
+ *   the score approximates q.x; the tables depend on the query only.
+ *   queries fp32 [nq, d] (d % 4 == 0, d <= 256, 16-byte aligned); codes uint8
+ *   [nx, M], stored list-contiguous, 16-byte aligned; list_offsets, nlist,
+ *   row_pos, probes, max_list_rows, exclude_bits / exclude_words, k, nprobe,
+ *   nq and nx: as rt_ivf_topk, the same window clamping (a probe of -1 or
+ *   outside [0, nlist) is skipped, nothing outside the list or the corpus is
+ *   read, a row whose row_pos is outside [0, nx) is dropped), the same grid
+ *   (rt_ivf_topk_plan) and the same result contract: the first k in (score
+ *   desc, original position asc) order, out_ids = original position, unfilled
+ *   slots (-FLT_MAX, -1). Three launches (tables, scan, finish), no host read,
+ *   stream-ordered, capturable.
+ *   Status, before any device work: RT_ERR_INVALID for a NULL operand (codes /
+ *   row_pos may be NULL when nx == 0; bias and exclude_bits are optional),
+ *   k <= 0, nprobe <= 0, nlist <= 0, d <= 0, M <= 0, a negative size,
+ *   misaligned queries / codebooks / codes / workspace (16 bytes), exclude_words
+ *   too small; RT_ERR_UNSUPPORTED for M or d outside the limits, k >
+ *   RT_IVF_MAX_K, nprobe > RT_IVF_MAX_NPROBE, nq > 65,535, nx >= 2^31 - 1;
+ *   RT_ERR_WORKSPACE. nq == 0: RT_OK.
+ * rt_ivf_pq_topk_workspace_bytes: rt_ivf_topk's partial lists rounded up to
+ *   256 bytes, then the tables, 1,024 nq M bytes (256 for nq <= 0 or a refused
+ *   M); monotone in nq and in M.
+ * ------------------------------------------------------------------------ */
+#define RT_PQ_MAX_M 64
+int rt_pq_encode(const void* rows, int64_t n, int d, int dtype, const float* centroids, int64_t nlist,
+                 const int64_t* assign, const float* codebooks, int M, uint8_t* codes, void* stream);
+size_t rt_ivf_pq_topk_workspace_bytes(int64_t nq, int nprobe, int64_t max_list_rows, int k, int M);
+int rt_ivf_pq_topk(const float* queries, int64_t nq, int d, const uint8_t* codes, int64_t nx, int M,
+                   const float* codebooks, const int64_t* list_offsets, int64_t nlist, const int32_t* row_pos,
+                   const int64_t* probes, const float* bias, int nprobe, int64_t max_list_rows, int k,
+                   const uint32_t* exclude_bits, int64_t exclude_words, float* out_scores, int64_t* out_ids,
+                   void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * IVF-Flat, list-major batch search: faiss.IndexIVFFlat.search with a batch
  * of users (src/serving/retrieval.py:141-197 at Q in the thousands, and the
  * offline evaluation), where rt_ivf_topk reads a list again for every (query,

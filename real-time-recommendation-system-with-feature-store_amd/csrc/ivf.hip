@@ -51,52 +51,11 @@
 // the largest CAPACITY, a host argument, so a captured call sees lists that
 // changed in place. The other two entry points pass list_len = nullptr and
 // n_pos = nx: the window and the range test they had.
-#include "topk_online.h"
+#include "ivf_select.h"
 
 namespace rt {
 namespace topk {
 namespace ivf {
-
-namespace on = rt::topk::online;
-
-constexpr int kMaxProbe = 128;                // RT_IVF_MAX_NPROBE
-constexpr int kMaxLists = on::kMaxBlocks;     // partial lists per query the finish takes (one thread each)
-constexpr int64_t kMaxNq = 65535;             // grid.y
-static_assert(kMaxProbe <= kMaxLists, "ivf: one partial list per probe at least");
-
-struct Plan {
-    int chunks;              // per probed list
-    int64_t rows_per_chunk;  // a multiple of the scan's 256-row tile
-};
-
-// Smallest chunks (>= min_tiles tiles) that keep nprobe x chunks within the
-// finish's 512 lists: at nq = 1 the blocks of a call are all the parallelism
-// there is (20 probes of ~1,000 rows = 80 blocks of one tile, not 20).
-inline Plan make_plan(int nprobe, int64_t max_list_rows, int min_tiles) {
-    const int64_t tile = on::kTileRows;
-    const int64_t mlr = max_list_rows > 0 ? max_list_rows : 1;
-    const int64_t cap = kMaxLists / (nprobe > 0 ? nprobe : 1);  // >= 4
-    int64_t tiles = (mlr + tile - 1) / tile;
-    int64_t tpc = (tiles + cap - 1) / cap;  // tiles per chunk
-    if (tpc < min_tiles) tpc = min_tiles;
-    Plan p;
-    p.rows_per_chunk = tpc * tile;
-    p.chunks = static_cast<int>((mlr + p.rows_per_chunk - 1) / p.rows_per_chunk);
-    return p;
-}
-
-// wave: compact one candidate buffer; thr = the lowest score kept
-__device__ __forceinline__ void compact_keep_ties(Cand* buf, int& n, int k, int limit, uint32_t* hist, float& thr) {
-    const int lane = threadIdx.x & 63;
-    float unused = 0.f;
-    v4::compact_stream(buf, n, k, limit, hist, unused);
-    wave_lds_sync();
-    float lo = INFINITY;
-    for (int i = lane; i < n; i += 64) lo = fminf(lo, buf[i].s);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) lo = fminf(lo, __shfl_xor(lo, o, 64));
-    thr = lo;
-}
 
 // ---- exclusion lists (the LISTS instantiation) ----
 // The staged lists take what two blocks per CU leave of the LDS next to the
@@ -153,26 +112,10 @@ __global__ __launch_bounds__(on::kThreads, 2) void ivf_scan(
     // the chunk, clamped to the list and to the corpus
     on::RowWindow w;
     w.X = X;
-    w.row_begin = w.row_end = 0;
-    const int64_t l = probes[static_cast<int64_t>(q) * nprobe + p];
-    if (l >= 0 && l < nlist) {
-        int64_t lo = list_offsets[l], hi = list_offsets[l + 1];
-        lo = lo < 0 ? 0 : lo;
-        hi = hi > nx ? nx : hi;
-        if (list_len && lo < hi) {  // lists with slack: the first list_len[l] rows of the capacity
-            const int64_t live = list_len[l];
-            hi = live <= 0 ? lo : (live < hi - lo ? lo + live : hi);
-        }
-        if (lo < hi) {
-            const int64_t len = hi - lo, first = static_cast<int64_t>(c) * rows_per_chunk;
-            if (first < len) {
-                w.row_begin = lo + first;
-                w.row_end = (first + rows_per_chunk) < len ? (w.row_begin + rows_per_chunk) : hi;
-            }
-        }
-    }
+    chunk_window(probes[static_cast<int64_t>(q) * nprobe + p], c, list_offsets, nlist, list_len, nx, rows_per_chunk,
+                 w.row_begin, w.row_end);
     if (w.row_end <= w.row_begin) {  // block-uniform
-        for (int r = threadIdx.x; r < k; r += kThreads) out[static_cast<int64_t>(r) * lists] = 0ull;
+        write_none(out, k, lists);
         return;
     }
 
@@ -271,9 +214,7 @@ __global__ __launch_bounds__(on::kThreads, 2) void ivf_scan(
         on::score_tile<T, 1>(R, w, t, stage, qs, d, acc);
 
         // ---- selection: at most one append per row ----
-        // a position outside [0, n_pos) (a corrupt row_pos, an empty slot of a list with
-        // slack) is dropped: it has no bit in the bitmap and no row in the caller's corpus
-        bool pass = pos >= 0 && static_cast<int64_t>(pos) < n_pos && acc[0] >= th;
+        bool pass = pos_passes(pos, n_pos, acc[0], th);
         if constexpr (TAGS) pass = pass && on::tag_eligible(tg, any_of, none_of);
         if constexpr (LISTS) {
             if (__any(pass)) {  // wave-uniform
@@ -285,7 +226,7 @@ __global__ __launch_bounds__(on::kThreads, 2) void ivf_scan(
                 }
             }
         } else if (excl && pass)
-            pass = ((excl[static_cast<int64_t>(q) * excl_words + (pos >> 5)] >> (pos & 31)) & 1u) == 0u;
+            pass = bitmap_clear(excl, excl_words, q, pos);
         over = __syncthreads_or(on::append<true>(pass, &cnt, cand, acc[0], static_cast<uint32_t>(pos)));
     }
 

@@ -795,6 +795,124 @@ def ivf_topk(queries: torch.Tensor, rows: torch.Tensor, list_offsets: torch.Tens
     return scores, ids
 
 
+# ---------------------------------------------------------------------------
+# IVF-PQ (faiss "IVF<nlist>,PQ<M>": product-quantised lists, include/rtrec_hip.h)
+# ---------------------------------------------------------------------------
+
+PQ_MAX_M = 64   # RT_PQ_MAX_M
+# Lookup tables one rt_ivf_pq_topk call may hold (1 KB per query and subspace): a
+# block reads its query's table once per (probe, chunk), so a chunk's tables
+# should stay in the 256 MB Infinity Cache next to the codes and partial lists —
+# a quarter of it: 4,096 queries at M = 16, 1,024 at M = 64. A policy default,
+# not a measured one.
+IVF_PQ_TABLE_BUDGET = 64 << 20
+
+
+def _pq_shape(d: int, M: int, what: str) -> int:
+    """dsub of a served (d, M) pair; raises otherwise."""
+    if not (4 <= M <= PQ_MAX_M and M % 4 == 0 and d % M == 0 and (d // M) % 2 == 0 and d // M <= 32):
+        raise ValueError(f"{what}: M={M}, d={d} — served: M % 4 == 0, 4 <= M <= {PQ_MAX_M}, d % M == 0, "
+                         "d / M even, d / M <= 32")
+    return d // M
+
+
+def pq_encode(rows: torch.Tensor, codebooks: torch.Tensor, centroids: Optional[torch.Tensor] = None,
+              assign: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 codes ``[n, M]`` of ``rows`` [n, d] (fp32 / f16 / bf16) against
+    ``codebooks`` fp32 ``[M, 256, d / M]`` (rt_pq_encode): per subspace the nearest
+    codeword by squared distance, a sequential fp32 fmaf chain, the lowest
+    codeword winning ties. With ``centroids`` (fp32 [nlist, d]) and ``assign``
+    (int64 [n]) the residual ``row - centroids[assign]`` is encoded (a row whose
+    ``assign`` is outside [0, nlist): the row itself)."""
+    native.require_device(rows, codebooks, centroids, assign, out, what="pq_encode")
+    if rows.dim() != 2 or not rows.is_contiguous():
+        raise ValueError("pq_encode expects contiguous [n, d] rows")
+    n, d = rows.shape
+    if codebooks.dtype != torch.float32 or codebooks.dim() != 3 or not codebooks.is_contiguous():
+        raise ValueError("codebooks must be contiguous fp32 [M, 256, d / M]")
+    M = codebooks.shape[0]
+    dsub = _pq_shape(d, M, "pq_encode")
+    if tuple(codebooks.shape) != (M, 256, dsub):
+        raise ValueError(f"codebooks must be [{M}, 256, {dsub}], got {tuple(codebooks.shape)}")
+    if (centroids is None) != (assign is None):
+        raise ValueError("centroids and assign come together")
+    nlist = 0
+    if centroids is not None:
+        if centroids.dtype != torch.float32 or centroids.dim() != 2 or centroids.shape[1] != d \
+                or not centroids.is_contiguous() or centroids.shape[0] < 1:
+            raise ValueError(f"centroids must be contiguous fp32 [nlist, {d}]")
+        if assign.dtype != torch.int64 or assign.numel() != n or not assign.is_contiguous():
+            raise ValueError("assign must be contiguous int64 [n]")
+        nlist = centroids.shape[0]
+    if out is None:
+        out = torch.empty((n, M), dtype=torch.uint8, device=rows.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (n, M) or not out.is_contiguous():
+        raise ValueError(f"out must be contiguous uint8 [{n}, {M}]")
+    call("rt_pq_encode", ptr(rows) if n else None, n, d, native.dtype_code(rows.dtype), ptr(centroids), nlist,
+         ptr(assign), ptr(codebooks), M, ptr(out) if n else None, stream_of(rows))
+    return out
+
+
+def ivf_pq_topk(queries: torch.Tensor, codes: torch.Tensor, codebooks: torch.Tensor, list_offsets: torch.Tensor,
+                row_pos: torch.Tensor, probes: torch.Tensor, max_list_rows: int, k: int,
+                bias: Optional[torch.Tensor] = None, exclude_bits: Optional[torch.Tensor] = None,
+                out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                workspace_buf: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Top-k over the probed lists of a product-quantised corpus (rt_ivf_pq_topk):
+    the operands and the result contract of :func:`ivf_topk` with the rows
+    replaced by ``codes`` uint8 [nx, M] (list-contiguous) and ``codebooks`` fp32
+    [M, 256, d / M]; ``queries`` fp32 [nq, d]. A row's score is ``bias[q, p]``
+    (fp32 [nq, nprobe], None = 0: for residual codes the coarse search's scores)
+    plus the sum over m of the query's lookup table at the row's code.
+    Batches run in chunks of ``IVF_PQ_TABLE_BUDGET / (1 KB x M)`` queries, which
+    bounds the tables in the workspace."""
+    native.require_device(queries, codes, codebooks, list_offsets, row_pos, probes, bias, exclude_bits,
+                          what="ivf_pq_topk")
+    if queries.dim() != 2 or queries.dtype != torch.float32:
+        raise ValueError("ivf_pq_topk expects fp32 [nq, d] queries")
+    if codes.dim() != 2 or codes.dtype != torch.uint8:
+        raise ValueError("codes must be uint8 [nx, M]")
+    nq, d = queries.shape
+    nx, M = codes.shape
+    dsub = _pq_shape(d, M, "ivf_pq_topk")
+    if codebooks.dtype != torch.float32 or tuple(codebooks.shape) != (M, 256, dsub):
+        raise ValueError(f"codebooks must be fp32 [{M}, 256, {dsub}]")
+    if not 1 <= k <= IVF_MAX_K:
+        raise ValueError(f"k={k}: ivf_pq_topk returns 1..{IVF_MAX_K} results per query")
+    if not (queries.is_contiguous() and codes.is_contiguous() and codebooks.is_contiguous()
+            and probes.is_contiguous() and list_offsets.is_contiguous() and row_pos.is_contiguous()):
+        raise ValueError("ivf_pq_topk expects contiguous operands")
+    if list_offsets.dtype != torch.int64 or list_offsets.dim() != 1 or list_offsets.numel() < 2:
+        raise ValueError("list_offsets must be int64 [nlist + 1]")
+    if row_pos.dtype != torch.int32 or row_pos.numel() != nx:
+        raise ValueError("row_pos must be int32 [nx]")
+    if probes.dtype != torch.int64 or probes.dim() != 2 or probes.shape[0] != nq:
+        raise ValueError("probes must be int64 [nq, nprobe]")
+    nprobe = probes.shape[1]
+    if not 1 <= nprobe <= IVF_MAX_NPROBE:
+        raise ValueError(f"nprobe={nprobe}: 1..{IVF_MAX_NPROBE}")
+    if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (nq, nprobe)
+                             or not bias.is_contiguous()):
+        raise ValueError(f"bias must be contiguous fp32 [{nq}, {nprobe}]")
+    nlist = list_offsets.numel() - 1
+    scores, ids = _topk_out(out, nq, k, queries.device)
+    words = _exclude_words(exclude_bits, nq, True)
+    step = max(1, min(IVF_QUERY_CHUNK, IVF_PQ_TABLE_BUDGET // (1024 * M)))
+    for a in range(0, nq, step):
+        b = min(nq, a + step)
+        ws = workspace_buf
+        if ws is None:
+            ws = workspace(queries.device,
+                           native.lib().rt_ivf_pq_topk_workspace_bytes(b - a, nprobe, int(max_list_rows), k, M),
+                           "ivf_pq_topk")
+        call("rt_ivf_pq_topk", ptr(queries[a:b]), b - a, d, ptr(codes) if nx else None, nx, M, ptr(codebooks),
+             ptr(list_offsets), nlist, ptr(row_pos) if nx else None, ptr(probes[a:b]),
+             ptr(bias[a:b]) if bias is not None else None, nprobe, int(max_list_rows), k,
+             ptr(exclude_bits[a:b]) if exclude_bits is not None else None, words, ptr(scores[a:b]), ptr(ids[a:b]),
+             ptr(ws), ws.numel(), stream_of(queries))
+    return scores, ids
+
+
 # Workspace one rt_ivf_topk_batch call may take; larger batches run in query
 # chunks. A policy default (the partial lists of a chunk stay inside the 256 MB
 # Infinity Cache), not a measured one.

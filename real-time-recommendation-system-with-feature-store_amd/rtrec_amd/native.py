@@ -158,6 +158,10 @@ SIGNATURES = {
     "rt_ivf_topk_batch": (c_int, [vp, c_i64, vp, c_i64, c_int, c_int, vp, c_i64, vp, c_i64, vp, vp, c_int, c_i64,
                                   c_int, vp, c_i64, vp, vp, vp, c_size, vp]),
     "rt_segment_mean_f32": (c_int, [vp, c_i64, c_int, c_int, vp, c_i64, vp, c_int, vp, vp]),
+    "rt_pq_encode": (c_int, [vp, c_i64, c_int, c_int, vp, c_i64, vp, vp, c_int, vp, vp]),
+    "rt_ivf_pq_topk_workspace_bytes": (c_size, [c_i64, c_int, c_i64, c_int, c_int]),
+    "rt_ivf_pq_topk": (c_int, [vp, c_i64, c_int, vp, c_i64, c_int, vp, vp, c_i64, vp, vp, vp, c_int, c_i64, c_int,
+                               vp, c_i64, vp, vp, vp, c_size, vp]),
     "rt_ivf_lists_update_workspace_bytes": (c_size, [c_i64, c_i64]),
     "rt_ivf_lists_update": (c_int, [vp, c_i64, c_int, c_int, vp, c_i64, vp, vp, vp, vp, vp, vp, vp, c_i64, vp, vp,
                                     c_size, vp]),

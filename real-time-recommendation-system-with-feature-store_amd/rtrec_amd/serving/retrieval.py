@@ -1667,6 +1667,11 @@ class HipIVFFlatIndex(_HbmIndex):
 
     _searcher_takes_exclude = True   # OnlineIVFSearcher: rt_ivf_topk_lists
     _lists_mutable = False           # HipMutableIVFFlatIndex: lists with slack, changed in place
+    _default_factory = _IVF_FACTORY
+
+    def _parse_factory(self, factory: str) -> int:
+        """nlist of the factory string (a subclass with its own grammar keeps the rest)."""
+        return _parse_ivf_factory(factory)
 
     def __init__(self, config: Optional[Dict[str, Any]] = None):
         super().__init__(dict(config or {}))
@@ -1675,8 +1680,8 @@ class HipIVFFlatIndex(_HbmIndex):
                              "HipMutableIVFFlatIndex (index type 'hip_ivf_mutable') updates, adds and removes "
                              "in place (for a Flat index: HipFlatIPIndex with mutable=True)")
         self.mutable = self._lists_mutable
-        self.index_factory = self.config.get("index_factory", _IVF_FACTORY)
-        self.nlist = _parse_ivf_factory(self.index_factory)
+        self.index_factory = self.config.get("index_factory", self._default_factory)
+        self.nlist = self._parse_factory(self.index_factory)
         self.nprobe = int(self.config.get("nprobe", 20))
         self.train_iters = int(self.config.get("train_iters", 10))
         self.max_points_per_centroid = int(self.config.get("max_points_per_centroid", 256))
@@ -1729,12 +1734,14 @@ class HipIVFFlatIndex(_HbmIndex):
             out[a:a + _ASSIGN_CHUNK] = ids.view(-1)
         return out
 
-    def _group(self, assign: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    def _group(self, assign: torch.Tensor, n_seg: Optional[int] = None
+               ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """(order, offsets, counts): the stable sort of the assignments (original order
-        kept within a list) and the lists' CSR offsets."""
+        kept within a list) and the lists' CSR offsets; ``n_seg`` segments (None: nlist)."""
+        n_seg = self.nlist if n_seg is None else n_seg
         order = torch.sort(assign, stable=True).indices
-        counts = torch.bincount(assign, minlength=self.nlist)
-        offsets = torch.zeros(self.nlist + 1, dtype=torch.int64, device=assign.device)
+        counts = torch.bincount(assign, minlength=n_seg)
+        offsets = torch.zeros(n_seg + 1, dtype=torch.int64, device=assign.device)
         offsets[1:] = torch.cumsum(counts, 0)
         return order, offsets, counts
 
@@ -2330,12 +2337,283 @@ class HipMutableIVFFlatIndex(HipIVFFlatIndex):
         return kernels.gather_rows(self.index, self.pos_slot[: self.current_size].long()).float().cpu().numpy()
 
 
+_IVF_PQ_FACTORY = "IVF1024,PQ16"
+
+
+def _parse_ivf_pq_factory(factory: str) -> Tuple[int, int]:
+    """``"IVF<nlist>,PQ<M>"`` or ``"IVF<nlist>,PQ<M>x8"`` -> (nlist, M); anything else raises."""
+    s = str(factory)
+    head, _, tail = s.partition(",")
+    m, x, bits = tail[2:].partition("x")
+    ok = head.startswith("IVF") and head[3:].isdigit() and int(head[3:]) >= 1 and tail.startswith("PQ") \
+        and m.isdigit() and (not x or bits == "8")
+    if not ok:
+        raise ValueError(f"index_factory {factory!r}: HipIVFPQIndex serves 'IVF<nlist>,PQ<M>' and "
+                         "'IVF<nlist>,PQ<M>x8' (8 bits per code, 256 codewords per subspace; "
+                         "'IVF<nlist>,Flat': HipIVFFlatIndex)")
+    return int(head[3:]), int(m)
+
+
+class HipIVFPQIndex(HipIVFFlatIndex):
+    """IVF index with product-quantised lists resident in HBM:
+    ``faiss.index_factory(d, "IVF1024,PQ16")`` (the reference hands its
+    ``index_factory`` string to Faiss, retrieval.py:96-110). A row is stored as M
+    bytes instead of 2-4 d: code m names one of the 256 codewords of subspace m
+    (``d / M`` elements). No full row is kept.
+
+    ``build``: the parent's preparation, coarse training and assignment; then the
+    M codebooks are trained by ``pq_train_iters`` Lloyd steps over the residuals
+    ``row - centroid`` (``by_residual``, Faiss's default; False: the rows) of a
+    seeded subsample of at most ``256 x max_points_per_centroid`` rows in ascending
+    position order — one step is one ``rt_pq_encode`` over the sample for all
+    subspaces, then per subspace the grouping, ``rt_gather_rows`` and
+    ``rt_segment_mean_f32`` of the coarse training; a codebook starts from the
+    sub-vectors at the first 256 entries of the same permutation, an empty
+    codeword keeps its value — and every row is encoded (``rt_pq_encode``) and
+    stored list-contiguous. Deterministic: the same data and ``seed`` give the
+    same index, bit for bit.
+
+    ``search``: the coarse search, then ``rt_ivf_pq_topk`` over the probed lists —
+    asymmetric distance computation: per-query lookup tables ``q_m . codeword``, a
+    row's score is the sum of M table entries plus, for residual codes, the
+    coarse score ``q . centroid`` of its list (``q . x ~ q . c + sum_m q_m . cb[m]
+    [code_m]``: the tables do not depend on the list). Results keep the parent's
+    contract — (score desc, original position asc), -1 pads — with approximate
+    scores. ``exclude_ids``, ``filter_ids`` and the category filters work as on the
+    parent, through the bitmap route.
+
+    Config keys: the parent's ``dimension``, ``metric``, ``nprobe``,
+    ``train_iters``, ``seed``, ``max_points_per_centroid``, ``device``,
+    ``categories``; ``index_factory`` (``"IVF<nlist>,PQ<M>"`` or ``"...PQ<M>x8"``,
+    default ``"IVF1024,PQ16"``; M % 4 == 0, 4 <= M <= 64, d % M == 0, d / M a
+    multiple of 4 up to 32 — the kernels take any even d / M, the training's
+    ``rt_segment_mean_f32`` whole 16-byte units); ``by_residual`` (True); ``pq_train_iters`` (25, Faiss's
+    ``ClusteringParameters.niter``). ``storage_dtype`` only reaches the Flat
+    fallback (below 1,024 items or nlist, as on the parent).
+
+    Not served here — each raises and names the class that has it: the MMR re-rank
+    (it needs stored rows), ``online_max_batch`` / ``online_searcher`` with their
+    exclusion lists and in-scan tag filter, and ``batch_min_queries``
+    (:class:`HipIVFFlatIndex`); ``update`` / ``remove`` / ``mutable``
+    (:class:`HipMutableIVFFlatIndex`).
+
+    ``vectors()`` returns the RECONSTRUCTION ``centroid + codewords`` (the
+    codewords alone without ``by_residual``), not the rows that were added; ``save``
+    writes ``<path>.ivfpq.npz`` (codes in original order, codebooks, centroids,
+    assignments) and ``<path>.pkl``, and a loaded index answers bit-identically."""
+
+    _searcher_takes_exclude = False
+    _default_factory = _IVF_PQ_FACTORY
+
+    def __init__(self, config: Optional[Dict[str, Any]] = None):
+        cfg = dict(config or {})
+        if cfg.get("online_max_batch"):
+            raise ValueError("HipIVFPQIndex has no resident searcher (online_max_batch): HipIVFFlatIndex has")
+        if cfg.get("batch_min_queries") is not None:
+            raise ValueError("HipIVFPQIndex has no list-major batch scan (batch_min_queries): HipIVFFlatIndex has")
+        super().__init__(cfg)
+        if kernels._pq_shape(self.dimension, self.pq_m, f"index_factory {self.index_factory!r}") % 4:
+            raise ValueError(f"index_factory {self.index_factory!r}: the codebook training takes sub-vectors of a "
+                             f"multiple of 4 elements (rt_segment_mean_f32), d / M = {self.dimension // self.pq_m}")
+        self.by_residual = bool(self.config.get("by_residual", True))
+        self.pq_train_iters = int(self.config.get("pq_train_iters", 25))
+        self.codebooks: Optional[torch.Tensor] = None   # [M, 256, d / M] fp32
+
+    def _parse_factory(self, factory: str) -> int:
+        nlist, self.pq_m = _parse_ivf_pq_factory(factory)
+        return nlist
+
+    @property
+    def codes(self) -> Optional[torch.Tensor]:
+        """uint8 [n, M], list-contiguous (``index`` of this class)."""
+        return None if self._flat is not None else self.index
+
+    def _check_mmr(self):
+        raise ValueError("mmr_lambda: the MMR re-rank reads stored rows, and HipIVFPQIndex keeps codes only; "
+                         "HipIVFFlatIndex serves it")
+
+    def online_searcher(self, max_batch: int = 8, max_exclude: int = 8192) -> "OnlineSearcher":
+        raise ValueError("HipIVFPQIndex has no resident searcher; HipIVFFlatIndex.online_searcher has")
+
+    def update(self, embeddings: Array, ids: List[str], item_categories=None):
+        raise NotImplementedError("HipIVFPQIndex does not update in place; HipMutableIVFFlatIndex does")
+
+    def remove(self, ids: List[str]):
+        raise NotImplementedError("HipIVFPQIndex does not remove; HipMutableIVFFlatIndex does")
+
+    # -- product quantiser -------------------------------------------------
+    def _train_pq(self, rows: torch.Tensor, assign: torch.Tensor) -> torch.Tensor:
+        """The codebooks [M, 256, dsub] from the (residuals of the) training subsample."""
+        n, M = rows.shape[0], self.pq_m
+        dsub = self.dimension // M
+        dev = rows.device
+        perm = torch.randperm(n, generator=torch.Generator().manual_seed(self.seed))
+        n_train = min(n, 256 * self.max_points_per_centroid)
+
+        def sample(pos: torch.Tensor) -> torch.Tensor:
+            x = kernels.gather_rows(rows, pos)
+            return x - self.centroids[assign[pos]] if self.by_residual else x
+
+        codebooks = sample(perm[:256].to(dev)).view(256, M, dsub).permute(1, 0, 2).contiguous()
+        train = sample(torch.sort(perm[:n_train]).values.to(dev))
+        subs = [train[:, m * dsub:(m + 1) * dsub].contiguous() for m in range(M)]
+        for _ in range(self.pq_train_iters):
+            codes = kernels.pq_encode(train, codebooks)
+            for m in range(M):
+                order, offsets, _ = self._group(codes[:, m].long(), 256)
+                kernels.segment_mean(kernels.gather_rows(subs[m], order), offsets, codebooks[m].clone(),
+                                     out=codebooks[m])
+        return codebooks
+
+    def _encode(self, rows: torch.Tensor, assign: torch.Tensor) -> torch.Tensor:
+        if self.by_residual:
+            return kernels.pq_encode(rows, self.codebooks, self.centroids, assign)
+        return kernels.pq_encode(rows, self.codebooks)
+
+    # -- IndexBase ---------------------------------------------------------
+    def build(self, embeddings: Array, ids: List[str], item_categories=None):
+        """As :meth:`HipIVFFlatIndex.build`, then the codebooks and the codes."""
+        n = len(embeddings)
+        if n < IVF_MIN_ITEMS or n < self.nlist:
+            self.codebooks = None
+            return super().build(embeddings, ids, item_categories=item_categories)   # the Flat fallback
+        start = time.time()
+        tags = self._item_tags(item_categories, n)
+        self._flat = None
+        rows = self._prepare(embeddings)
+        self.centroids = self._train(rows)
+        assign = self._assign_rows(rows, self.centroids)
+        self.codebooks = self._train_pq(rows, assign)
+        self._regroup(self._encode(rows, assign), None, assign)
+        self._tags = None
+        self._tags_store(0, tags)
+        self._reset_ids()
+        self._record_ids(0, ids, max(n, len(ids)))
+        self._generation += 1
+        logger.info("Index built in %.2f seconds", time.time() - start)
+
+    def coarse_search(self, q32: torch.Tensor, nprobe: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(scores, lists) [nq, nprobe] of the prepared fp32 queries over the centroids."""
+        if q32.shape[0] <= kernels.ONLINE_MAX_NQ:
+            return kernels.flatip_topk_online(q32, self.centroids, nprobe)
+        return kernels.flatip_topk(q32, self.centroids, nprobe)
+
+    def search_tensors(self, query_embeddings: Array, k: int, exclude_bits: Optional[torch.Tensor] = None,
+                       nprobe: Optional[int] = None, tag_filter=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """As :meth:`HipIVFFlatIndex.search_tensors`; the scores are the ADC
+        approximations. With ``by_residual`` the coarse scores are the scan's bias."""
+        if self.index is None:
+            raise ValueError("Index not built yet")
+        if self._flat is not None:
+            return self._flat.search_tensors(query_embeddings, k, exclude_bits=exclude_bits, tag_filter=tag_filter)
+        if not 1 <= k <= kernels.IVF_MAX_K:
+            raise ValueError(f"k={k}: the MI355X IVF index returns 1..{kernels.IVF_MAX_K} results per query")
+        np_ = self._n_probe(nprobe)
+        q32 = self._prepare(query_embeddings)
+        exclude_bits = self._filter_bits(tag_filter, q32.shape[0], exclude_bits)
+        coarse, probes = self.coarse_search(q32, np_)
+        return kernels.ivf_pq_topk(q32, self.index, self.codebooks, self.list_offsets, self.row_pos, probes,
+                                   self.max_list_rows, k, bias=coarse if self.by_residual else None,
+                                   exclude_bits=exclude_bits)
+
+    def add(self, embeddings: Array, ids: List[str], item_categories=None):
+        """As :meth:`HipIVFFlatIndex.add`: the new rows are assigned to the existing
+        centroids and encoded against the existing codebooks (nothing is trained
+        again), then every list is regrouped."""
+        if self.index is None:
+            raise ValueError("Index not built yet")
+        if self._flat is not None:
+            return super().add(embeddings, ids, item_categories=item_categories)
+        rows = self._prepare(embeddings)
+        n_old, m = self.current_size, rows.shape[0]
+        tags = self._item_tags(item_categories, m)
+        dev = rows.device
+        inv = torch.empty(n_old, dtype=torch.int64, device=dev)
+        inv[self.row_pos.long()] = torch.arange(n_old, dtype=torch.int64, device=dev)
+        src_index = torch.cat([inv, torch.arange(n_old, n_old + m, dtype=torch.int64, device=dev)])
+        new_assign = self._assign_rows(rows, self.centroids)
+        src = torch.cat([self.index, self._encode(rows, new_assign)])
+        self._regroup(src, src_index, torch.cat([self.assign, new_assign]))
+        self._tags_store(n_old, tags)
+        self._record_ids(n_old, ids, max(m, len(ids)))
+        self._generation += 1
+        logger.info("Added %d items to index. Total size: %d", m, self.current_size)
+
+    def _codes_by_position(self) -> torch.Tensor:
+        out = torch.empty_like(self.index)
+        out[self.row_pos.long()] = self.index
+        return out
+
+    def vectors(self) -> np.ndarray:
+        """The RECONSTRUCTION of every row in original order (fp32): the codewords its
+        codes name, plus its list's centroid with ``by_residual`` — not the row that
+        was added (the Flat fallback returns the rows)."""
+        if self._flat is not None:
+            return self._flat.vectors()
+        if self.index is None:
+            return np.zeros((0, self.dimension), np.float32)
+        codes = self._codes_by_position().long()
+        parts = [self.codebooks[m][codes[:, m]] for m in range(self.pq_m)]
+        out = torch.cat(parts, dim=1)
+        if self.by_residual:
+            out = out + self.centroids[self.assign]
+        return out.cpu().numpy()
+
+    def save(self, path: str):
+        """``<path>.pkl`` (id maps) and ``<path>.ivfpq.npz``: codes in original order,
+        codebooks, centroids, assignments, config; the Flat fallback saves as the
+        Flat index does."""
+        if self.index is None:
+            raise ValueError("No index to save")
+        path = Path(path)
+        npz = path.with_suffix(".ivfpq.npz")
+        if self._flat is not None:
+            self._flat.save(str(path))
+            if npz.exists():
+                npz.unlink()
+            return
+        path.parent.mkdir(parents=True, exist_ok=True)
+        self._save_ids(path)
+        cfg = {k: v for k, v in self.config.items() if isinstance(v, (str, int, float, bool, type(None)))}
+        np.savez(npz, codes=self._codes_by_position().cpu().numpy(), codebooks=self.codebooks.cpu().numpy(),
+                 centroids=self.centroids.cpu().numpy(), assign=self.assign.cpu().numpy(),
+                 config=np.array(json.dumps(cfg)), seed=np.int64(self.seed), nlist=np.int64(self.nlist),
+                 by_residual=np.bool_(self.by_residual))
+        self._save_tags(path)
+        logger.info("Saved index to %s", path)
+
+    def load(self, path: str):
+        path = Path(path)
+        npz = path.with_suffix(".ivfpq.npz")
+        if not npz.exists():   # saved by the Flat fallback
+            self.codebooks = None
+            return super().load(str(path))
+        self._online = None
+        data = self._read_pkl(path)
+        with np.load(npz) as z:
+            codes, codebooks, centroids, assign = z["codes"], z["codebooks"], z["centroids"], z["assign"]
+            self.seed, self.nlist, self.by_residual = int(z["seed"]), int(z["nlist"]), bool(z["by_residual"])
+        self._flat = None
+        self.config = dict(data.get("config", self.config))
+        self.metric = self.config.get("metric", self.metric)
+        self.pq_m, self.dimension = int(codebooks.shape[0]), int(centroids.shape[1])
+        self.index_factory = f"IVF{self.nlist},PQ{self.pq_m}"
+        dev = self._dev()
+        self.centroids = torch.from_numpy(centroids).to(dev)
+        self.codebooks = torch.from_numpy(codebooks).to(dev)
+        self._regroup(torch.from_numpy(codes).to(dev), None, torch.from_numpy(assign).to(dev))
+        self._load_ids(data, self.current_size)
+        self._load_tags(path)
+        self._generation += 1
+        logger.info("Loaded index from %s with %d items", path, self.current_size)
+
+
 # Backwards-compatible name: configs with index_type "faiss" get the exact
 # HBM-resident index (Faiss-CPU is not part of the MI355X build).
 FaissIndex = HipFlatIPIndex
 
 _INDEX_TYPES = {"hip_flat": HipFlatIPIndex, "faiss": HipFlatIPIndex, "hip_flat_sharded": HipShardedFlatIPIndex,
-                "hip_ivf": HipIVFFlatIndex, "hip_ivf_mutable": HipMutableIVFFlatIndex}
+                "hip_ivf": HipIVFFlatIndex, "hip_ivf_mutable": HipMutableIVFFlatIndex, "hip_ivf_pq": HipIVFPQIndex}
 
 
 def register_index(name: str, cls):

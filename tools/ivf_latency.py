@@ -69,6 +69,15 @@ lambda 0.5; alternating call by call, 6 rounds with each side first in turn. p50
 p99 per side and round, the added p50, the ratio, and the re-rank launch alone by
 hipEvent pairs. No bar.
 
+``--legs pq`` (not in the default list): the product-quantised index against
+IVF-Flat float16 on the same corpus, nlist and probes: ``hip_ivf_pq`` at M = 16 and
+M = 32, ``hip_ivf`` float16; nprobe = 20, k = 10, nq in {1, 8, 256, 4096}. The three
+``search_tensors`` calls alternate call by call (host clock around a call that ends
+in a device synchronise), 3 rounds with each side first in turn; per
+configuration the median latency per round, recall@10 against the exact Flat
+lists and against IVF-Flat, and the resident bytes per item (codes or rows, plus
+row_pos and the assignment). No bar.
+
 Prints one JSON line per case and a closing summary line; run it under a time
 limit, e.g. ``timeout 900 python tools/ivf_latency.py > profiles/ivf_latency.txt``.
 """
@@ -88,7 +97,8 @@ for p in (REPO, os.path.join(REPO, "real-time-recommendation-system-with-feature
 import torch  # noqa: E402
 
 from rtrec_amd import kernels  # noqa: E402
-from rtrec_amd.serving.retrieval import HipFlatIPIndex, HipIVFFlatIndex, HipMutableIVFFlatIndex  # noqa: E402
+from rtrec_amd.serving.retrieval import (HipFlatIPIndex, HipIVFFlatIndex, HipIVFPQIndex,  # noqa: E402
+                                         HipMutableIVFFlatIndex)
 
 
 def pct(samples_ms):
@@ -474,6 +484,56 @@ def leg_batch(args, storage, rows, queries, dev):
     return out
 
 
+def leg_pq(args, rows, dev):
+    """The pq leg: one JSON line per nq. ``rows``: fp32 unit rows on the device."""
+    n, d, k, nprobe = rows.shape[0], rows.shape[1], 10, 20
+    nqs = [int(x) for x in args.pq_nq.split(",")]
+    queries = torch.from_numpy(corpus(n, d, 4096, max(nqs), dev)[1]).to(dev)   # the same rows, more queries
+    base = {"dimension": d, "metric": "cosine", "nprobe": nprobe, "train_iters": args.train_iters}
+    sides, build_s = {}, {}
+    for name, cls, cfg in (("ivf_f16", HipIVFFlatIndex, {"index_factory": f"IVF{args.nlist},Flat",
+                                                         "storage_dtype": "float16"}),
+                           ("pq16", HipIVFPQIndex, {"index_factory": f"IVF{args.nlist},PQ16"}),
+                           ("pq32", HipIVFPQIndex, {"index_factory": f"IVF{args.nlist},PQ32"})):
+        t0 = time.perf_counter()
+        sides[name] = cls({**base, **cfg})
+        sides[name].build(rows, [])
+        torch.cuda.synchronize()
+        build_s[name] = round(time.perf_counter() - t0, 3)
+    flat = HipFlatIPIndex({"dimension": d, "metric": "cosine", "storage_dtype": "float32"})
+    flat.build(rows, [])
+    # what a search reads per item and what stays resident next to it (row_pos int32, assign int64)
+    bytes_per_item = {name: ix.index.shape[1] * ix.index.element_size() + 12 for name, ix in sides.items()}
+    out = []
+    for nq in nqs:
+        q = queries[:nq].contiguous()
+        calls = max(5, min(args.calls, 20480 // nq))
+
+        def run(ix):
+            def f():
+                r = ix.search_tensors(q, k)
+                torch.cuda.synchronize()
+                return r
+            return f
+
+        fns = {name: run(ix) for name, ix in sides.items()}
+        exact = flat.search_tensors(q, k)[1].cpu().numpy()
+        got = {name: f()[1].cpu().numpy() for name, f in fns.items()}
+        names, rounds = list(fns), []
+        for r in range(3):
+            order = names[r:] + names[:r]
+            rounds.append({"first": order[0], **timed_alternating({nm: fns[nm] for nm in order}, calls, 3)})
+        case = {"leg": "pq", "nq": nq, "nprobe": nprobe, "k": k, "calls_per_round": calls, "rounds": rounds,
+                "p50_ms": {nm: sorted(r[nm]["p50_ms"] for r in rounds)[1] for nm in names},
+                "recall_at_10_vs_flat": {nm: round(recall(got[nm], exact), 4) for nm in names},
+                "recall_at_10_vs_ivf_flat": {nm: round(recall(got[nm], got["ivf_f16"]), 4) for nm in names},
+                "bytes_per_item": bytes_per_item, "build_s": build_s}
+        print(json.dumps(case), flush=True)
+        out.append({key: case[key] for key in ("nq", "p50_ms", "recall_at_10_vs_flat", "recall_at_10_vs_ivf_flat",
+                                               "bytes_per_item")})
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=1_000_000)
@@ -487,7 +547,8 @@ def main():
     ap.add_argument("--nq", default="1,8")
     ap.add_argument("--chunk-tiles", default="", help="comma list of chunk floors (256-row tiles) for the scan alone")
     ap.add_argument("--train-iters", type=int, default=10)
-    ap.add_argument("--legs", default="search", help="comma list of: search (the default), exclude, mutate, batch, filter, mmr")
+    ap.add_argument("--legs", default="search", help="comma list of: search (the default), exclude, mutate, batch, filter, mmr, pq")
+    ap.add_argument("--pq-nq", default="1,8,256,4096", help="batch sizes of the pq leg")
     ap.add_argument("--mutate-sizes", default="1,64,1024", help="known rows per update call of the mutate leg")
     ap.add_argument("--mutate-calls", type=int, default=12, help="timed update calls per size (fewer for large sizes)")
     ap.add_argument("--exclude-nprobe", type=int, default=20)
@@ -502,8 +563,14 @@ def main():
     ids = []   # positions only: the id maps are not what is measured
     summary = {"rows": n, "dim": d, "k": k, "nlist": args.nlist, "cases": []}
     legs = args.legs.split(",")
-    if set(legs) - {"search", "exclude", "mutate", "batch", "filter", "mmr"}:
+    if set(legs) - {"search", "exclude", "mutate", "batch", "filter", "mmr", "pq"}:
         raise SystemExit(f"unknown leg in {args.legs!r}")
+    if "pq" in legs:
+        summary["pq"] = leg_pq(args, rows, dev)
+        torch.cuda.empty_cache()
+        if legs == ["pq"]:
+            print(json.dumps(summary), flush=True)
+            return
     if "batch" in legs:
         # the same rows (the generator draws them first) and as many queries as the largest batch
         nq_max = max(int(x) for x in args.batch_nq.split(","))
