@@ -387,6 +387,69 @@ int rt_ivf_pq_topk(const float* queries, int64_t nq, int d, const uint8_t* codes
                    void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * IVF-SQ8 (faiss.index_factory(d, "IVF1024,SQ8")): lists of 8-bit scalar-
+ * quantised rows. The quantiser is lo, step and inv_step, fp32 [d] each
+ * (device, 16-byte aligned); a stored row is d bytes, 16-byte aligned.
+ * Limits of both entry points: d % 16 == 0, RT_SQ8_MIN_D <= d <= RT_SQ8_MAX_D.
+ *   Decoding: x^_j = lo_j + (code_j + 0.5) step_j.
+ *   Encoding, r_j the element: t = (r_j - lo_j) * inv_step_j (one fp32
+ *   subtraction, one fp32 multiplication); code_j = 255 if t >= 255, (int)t if
+ *   t > 0, else 0 (NaN gives 0; inv_step_j == 0 always gives 0; values outside
+ *   the range clamp, as in Faiss).
+ *   Score of query q against a row of the list named by probe entry p, fp32,
+ *   a function of (q, row) only, never of the grid:
+ *     mid_j = fmaf(0.5f, step_j, lo_j)
+ *     b0[q] = the chain fmaf(q_j, mid_j, .) over j ascending from 0
+ *     qs[q][j] = q_j * step_j
+ *     acc = bias[q][p] + b0[q]   (b0[q] when bias == NULL)
+ *     acc = fmaf(qs[q][j], (float)code_j, acc), j ascending.
+ *
+ * rt_sq8_encode: codes (uint8 [n, d], 16-byte aligned) of rows [n, d] of
+ *   `dtype` (f32 / f16 / bf16, 16-byte aligned). centroids (fp32 [nlist, d],
+ *   16-byte aligned) and assign (int64 [n]) come together or are both NULL:
+ *   with them r = to_f32(x) - centroid[assign[i]] (one fp32 subtraction),
+ *   without them — or for a row whose assign is outside [0, nlist) — the
+ *   widened row itself. One launch, stream-ordered; reads and writes are
+ *   coalesced, codes are written as whole 4-byte words.
+ *   Status, before any device work: RT_ERR_INVALID for a NULL rows / lo /
+ *   inv_step / codes (n > 0), centroids without assign or the reverse,
+ *   centroids with nlist <= 0, n < 0, d <= 0, an unknown dtype, a misaligned
+ *   rows / lo / inv_step / centroids / codes; RT_ERR_UNSUPPORTED for d outside
+ *   the limits or n d >= 2^41. n == 0: RT_OK.
+ * rt_ivf_sq8_topk: rt_ivf_topk over lists of codes with the score above. bias
+ *   (fp32 [nq, nprobe], device; NULL = 0): for codes of residuals the query's
+ *   inner product with the list's centroid — the coarse search's scores — so
+ *   that the score approximates q.x at no cost to the scan. queries fp32
+ *   [nq, d], 16-byte aligned; codes uint8 [nx, d] stored list-contiguous;
+ *   list_offsets, nlist, row_pos, probes, max_list_rows, exclude_bits /
+ *   exclude_words, k, nprobe, nq and nx: as rt_ivf_pq_topk — the same window
+ *   clamping, the same grid (rt_ivf_topk_plan, honouring rt_ivf_topk_tuning)
+ *   and the same result contract. Three launches (fold, scan, finish), no
+ *   host read, stream-ordered, capturable.
+ *   Status, before any device work: RT_ERR_INVALID for a NULL operand (codes /
+ *   row_pos may be NULL when nx == 0; bias and exclude_bits are optional),
+ *   k <= 0, nprobe <= 0, nlist <= 0, d <= 0, a negative size, misaligned
+ *   queries / lo / step / codes / workspace (16 bytes), exclude_words too
+ *   small; RT_ERR_UNSUPPORTED for d outside the limits, k > RT_IVF_MAX_K,
+ *   nprobe > RT_IVF_MAX_NPROBE, nq > 65,535, nx >= 2^31 - 1; RT_ERR_WORKSPACE.
+ *   nq == 0: RT_OK.
+ * rt_ivf_sq8_topk_workspace_bytes: rt_ivf_topk's partial lists rounded up to
+ *   256 bytes, then per query the folded query: d floats of qs and nprobe
+ *   (rounded up to 4) floats of bias + b0 (256 for a refused shape); monotone
+ *   in nq and in d.
+ * ------------------------------------------------------------------------ */
+#define RT_SQ8_MIN_D 16
+#define RT_SQ8_MAX_D 256
+int rt_sq8_encode(const void* rows, int64_t n, int d, int dtype, const float* centroids, int64_t nlist,
+                  const int64_t* assign, const float* lo, const float* inv_step, uint8_t* codes, void* stream);
+size_t rt_ivf_sq8_topk_workspace_bytes(int64_t nq, int nprobe, int64_t max_list_rows, int k, int d);
+int rt_ivf_sq8_topk(const float* queries, int64_t nq, int d, const uint8_t* codes, int64_t nx, const float* lo,
+                    const float* step, const int64_t* list_offsets, int64_t nlist, const int32_t* row_pos,
+                    const int64_t* probes, const float* bias, int nprobe, int64_t max_list_rows, int k,
+                    const uint32_t* exclude_bits, int64_t exclude_words, float* out_scores, int64_t* out_ids,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * IVF-Flat, list-major batch search: faiss.IndexIVFFlat.search with a batch
  * of users (src/serving/retrieval.py:141-197 at Q in the thousands, and the
  * offline evaluation), where rt_ivf_topk reads a list again for every (query,

@@ -913,6 +913,111 @@ def ivf_pq_topk(queries: torch.Tensor, codes: torch.Tensor, codebooks: torch.Ten
     return scores, ids
 
 
+# ---------------------------------------------------------------------------
+# IVF-SQ8 (faiss "IVF<nlist>,SQ8": 8-bit scalar-quantised lists, include/rtrec_hip.h)
+# ---------------------------------------------------------------------------
+
+SQ8_MIN_D, SQ8_MAX_D = 16, 256   # RT_SQ8_MIN_D, RT_SQ8_MAX_D
+
+
+def _sq8_params(d: int, what: str, **params: torch.Tensor) -> None:
+    """d within the kernels' limits and every quantiser parameter a contiguous fp32 [d]."""
+    if not (SQ8_MIN_D <= d <= SQ8_MAX_D and d % 16 == 0):
+        raise ValueError(f"{what}: d={d} — served: d % 16 == 0, {SQ8_MIN_D} <= d <= {SQ8_MAX_D}")
+    for name, t in params.items():
+        if t.dtype != torch.float32 or tuple(t.shape) != (d,) or not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous fp32 [{d}]")
+
+
+def sq8_encode(rows: torch.Tensor, lo: torch.Tensor, inv_step: torch.Tensor,
+               centroids: Optional[torch.Tensor] = None, assign: Optional[torch.Tensor] = None,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 codes ``[n, d]`` of ``rows`` [n, d] (fp32 / f16 / bf16) under the
+    per-dimension quantiser ``lo``, ``inv_step`` (fp32 [d]) (rt_sq8_encode):
+    ``t = (r - lo) * inv_step``, code 255 for t >= 255, int(t) for t > 0, else 0 —
+    values outside the range clamp. With ``centroids`` (fp32 [nlist, d]) and
+    ``assign`` (int64 [n]) r is the residual ``row - centroids[assign]`` (a row
+    whose ``assign`` is outside [0, nlist): the row itself)."""
+    native.require_device(rows, lo, inv_step, centroids, assign, out, what="sq8_encode")
+    if rows.dim() != 2 or not rows.is_contiguous():
+        raise ValueError("sq8_encode expects contiguous [n, d] rows")
+    n, d = rows.shape
+    _sq8_params(d, "sq8_encode", lo=lo, inv_step=inv_step)
+    if (centroids is None) != (assign is None):
+        raise ValueError("centroids and assign come together")
+    nlist = 0
+    if centroids is not None:
+        if centroids.dtype != torch.float32 or centroids.dim() != 2 or centroids.shape[1] != d \
+                or not centroids.is_contiguous() or centroids.shape[0] < 1:
+            raise ValueError(f"centroids must be contiguous fp32 [nlist, {d}]")
+        if assign.dtype != torch.int64 or assign.numel() != n or not assign.is_contiguous():
+            raise ValueError("assign must be contiguous int64 [n]")
+        nlist = centroids.shape[0]
+    if out is None:
+        out = torch.empty((n, d), dtype=torch.uint8, device=rows.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (n, d) or not out.is_contiguous():
+        raise ValueError(f"out must be contiguous uint8 [{n}, {d}]")
+    call("rt_sq8_encode", ptr(rows) if n else None, n, d, native.dtype_code(rows.dtype), ptr(centroids), nlist,
+         ptr(assign), ptr(lo), ptr(inv_step), ptr(out) if n else None, stream_of(rows))
+    return out
+
+
+def ivf_sq8_topk(queries: torch.Tensor, codes: torch.Tensor, lo: torch.Tensor, step: torch.Tensor,
+                 list_offsets: torch.Tensor, row_pos: torch.Tensor, probes: torch.Tensor, max_list_rows: int, k: int,
+                 bias: Optional[torch.Tensor] = None, exclude_bits: Optional[torch.Tensor] = None,
+                 out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                 workspace_buf: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Top-k over the probed lists of a scalar-quantised corpus (rt_ivf_sq8_topk):
+    the operands and the result contract of :func:`ivf_topk` with the rows
+    replaced by ``codes`` uint8 [nx, d] (list-contiguous) and the quantiser ``lo``,
+    ``step`` (fp32 [d]); ``queries`` fp32 [nq, d]. A row's score is ``bias[q, p]``
+    (fp32 [nq, nprobe], None = 0: for residual codes the coarse search's scores)
+    plus the query's inner product with the decoded row ``lo + (code + 0.5) step``,
+    in the order of include/rtrec_hip.h. Batches above 32,768 queries run in chunks."""
+    native.require_device(queries, codes, lo, step, list_offsets, row_pos, probes, bias, exclude_bits,
+                          what="ivf_sq8_topk")
+    if queries.dim() != 2 or queries.dtype != torch.float32:
+        raise ValueError("ivf_sq8_topk expects fp32 [nq, d] queries")
+    nq, d = queries.shape
+    if codes.dtype != torch.uint8 or codes.dim() != 2 or codes.shape[1] != d:
+        raise ValueError(f"codes must be uint8 [nx, {d}]")
+    nx = codes.shape[0]
+    _sq8_params(d, "ivf_sq8_topk", lo=lo, step=step)
+    if not 1 <= k <= IVF_MAX_K:
+        raise ValueError(f"k={k}: ivf_sq8_topk returns 1..{IVF_MAX_K} results per query")
+    if not (queries.is_contiguous() and codes.is_contiguous() and probes.is_contiguous()
+            and list_offsets.is_contiguous() and row_pos.is_contiguous()):
+        raise ValueError("ivf_sq8_topk expects contiguous operands")
+    if list_offsets.dtype != torch.int64 or list_offsets.dim() != 1 or list_offsets.numel() < 2:
+        raise ValueError("list_offsets must be int64 [nlist + 1]")
+    if row_pos.dtype != torch.int32 or row_pos.numel() != nx:
+        raise ValueError("row_pos must be int32 [nx]")
+    if probes.dtype != torch.int64 or probes.dim() != 2 or probes.shape[0] != nq:
+        raise ValueError("probes must be int64 [nq, nprobe]")
+    nprobe = probes.shape[1]
+    if not 1 <= nprobe <= IVF_MAX_NPROBE:
+        raise ValueError(f"nprobe={nprobe}: 1..{IVF_MAX_NPROBE}")
+    if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (nq, nprobe)
+                             or not bias.is_contiguous()):
+        raise ValueError(f"bias must be contiguous fp32 [{nq}, {nprobe}]")
+    nlist = list_offsets.numel() - 1
+    scores, ids = _topk_out(out, nq, k, queries.device)
+    words = _exclude_words(exclude_bits, nq, True)
+    for a in range(0, nq, IVF_QUERY_CHUNK):
+        b = min(nq, a + IVF_QUERY_CHUNK)
+        ws = workspace_buf
+        if ws is None:
+            ws = workspace(queries.device,
+                           native.lib().rt_ivf_sq8_topk_workspace_bytes(b - a, nprobe, int(max_list_rows), k, d),
+                           "ivf_sq8_topk")
+        call("rt_ivf_sq8_topk", ptr(queries[a:b]), b - a, d, ptr(codes) if nx else None, nx, ptr(lo), ptr(step),
+             ptr(list_offsets), nlist, ptr(row_pos) if nx else None, ptr(probes[a:b]),
+             ptr(bias[a:b]) if bias is not None else None, nprobe, int(max_list_rows), k,
+             ptr(exclude_bits[a:b]) if exclude_bits is not None else None, words, ptr(scores[a:b]), ptr(ids[a:b]),
+             ptr(ws), ws.numel(), stream_of(queries))
+    return scores, ids
+
+
 # Workspace one rt_ivf_topk_batch call may take; larger batches run in query
 # chunks. A policy default (the partial lists of a chunk stay inside the 256 MB
 # Infinity Cache), not a measured one.

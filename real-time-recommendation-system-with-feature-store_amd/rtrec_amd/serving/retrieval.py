@@ -2337,6 +2337,102 @@ class HipMutableIVFFlatIndex(HipIVFFlatIndex):
         return kernels.gather_rows(self.index, self.pos_slot[: self.current_size].long()).float().cpu().numpy()
 
 
+class _IVFCodesIndex(HipIVFFlatIndex):
+    """What the IVF indexes that keep codes instead of rows share (:class:`HipIVFPQIndex`,
+    :class:`HipIVFSQ8Index`): the refusals of what needs stored rows or lists with slack,
+    the search around the scan (``_scan_codes``), ``add`` against the trained quantiser
+    (``_encode``) and the codes in original order."""
+
+    _searcher_takes_exclude = False
+
+    def __init__(self, config: Optional[Dict[str, Any]] = None):
+        cfg = dict(config or {})
+        name = type(self).__name__
+        if cfg.get("online_max_batch"):
+            raise ValueError(f"{name} has no resident searcher (online_max_batch): HipIVFFlatIndex has")
+        if cfg.get("batch_min_queries") is not None:
+            raise ValueError(f"{name} has no list-major batch scan (batch_min_queries): HipIVFFlatIndex has")
+        super().__init__(cfg)
+        self.by_residual = bool(self.config.get("by_residual", True))
+
+    @property
+    def codes(self) -> Optional[torch.Tensor]:
+        """uint8 [n, bytes per row], list-contiguous (``index`` of this class)."""
+        return None if self._flat is not None else self.index
+
+    def _check_mmr(self):
+        raise ValueError(f"mmr_lambda: the MMR re-rank reads stored rows, and {type(self).__name__} keeps codes only; "
+                         "HipIVFFlatIndex serves it")
+
+    def online_searcher(self, max_batch: int = 8, max_exclude: int = 8192) -> "OnlineSearcher":
+        raise ValueError(f"{type(self).__name__} has no resident searcher; HipIVFFlatIndex.online_searcher has")
+
+    def update(self, embeddings: Array, ids: List[str], item_categories=None):
+        raise NotImplementedError(f"{type(self).__name__} does not update in place; HipMutableIVFFlatIndex does")
+
+    def remove(self, ids: List[str]):
+        raise NotImplementedError(f"{type(self).__name__} does not remove; HipMutableIVFFlatIndex does")
+
+    def _encode(self, rows: torch.Tensor, assign: torch.Tensor) -> torch.Tensor:
+        """uint8 codes of prepared fp32 rows under the trained quantiser."""
+        raise NotImplementedError
+
+    def _scan_codes(self, q32: torch.Tensor, probes: torch.Tensor, k: int, bias: Optional[torch.Tensor],
+                    exclude_bits: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The probed-list scan over ``self.index``."""
+        raise NotImplementedError
+
+    def coarse_search(self, q32: torch.Tensor, nprobe: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(scores, lists) [nq, nprobe] of the prepared fp32 queries over the centroids."""
+        if q32.shape[0] <= kernels.ONLINE_MAX_NQ:
+            return kernels.flatip_topk_online(q32, self.centroids, nprobe)
+        return kernels.flatip_topk(q32, self.centroids, nprobe)
+
+    def search_tensors(self, query_embeddings: Array, k: int, exclude_bits: Optional[torch.Tensor] = None,
+                       nprobe: Optional[int] = None, tag_filter=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """As :meth:`HipIVFFlatIndex.search_tensors`; the scores are approximations
+        from the codes. With ``by_residual`` the coarse scores are the scan's bias."""
+        if self.index is None:
+            raise ValueError("Index not built yet")
+        if self._flat is not None:
+            return self._flat.search_tensors(query_embeddings, k, exclude_bits=exclude_bits, tag_filter=tag_filter)
+        if not 1 <= k <= kernels.IVF_MAX_K:
+            raise ValueError(f"k={k}: the MI355X IVF index returns 1..{kernels.IVF_MAX_K} results per query")
+        np_ = self._n_probe(nprobe)
+        q32 = self._prepare(query_embeddings)
+        exclude_bits = self._filter_bits(tag_filter, q32.shape[0], exclude_bits)
+        coarse, probes = self.coarse_search(q32, np_)
+        return self._scan_codes(q32, probes, k, coarse if self.by_residual else None, exclude_bits)
+
+    def add(self, embeddings: Array, ids: List[str], item_categories=None):
+        """As :meth:`HipIVFFlatIndex.add`: the new rows are assigned to the existing
+        centroids and encoded against the existing quantiser (nothing is trained
+        again), then every list is regrouped."""
+        if self.index is None:
+            raise ValueError("Index not built yet")
+        if self._flat is not None:
+            return super().add(embeddings, ids, item_categories=item_categories)
+        rows = self._prepare(embeddings)
+        n_old, m = self.current_size, rows.shape[0]
+        tags = self._item_tags(item_categories, m)
+        dev = rows.device
+        inv = torch.empty(n_old, dtype=torch.int64, device=dev)
+        inv[self.row_pos.long()] = torch.arange(n_old, dtype=torch.int64, device=dev)
+        src_index = torch.cat([inv, torch.arange(n_old, n_old + m, dtype=torch.int64, device=dev)])
+        new_assign = self._assign_rows(rows, self.centroids)
+        src = torch.cat([self.index, self._encode(rows, new_assign)])
+        self._regroup(src, src_index, torch.cat([self.assign, new_assign]))
+        self._tags_store(n_old, tags)
+        self._record_ids(n_old, ids, max(m, len(ids)))
+        self._generation += 1
+        logger.info("Added %d items to index. Total size: %d", m, self.current_size)
+
+    def _codes_by_position(self) -> torch.Tensor:
+        out = torch.empty_like(self.index)
+        out[self.row_pos.long()] = self.index
+        return out
+
+
 _IVF_PQ_FACTORY = "IVF1024,PQ16"
 
 
@@ -2354,7 +2450,7 @@ def _parse_ivf_pq_factory(factory: str) -> Tuple[int, int]:
     return int(head[3:]), int(m)
 
 
-class HipIVFPQIndex(HipIVFFlatIndex):
+class HipIVFPQIndex(_IVFCodesIndex):
     """IVF index with product-quantised lists resident in HBM:
     ``faiss.index_factory(d, "IVF1024,PQ16")`` (the reference hands its
     ``index_factory`` string to Faiss, retrieval.py:96-110). A row is stored as M
@@ -2402,44 +2498,19 @@ class HipIVFPQIndex(HipIVFFlatIndex):
     writes ``<path>.ivfpq.npz`` (codes in original order, codebooks, centroids,
     assignments) and ``<path>.pkl``, and a loaded index answers bit-identically."""
 
-    _searcher_takes_exclude = False
     _default_factory = _IVF_PQ_FACTORY
 
     def __init__(self, config: Optional[Dict[str, Any]] = None):
-        cfg = dict(config or {})
-        if cfg.get("online_max_batch"):
-            raise ValueError("HipIVFPQIndex has no resident searcher (online_max_batch): HipIVFFlatIndex has")
-        if cfg.get("batch_min_queries") is not None:
-            raise ValueError("HipIVFPQIndex has no list-major batch scan (batch_min_queries): HipIVFFlatIndex has")
-        super().__init__(cfg)
+        super().__init__(config)
         if kernels._pq_shape(self.dimension, self.pq_m, f"index_factory {self.index_factory!r}") % 4:
             raise ValueError(f"index_factory {self.index_factory!r}: the codebook training takes sub-vectors of a "
                              f"multiple of 4 elements (rt_segment_mean_f32), d / M = {self.dimension // self.pq_m}")
-        self.by_residual = bool(self.config.get("by_residual", True))
         self.pq_train_iters = int(self.config.get("pq_train_iters", 25))
         self.codebooks: Optional[torch.Tensor] = None   # [M, 256, d / M] fp32
 
     def _parse_factory(self, factory: str) -> int:
         nlist, self.pq_m = _parse_ivf_pq_factory(factory)
         return nlist
-
-    @property
-    def codes(self) -> Optional[torch.Tensor]:
-        """uint8 [n, M], list-contiguous (``index`` of this class)."""
-        return None if self._flat is not None else self.index
-
-    def _check_mmr(self):
-        raise ValueError("mmr_lambda: the MMR re-rank reads stored rows, and HipIVFPQIndex keeps codes only; "
-                         "HipIVFFlatIndex serves it")
-
-    def online_searcher(self, max_batch: int = 8, max_exclude: int = 8192) -> "OnlineSearcher":
-        raise ValueError("HipIVFPQIndex has no resident searcher; HipIVFFlatIndex.online_searcher has")
-
-    def update(self, embeddings: Array, ids: List[str], item_categories=None):
-        raise NotImplementedError("HipIVFPQIndex does not update in place; HipMutableIVFFlatIndex does")
-
-    def remove(self, ids: List[str]):
-        raise NotImplementedError("HipIVFPQIndex does not remove; HipMutableIVFFlatIndex does")
 
     # -- product quantiser -------------------------------------------------
     def _train_pq(self, rows: torch.Tensor, assign: torch.Tensor) -> torch.Tensor:
@@ -2492,57 +2563,9 @@ class HipIVFPQIndex(HipIVFFlatIndex):
         self._generation += 1
         logger.info("Index built in %.2f seconds", time.time() - start)
 
-    def coarse_search(self, q32: torch.Tensor, nprobe: int) -> Tuple[torch.Tensor, torch.Tensor]:
-        """(scores, lists) [nq, nprobe] of the prepared fp32 queries over the centroids."""
-        if q32.shape[0] <= kernels.ONLINE_MAX_NQ:
-            return kernels.flatip_topk_online(q32, self.centroids, nprobe)
-        return kernels.flatip_topk(q32, self.centroids, nprobe)
-
-    def search_tensors(self, query_embeddings: Array, k: int, exclude_bits: Optional[torch.Tensor] = None,
-                       nprobe: Optional[int] = None, tag_filter=None) -> Tuple[torch.Tensor, torch.Tensor]:
-        """As :meth:`HipIVFFlatIndex.search_tensors`; the scores are the ADC
-        approximations. With ``by_residual`` the coarse scores are the scan's bias."""
-        if self.index is None:
-            raise ValueError("Index not built yet")
-        if self._flat is not None:
-            return self._flat.search_tensors(query_embeddings, k, exclude_bits=exclude_bits, tag_filter=tag_filter)
-        if not 1 <= k <= kernels.IVF_MAX_K:
-            raise ValueError(f"k={k}: the MI355X IVF index returns 1..{kernels.IVF_MAX_K} results per query")
-        np_ = self._n_probe(nprobe)
-        q32 = self._prepare(query_embeddings)
-        exclude_bits = self._filter_bits(tag_filter, q32.shape[0], exclude_bits)
-        coarse, probes = self.coarse_search(q32, np_)
+    def _scan_codes(self, q32, probes, k, bias, exclude_bits):
         return kernels.ivf_pq_topk(q32, self.index, self.codebooks, self.list_offsets, self.row_pos, probes,
-                                   self.max_list_rows, k, bias=coarse if self.by_residual else None,
-                                   exclude_bits=exclude_bits)
-
-    def add(self, embeddings: Array, ids: List[str], item_categories=None):
-        """As :meth:`HipIVFFlatIndex.add`: the new rows are assigned to the existing
-        centroids and encoded against the existing codebooks (nothing is trained
-        again), then every list is regrouped."""
-        if self.index is None:
-            raise ValueError("Index not built yet")
-        if self._flat is not None:
-            return super().add(embeddings, ids, item_categories=item_categories)
-        rows = self._prepare(embeddings)
-        n_old, m = self.current_size, rows.shape[0]
-        tags = self._item_tags(item_categories, m)
-        dev = rows.device
-        inv = torch.empty(n_old, dtype=torch.int64, device=dev)
-        inv[self.row_pos.long()] = torch.arange(n_old, dtype=torch.int64, device=dev)
-        src_index = torch.cat([inv, torch.arange(n_old, n_old + m, dtype=torch.int64, device=dev)])
-        new_assign = self._assign_rows(rows, self.centroids)
-        src = torch.cat([self.index, self._encode(rows, new_assign)])
-        self._regroup(src, src_index, torch.cat([self.assign, new_assign]))
-        self._tags_store(n_old, tags)
-        self._record_ids(n_old, ids, max(m, len(ids)))
-        self._generation += 1
-        logger.info("Added %d items to index. Total size: %d", m, self.current_size)
-
-    def _codes_by_position(self) -> torch.Tensor:
-        out = torch.empty_like(self.index)
-        out[self.row_pos.long()] = self.index
-        return out
+                                   self.max_list_rows, k, bias=bias, exclude_bits=exclude_bits)
 
     def vectors(self) -> np.ndarray:
         """The RECONSTRUCTION of every row in original order (fp32): the codewords its
@@ -2608,12 +2631,188 @@ class HipIVFPQIndex(HipIVFFlatIndex):
         logger.info("Loaded index from %s with %d items", path, self.current_size)
 
 
+_IVF_SQ8_FACTORY = "IVF1024,SQ8"
+_SQ8_RANGE_CHUNK = 1 << 18   # rows per amin / amax pass of the range
+
+
+def _parse_ivf_sq8_factory(factory: str) -> int:
+    """``"IVF<nlist>,SQ8"`` -> nlist; anything else raises."""
+    head, _, tail = str(factory).partition(",")
+    if not (head.startswith("IVF") and head[3:].isdigit() and int(head[3:]) >= 1 and tail == "SQ8"):
+        raise ValueError(f"index_factory {factory!r}: HipIVFSQ8Index serves 'IVF<nlist>,SQ8' (one byte per "
+                         "dimension; 'IVF<nlist>,Flat': HipIVFFlatIndex, 'IVF<nlist>,PQ<M>': HipIVFPQIndex)")
+    return int(head[3:])
+
+
+class HipIVFSQ8Index(_IVFCodesIndex):
+    """IVF index with 8-bit scalar-quantised lists resident in HBM:
+    ``faiss.index_factory(d, "IVF1024,SQ8")``. A row is stored as d bytes, one per
+    dimension: code j names one of 256 equal bins of dimension j's range
+    ``[lo_j, hi_j]``, decoded as ``lo_j + (code_j + 0.5) step_j``. The error per
+    dimension is bounded by half a step, 1 / 510 of the range — the point between
+    :class:`HipIVFFlatIndex` (2-4 d bytes, exact) and :class:`HipIVFPQIndex` (M
+    bytes, recall@10 0.3-0.5 at 1M x 128).
+
+    ``build``: the parent's preparation, coarse training and assignment; then
+    ``lo`` / ``hi`` are the exact minimum and maximum per dimension over the
+    residuals ``row - centroid`` (``by_residual``; False: the rows) of ALL rows,
+    ``step = (hi - lo) / 255`` and ``inv_step = 255 / (hi - lo)`` (0 where ``hi ==
+    lo``) in fp32, and every row is encoded (``rt_sq8_encode``) and stored
+    list-contiguous. Deterministic.
+
+    ``search``: the coarse search, then ``rt_ivf_sq8_topk`` over the probed lists.
+    The quantiser is folded into the query once per call (``q_j step_j`` and
+    ``sum_j q_j (lo_j + step_j / 2)``), so the scan is one byte-to-float conversion
+    and one FMA per element; with residual codes the coarse score ``q . centroid``
+    is the scan's bias. Results keep the parent's contract — (score desc, original
+    position asc), -1 pads — with approximate scores. ``exclude_ids``,
+    ``filter_ids`` and the category filters work through the bitmap route.
+
+    Config keys: the parent's ``dimension`` (a multiple of 16, 16..256),
+    ``metric``, ``nprobe``, ``train_iters``, ``seed``, ``max_points_per_centroid``,
+    ``device``, ``categories``; ``index_factory`` (``"IVF<nlist>,SQ8"``, default
+    ``"IVF1024,SQ8"``); ``by_residual`` (True). ``storage_dtype`` only reaches the
+    Flat fallback (below 1,024 items or nlist, as on the parent).
+
+    ``add`` encodes against the existing range — a value outside it clamps to the
+    first or last bin, nothing is trained again. Not served here — each raises and
+    names the class that has it: the MMR re-rank, ``online_max_batch`` /
+    ``online_searcher`` and ``batch_min_queries`` (:class:`HipIVFFlatIndex`);
+    ``update`` / ``remove`` / ``mutable`` (:class:`HipMutableIVFFlatIndex`).
+
+    ``vectors()`` returns the RECONSTRUCTION in original order, within half a step
+    per dimension of the rows that were built; ``save`` writes ``<path>.ivfsq8.npz``
+    (codes in original order, lo, step, inv_step, centroids, assignments) and
+    ``<path>.pkl``, and a loaded index answers bit-identically."""
+
+    _default_factory = _IVF_SQ8_FACTORY
+
+    def __init__(self, config: Optional[Dict[str, Any]] = None):
+        super().__init__(config)
+        kernels._sq8_params(self.dimension, f"index_factory {self.index_factory!r}")
+        self.lo: Optional[torch.Tensor] = None         # [d] fp32, the quantiser
+        self.step: Optional[torch.Tensor] = None
+        self.inv_step: Optional[torch.Tensor] = None
+
+    def _parse_factory(self, factory: str) -> int:
+        return _parse_ivf_sq8_factory(factory)
+
+    def _train_range(self, rows: torch.Tensor, assign: torch.Tensor):
+        """lo, step, inv_step from the exact per-dimension range of every (residual) row."""
+        lo = hi = None
+        for a in range(0, rows.shape[0], _SQ8_RANGE_CHUNK):
+            x = rows[a:a + _SQ8_RANGE_CHUNK]
+            if self.by_residual:
+                x = x - self.centroids[assign[a:a + _SQ8_RANGE_CHUNK]]   # the encode's fp32 subtraction
+            mn, mx = x.amin(dim=0), x.amax(dim=0)
+            lo = mn if lo is None else torch.minimum(lo, mn)
+            hi = mx if hi is None else torch.maximum(hi, mx)
+        span = hi - lo
+        self.lo = lo.contiguous()
+        self.step = (span / 255.0).contiguous()
+        self.inv_step = torch.where(span > 0, 255.0 / span, torch.zeros_like(span)).contiguous()
+
+    def _encode(self, rows: torch.Tensor, assign: torch.Tensor) -> torch.Tensor:
+        if self.by_residual:
+            return kernels.sq8_encode(rows, self.lo, self.inv_step, self.centroids, assign)
+        return kernels.sq8_encode(rows, self.lo, self.inv_step)
+
+    def _scan_codes(self, q32, probes, k, bias, exclude_bits):
+        return kernels.ivf_sq8_topk(q32, self.index, self.lo, self.step, self.list_offsets, self.row_pos, probes,
+                                    self.max_list_rows, k, bias=bias, exclude_bits=exclude_bits)
+
+    def build(self, embeddings: Array, ids: List[str], item_categories=None):
+        """As :meth:`HipIVFFlatIndex.build`, then the range and the codes."""
+        n = len(embeddings)
+        if n < IVF_MIN_ITEMS or n < self.nlist:
+            self.lo = self.step = self.inv_step = None
+            return super().build(embeddings, ids, item_categories=item_categories)   # the Flat fallback
+        start = time.time()
+        tags = self._item_tags(item_categories, n)
+        self._flat = None
+        rows = self._prepare(embeddings)
+        self.centroids = self._train(rows)
+        assign = self._assign_rows(rows, self.centroids)
+        self._train_range(rows, assign)
+        self._regroup(self._encode(rows, assign), None, assign)
+        self._tags = None
+        self._tags_store(0, tags)
+        self._reset_ids()
+        self._record_ids(0, ids, max(n, len(ids)))
+        self._generation += 1
+        logger.info("Index built in %.2f seconds", time.time() - start)
+
+    def vectors(self) -> np.ndarray:
+        """The RECONSTRUCTION of every row in original order (fp32): ``lo + (code + 0.5)
+        step``, plus its list's centroid with ``by_residual`` — not the row that was
+        added (the Flat fallback returns the rows)."""
+        if self._flat is not None:
+            return self._flat.vectors()
+        if self.index is None:
+            return np.zeros((0, self.dimension), np.float32)
+        out = self.lo + (self._codes_by_position().float() + 0.5) * self.step
+        if self.by_residual:
+            out = out + self.centroids[self.assign]
+        return out.cpu().numpy()
+
+    def save(self, path: str):
+        """``<path>.pkl`` (id maps) and ``<path>.ivfsq8.npz``: codes in original order, the
+        quantiser, centroids, assignments, config; the Flat fallback saves as the Flat
+        index does."""
+        if self.index is None:
+            raise ValueError("No index to save")
+        path = Path(path)
+        npz = path.with_suffix(".ivfsq8.npz")
+        if self._flat is not None:
+            self._flat.save(str(path))
+            if npz.exists():
+                npz.unlink()
+            return
+        path.parent.mkdir(parents=True, exist_ok=True)
+        self._save_ids(path)
+        cfg = {k: v for k, v in self.config.items() if isinstance(v, (str, int, float, bool, type(None)))}
+        np.savez(npz, codes=self._codes_by_position().cpu().numpy(), lo=self.lo.cpu().numpy(),
+                 step=self.step.cpu().numpy(), inv_step=self.inv_step.cpu().numpy(),
+                 centroids=self.centroids.cpu().numpy(), assign=self.assign.cpu().numpy(),
+                 config=np.array(json.dumps(cfg)), seed=np.int64(self.seed), nlist=np.int64(self.nlist),
+                 by_residual=np.bool_(self.by_residual))
+        self._save_tags(path)
+        logger.info("Saved index to %s", path)
+
+    def load(self, path: str):
+        path = Path(path)
+        npz = path.with_suffix(".ivfsq8.npz")
+        if not npz.exists():   # saved by the Flat fallback
+            self.lo = self.step = self.inv_step = None
+            return super().load(str(path))
+        self._online = None
+        data = self._read_pkl(path)
+        with np.load(npz) as z:
+            codes, centroids, assign = z["codes"], z["centroids"], z["assign"]
+            quant = [z[name] for name in ("lo", "step", "inv_step")]
+            self.seed, self.nlist, self.by_residual = int(z["seed"]), int(z["nlist"]), bool(z["by_residual"])
+        self._flat = None
+        self.config = dict(data.get("config", self.config))
+        self.metric = self.config.get("metric", self.metric)
+        self.dimension = int(centroids.shape[1])
+        self.index_factory = f"IVF{self.nlist},SQ8"
+        dev = self._dev()
+        self.centroids = torch.from_numpy(centroids).to(dev)
+        self.lo, self.step, self.inv_step = (torch.from_numpy(a).to(dev) for a in quant)
+        self._regroup(torch.from_numpy(codes).to(dev), None, torch.from_numpy(assign).to(dev))
+        self._load_ids(data, self.current_size)
+        self._load_tags(path)
+        self._generation += 1
+        logger.info("Loaded index from %s with %d items", path, self.current_size)
+
+
 # Backwards-compatible name: configs with index_type "faiss" get the exact
 # HBM-resident index (Faiss-CPU is not part of the MI355X build).
 FaissIndex = HipFlatIPIndex
 
 _INDEX_TYPES = {"hip_flat": HipFlatIPIndex, "faiss": HipFlatIPIndex, "hip_flat_sharded": HipShardedFlatIPIndex,
-                "hip_ivf": HipIVFFlatIndex, "hip_ivf_mutable": HipMutableIVFFlatIndex, "hip_ivf_pq": HipIVFPQIndex}
+                "hip_ivf": HipIVFFlatIndex, "hip_ivf_mutable": HipMutableIVFFlatIndex, "hip_ivf_pq": HipIVFPQIndex,
+                "hip_ivf_sq8": HipIVFSQ8Index}
 
 
 def register_index(name: str, cls):

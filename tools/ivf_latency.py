@@ -78,6 +78,11 @@ configuration the median latency per round, recall@10 against the exact Flat
 lists and against IVF-Flat, and the resident bytes per item (codes or rows, plus
 row_pos and the assignment). No bar.
 
+``--legs sq8`` (not in the default list): the pq leg's protocol with ``hip_ivf_sq8`` as the
+third side, next to ``hip_ivf`` float16 and ``hip_ivf_pq`` at M = 16: the scalar-quantised
+index on the same corpus, nlist and probes; additionally the ratio of its p50 to IVF-Flat
+float16's from the same alternating run. No bar.
+
 Prints one JSON line per case and a closing summary line; run it under a time
 limit, e.g. ``timeout 900 python tools/ivf_latency.py > profiles/ivf_latency.txt``.
 """
@@ -98,7 +103,7 @@ import torch  # noqa: E402
 
 from rtrec_amd import kernels  # noqa: E402
 from rtrec_amd.serving.retrieval import (HipFlatIPIndex, HipIVFFlatIndex, HipIVFPQIndex,  # noqa: E402
-                                         HipMutableIVFFlatIndex)
+                                         HipIVFSQ8Index, HipMutableIVFFlatIndex)
 
 
 def pct(samples_ms):
@@ -484,17 +489,18 @@ def leg_batch(args, storage, rows, queries, dev):
     return out
 
 
-def leg_pq(args, rows, dev):
-    """The pq leg: one JSON line per nq. ``rows``: fp32 unit rows on the device."""
+def leg_pq(args, rows, dev, leg="pq"):
+    """The pq and sq8 legs: one JSON line per nq. ``rows``: fp32 unit rows on the device."""
     n, d, k, nprobe = rows.shape[0], rows.shape[1], 10, 20
     nqs = [int(x) for x in args.pq_nq.split(",")]
     queries = torch.from_numpy(corpus(n, d, 4096, max(nqs), dev)[1]).to(dev)   # the same rows, more queries
     base = {"dimension": d, "metric": "cosine", "nprobe": nprobe, "train_iters": args.train_iters}
     sides, build_s = {}, {}
+    third = {"pq": ("pq32", HipIVFPQIndex, {"index_factory": f"IVF{args.nlist},PQ32"}),
+             "sq8": ("sq8", HipIVFSQ8Index, {"index_factory": f"IVF{args.nlist},SQ8"})}[leg]
     for name, cls, cfg in (("ivf_f16", HipIVFFlatIndex, {"index_factory": f"IVF{args.nlist},Flat",
                                                          "storage_dtype": "float16"}),
-                           ("pq16", HipIVFPQIndex, {"index_factory": f"IVF{args.nlist},PQ16"}),
-                           ("pq32", HipIVFPQIndex, {"index_factory": f"IVF{args.nlist},PQ32"})):
+                           ("pq16", HipIVFPQIndex, {"index_factory": f"IVF{args.nlist},PQ16"}), third):
         t0 = time.perf_counter()
         sides[name] = cls({**base, **cfg})
         sides[name].build(rows, [])
@@ -523,11 +529,13 @@ def leg_pq(args, rows, dev):
         for r in range(3):
             order = names[r:] + names[:r]
             rounds.append({"first": order[0], **timed_alternating({nm: fns[nm] for nm in order}, calls, 3)})
-        case = {"leg": "pq", "nq": nq, "nprobe": nprobe, "k": k, "calls_per_round": calls, "rounds": rounds,
+        case = {"leg": leg, "nq": nq, "nprobe": nprobe, "k": k, "calls_per_round": calls, "rounds": rounds,
                 "p50_ms": {nm: sorted(r[nm]["p50_ms"] for r in rounds)[1] for nm in names},
                 "recall_at_10_vs_flat": {nm: round(recall(got[nm], exact), 4) for nm in names},
                 "recall_at_10_vs_ivf_flat": {nm: round(recall(got[nm], got["ivf_f16"]), 4) for nm in names},
                 "bytes_per_item": bytes_per_item, "build_s": build_s}
+        if leg == "sq8":
+            case["sq8_over_ivf_f16"] = round(case["p50_ms"]["sq8"] / case["p50_ms"]["ivf_f16"], 3)
         print(json.dumps(case), flush=True)
         out.append({key: case[key] for key in ("nq", "p50_ms", "recall_at_10_vs_flat", "recall_at_10_vs_ivf_flat",
                                                "bytes_per_item")})
@@ -547,8 +555,8 @@ def main():
     ap.add_argument("--nq", default="1,8")
     ap.add_argument("--chunk-tiles", default="", help="comma list of chunk floors (256-row tiles) for the scan alone")
     ap.add_argument("--train-iters", type=int, default=10)
-    ap.add_argument("--legs", default="search", help="comma list of: search (the default), exclude, mutate, batch, filter, mmr, pq")
-    ap.add_argument("--pq-nq", default="1,8,256,4096", help="batch sizes of the pq leg")
+    ap.add_argument("--legs", default="search", help="comma list of: search (the default), exclude, mutate, batch, filter, mmr, pq, sq8")
+    ap.add_argument("--pq-nq", default="1,8,256,4096", help="batch sizes of the pq and sq8 legs")
     ap.add_argument("--mutate-sizes", default="1,64,1024", help="known rows per update call of the mutate leg")
     ap.add_argument("--mutate-calls", type=int, default=12, help="timed update calls per size (fewer for large sizes)")
     ap.add_argument("--exclude-nprobe", type=int, default=20)
@@ -563,14 +571,15 @@ def main():
     ids = []   # positions only: the id maps are not what is measured
     summary = {"rows": n, "dim": d, "k": k, "nlist": args.nlist, "cases": []}
     legs = args.legs.split(",")
-    if set(legs) - {"search", "exclude", "mutate", "batch", "filter", "mmr", "pq"}:
+    if set(legs) - {"search", "exclude", "mutate", "batch", "filter", "mmr", "pq", "sq8"}:
         raise SystemExit(f"unknown leg in {args.legs!r}")
-    if "pq" in legs:
-        summary["pq"] = leg_pq(args, rows, dev)
-        torch.cuda.empty_cache()
-        if legs == ["pq"]:
-            print(json.dumps(summary), flush=True)
-            return
+    for leg in ("pq", "sq8"):
+        if leg in legs:
+            summary[leg] = leg_pq(args, rows, dev, leg)
+            torch.cuda.empty_cache()
+    if not set(legs) - {"pq", "sq8"}:
+        print(json.dumps(summary), flush=True)
+        return
     if "batch" in legs:
         # the same rows (the generator draws them first) and as many queries as the largest batch
         nq_max = max(int(x) for x in args.batch_nq.split(","))
