@@ -517,6 +517,49 @@ int rt_ivf_topk_batch(const void* queries, int64_t nq, const void* rows, int64_t
                       float* out_scores, int64_t* out_ids, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * IVF-SQ8, list-major batch search: rt_ivf_sq8_topk for batches in the
+ * thousands, with the work grouped as in rt_ivf_topk_batch.
+ *
+ * rt_ivf_sq8_topk_batch: the operands of rt_ivf_sq8_topk plus nlist-sized
+ *   grouping (the plan is rt_ivf_topk_batch_plan's, unchanged). For every
+ *   operand set rt_ivf_sq8_topk accepts, out_scores and out_ids are that
+ *   function's BIT FOR BIT, bias and exclude_bits NULL or not: the score is
+ *   the chain of the IVF-SQ8 section, computed by the fp32 MFMA from acc =
+ *   bias[q][p] + b0[q] (one accumulation chain per score, j ascending, only
+ *   k-steps inside d); the window clamping, the skipped probe entries, the
+ *   dropped row_pos and the result order are rt_ivf_topk_batch's. No 8-bit or
+ *   16-bit MFMA: which path serves a call never changes a result.
+ *   Work: a work item is (list, tile of 32 (query, probe slot) pairs naming
+ *   it, row chunk); its codes are staged as bytes and converted once for the
+ *   32 queries. Seven launches (fold, the four grouping launches, scan,
+ *   finish), stream-ordered, no host read; the grid depends on host arguments
+ *   only, so a captured call may be replayed after probes, queries, bias or
+ *   the codes changed in place. rt_ivf_topk_batch_tuning's stage mask applies
+ *   (the fold belongs to the grouping bit).
+ *   Limits: d % 16 == 0, RT_SQ8_MIN_D <= d <= RT_SQ8_MAX_D; 1 <= k <=
+ *   RT_IVF_MAX_K; 1 <= nprobe <= RT_IVF_MAX_NPROBE; nq x nprobe < 2^31 - 1;
+ *   nx < 2^31 - 1; nlist < 2^31 - 1; max_list_rows < 2^32 - 1; the plan's
+ *   blocks < 2^31 - 1.
+ *   Status, before any device work: RT_ERR_INVALID for a NULL operand (codes /
+ *   row_pos may be NULL when nx == 0; bias and exclude_bits are optional),
+ *   k <= 0, nprobe <= 0, nlist <= 0, d <= 0, a negative size, misaligned
+ *   queries / lo / step / codes / workspace (16 bytes) or bias (4 bytes),
+ *   exclude_words < ceil(nx / 32); RT_ERR_UNSUPPORTED for a limit above;
+ *   RT_ERR_WORKSPACE. nq == 0: RT_OK without a launch.
+ * rt_ivf_sq8_topk_batch_workspace_bytes: rt_ivf_topk_batch's partial lists and
+ *   tables (a multiple of 256), then per query the folded query: d floats of
+ *   qs and nprobe (rounded up to 4) floats of bias + b0; monotone in nq and in
+ *   d; 256 for a refused shape.
+ * ------------------------------------------------------------------------ */
+size_t rt_ivf_sq8_topk_batch_workspace_bytes(int64_t nq, int nprobe, int64_t nlist, int64_t max_list_rows, int k,
+                                             int d);
+int rt_ivf_sq8_topk_batch(const float* queries, int64_t nq, int d, const uint8_t* codes, int64_t nx, const float* lo,
+                          const float* step, const int64_t* list_offsets, int64_t nlist, const int32_t* row_pos,
+                          const int64_t* probes, const float* bias, int nprobe, int64_t max_list_rows, int k,
+                          const uint32_t* exclude_bits, int64_t exclude_words, float* out_scores, int64_t* out_ids,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Category filters: the request schema's filter_categories
  * (src/api/schemas.py:21-34), tested by the scan itself.
  *

@@ -7,7 +7,8 @@
 // tile come from the fp32 MFMA.
 //
 // Six launches, all sized by host arguments (no host read, stream-ordered,
-// capturable):
+// capturable). Launches 0-3, the work item of a scan block and everything
+// behind the score live in ivf_batch_group.h, shared with ivf_sq8_batch.hip:
 //
 // 0. ivfb_zero: the partial lists and the per-list counts are zeroed: a partial
 //    list that no work item writes (a skipped probe, a chunk past its list)
@@ -46,26 +47,15 @@
 //    scan.
 // 5. flatip_online_finish (topk_online.h, unchanged), one block per query over
 //    its nprobe x chunks <= 512 partial lists.
-#include "ivf_batch_plan.h"
-#include "topk_online.h"
+#include "ivf_batch_group.h"
 
 namespace rt {
 namespace topk {
 namespace ivfb {
 
-namespace on = rt::topk::online;
-
-constexpr int kThreads = 256;
-constexpr int kWaves = 4;
 constexpr int kKC = 32;             // d per LDS chunk
 constexpr int kLS = kKC + 4;        // row stride (floats): 144 B, conflict-free b128 fragment reads
 constexpr int kQS = 256 + 4;        // query stride (floats): the same bank pattern
-constexpr int kCap = 320;           // candidate buffer of one query
-constexpr int kRoom = kCap - kTileRows;
-static_assert(kTileRows == 32 * kWaves, "ivf batch: a wave scores one 32-row MFMA tile per step");
-static_assert(kRoom >= kMaxK, "ivf batch: a compaction must be able to keep the k best");
-static_assert(kMaxK <= v4::kFinishCap, "ivf batch: the block's list is sorted by the 128-entry register sort");
-static_assert(kMaxLists == on::kMaxBlocks && kMaxK == on::kMaxK, "ivf_batch_plan.h restates the finish's limits");
 
 struct Lds {
     static constexpr int kRows = 2 * kTileRows * kLS * 4;
@@ -76,88 +66,6 @@ struct Lds {
     // one block per CU; 1 KiB left for the block's small arrays and the barrier's reduction
     static_assert(kBytes + 1024 <= 163840, "ivf batch: the block's LDS");
 };
-
-// zero `bytes` (a multiple of 4) from an 8-byte aligned base: the partial lists and the counts
-__global__ __launch_bounds__(256) void ivfb_zero(uint64_t* __restrict__ base, size_t bytes) {
-    const size_t n8 = bytes / 8;
-    const size_t step = static_cast<size_t>(gridDim.x) * 256;
-    for (size_t i = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x; i < n8; i += step) base[i] = 0ull;
-    if ((bytes & 4) && blockIdx.x == 0 && threadIdx.x == 0) reinterpret_cast<uint32_t*>(base)[2 * n8] = 0u;
-}
-
-__global__ __launch_bounds__(256) void ivfb_count(const int64_t* __restrict__ probes, int64_t pairs, int64_t nlist,
-                                                  int32_t* __restrict__ count, int32_t* __restrict__ rank) {
-    const int64_t p = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
-    if (p >= pairs) return;
-    const int64_t l = probes[p];
-    rank[p] = (l >= 0 && l < nlist) ? atomicAdd(&count[l], 1) : -1;
-}
-
-// one block: thread t owns the lists [t seg, (t + 1) seg)
-__global__ __launch_bounds__(1024) void ivfb_offsets(const int32_t* __restrict__ count, int64_t nlist,
-                                                     int32_t* __restrict__ pair_start,
-                                                     int32_t* __restrict__ tile_start) {
-    __shared__ int sp[1024], st[1024];
-    const int t = threadIdx.x;
-    const int64_t seg = (nlist + 1023) / 1024;
-    const int64_t a = t * seg < nlist ? t * seg : nlist, b = (a + seg) < nlist ? (a + seg) : nlist;
-    int np = 0, nt = 0;
-    for (int64_t l = a; l < b; ++l) {
-        const int c = count[l];
-        np += c;
-        nt += (c + kQT - 1) / kQT;
-    }
-    sp[t] = np;
-    st[t] = nt;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        const int up = t >= o ? sp[t - o] : 0, ut = t >= o ? st[t - o] : 0;
-        __syncthreads();
-        sp[t] += up;
-        st[t] += ut;
-        __syncthreads();
-    }
-    int bp = sp[t] - np, bt = st[t] - nt;
-    for (int64_t l = a; l < b; ++l) {
-        const int c = count[l];
-        pair_start[l] = bp;
-        tile_start[l] = bt;
-        bp += c;
-        bt += (c + kQT - 1) / kQT;
-    }
-    if (t == 1023) {
-        pair_start[nlist] = sp[t];
-        tile_start[nlist] = st[t];
-    }
-}
-
-__global__ __launch_bounds__(256) void ivfb_scatter(const int64_t* __restrict__ probes, int64_t pairs, int64_t nlist,
-                                                    const int32_t* __restrict__ pair_start,
-                                                    const int32_t* __restrict__ rank, int32_t* __restrict__ out) {
-    const int64_t p = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
-    if (p >= pairs) return;
-    const int64_t l = probes[p];
-    const int r = rank[p];
-    // probes may change between two launches of a call only by the caller's error: the
-    // slot is tested all the same, so that nothing is written outside `out`
-    if (l >= 0 && l < nlist && r >= 0) {
-        const int64_t at = static_cast<int64_t>(pair_start[l]) + r;
-        if (at < pairs) out[at] = static_cast<int32_t>(p);
-    }
-}
-
-// wave: compact one candidate buffer; thr = the lowest score kept (ivf.hip)
-__device__ __forceinline__ void compact_keep_ties(Cand* buf, int& n, int k, int limit, uint32_t* hist, float& thr) {
-    const int lane = threadIdx.x & 63;
-    float unused = 0.f;
-    v4::compact_stream(buf, n, k, limit, hist, unused);
-    wave_lds_sync();
-    float lo = INFINITY;
-    for (int i = lane; i < n; i += 64) lo = fminf(lo, buf[i].s);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) lo = fminf(lo, __shfl_xor(lo, o, 64));
-    thr = lo;
-}
 
 template <typename T>
 __global__ __launch_bounds__(kThreads, 1) void ivfb_scan(
@@ -181,47 +89,11 @@ __global__ __launch_bounds__(kThreads, 1) void ivfb_scan(
     uint32_t* const hist = reinterpret_cast<uint32_t*>(lds + Lds::kRows + Lds::kQuery + Lds::kCand) + wave * 256;
 
     // ---- the work item: (list, query tile, chunk) ----
-    const int T_ = static_cast<int>(blockIdx.x / static_cast<unsigned>(chunks));
-    const int c = static_cast<int>(blockIdx.x - static_cast<unsigned>(T_) * static_cast<unsigned>(chunks));
-    if (T_ >= tile_start[nlist]) return;  // block-uniform: a surplus block of the host bound
-    int64_t l;
-    {
-        int64_t lo = 0, hi = nlist - 1;  // the first list with tile_start[l + 1] > T_ (one exists)
-        while (lo < hi) {
-            const int64_t mid = lo + ((hi - lo) >> 1);
-            if (tile_start[mid + 1] > T_) hi = mid;
-            else lo = mid + 1;
-        }
-        l = lo;
-    }
-    // The tables are this call's own (ivfb_offsets), and consistent ones give 0 <= p0 < p1 <=
-    // n_pairs; the block tests it all the same (in 64 bits), and every pair id below, so that no
-    // table contents can take a read outside `pairs` or a write outside the partial lists.
-    const int64_t p0 = pair_start[l] + (static_cast<int64_t>(T_) - tile_start[l]) * kQT;
-    int64_t p1 = pair_start[l + 1];
-    p1 = p1 < n_pairs ? p1 : n_pairs;
-    if (p0 < 0 || p0 >= p1) return;  // block-uniform
-    const int nqt = (p1 - p0) < kQT ? static_cast<int>(p1 - p0) : kQT;
-
-    // the chunk, clamped to the list and to the corpus (ivf_scan's window)
-    int64_t row_begin = 0, row_end = 0;
-    {
-        int64_t lo = list_offsets[l], hi = list_offsets[l + 1];
-        lo = lo < 0 ? 0 : lo;
-        hi = hi > nx ? nx : hi;
-        if (list_len && lo < hi) {  // lists with slack: the first list_len[l] rows of the capacity
-            const int64_t live = list_len[l];
-            hi = live <= 0 ? lo : (live < hi - lo ? lo + live : hi);
-        }
-        if (lo < hi) {
-            const int64_t len = hi - lo, first = static_cast<int64_t>(c) * rows_per_chunk;
-            if (first < len) {
-                row_begin = lo + first;
-                row_end = (first + rows_per_chunk) < len ? (row_begin + rows_per_chunk) : hi;
-            }
-        }
-    }
-    if (row_end <= row_begin) return;  // block-uniform: the partial lists were zeroed
+    Item w;
+    if (!work_item(pair_start, tile_start, n_pairs, chunks, list_offsets, nlist, list_len, nx, rows_per_chunk, w))
+        return;  // block-uniform
+    const int nqt = w.nqt;
+    const int64_t row_begin = w.row_begin, row_end = w.row_end;
 
     const int64_t row_bytes = static_cast<int64_t>(d) * static_cast<int64_t>(sizeof(T));
     const int nchunks = (d + kKC - 1) / kKC;
@@ -263,16 +135,7 @@ __global__ __launch_bounds__(kThreads, 1) void ivfb_scan(
     };
 
     load(0, 0);
-    if (tid < kQT) {
-        int pid = -1;
-        if (tid < nqt) pid = pairs[p0 + tid];
-        const bool ok = pid >= 0 && pid < n_pairs;
-        const int q = ok ? pid / nprobe : -1;  // -1: no query in this slot of the tile
-        qid[tid] = q;
-        qslot[tid] = ok ? pid - q * nprobe : 0;
-        cnt[tid] = 0;
-        thr[tid] = -INFINITY;
-    }
+    tile_slots(w, pairs, n_pairs, nprobe, qid, qslot, cnt, thr);
     __syncthreads();
     // the tile's queries as fp32, in the rows' chunk layout; padding queries and columns: zeros
     {
@@ -331,44 +194,11 @@ __global__ __launch_bounds__(kThreads, 1) void ivfb_scan(
             // a position outside [0, n_pos) (a corrupt row_pos, an empty slot of a list with
             // slack) is dropped: it has no bit in the bitmap and no row in the caller's corpus
             const bool valid = row < row_end && pos >= 0 && static_cast<int64_t>(pos) < n_pos;
-            int mine_over = 0;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int qi = tile_row(r, half);
-                bool pass = valid && qid[qi] >= 0 && acc[r] >= thr[qi];
-                if (excl && pass)
-                    pass = ((excl[static_cast<int64_t>(qid[qi]) * excl_words + (pos >> 5)] >> (pos & 31)) & 1u) == 0u;
-                const uint64_t bm = __ballot(pass);
-                if (bm) {  // wave-uniform
-                    // one LDS atomic per lane half: the halves hold different queries
-                    const uint32_t mine = half ? static_cast<uint32_t>(bm >> 32) : static_cast<uint32_t>(bm);
-                    const int n_mine = __popc(mine);
-                    int base = 0;
-                    if (col == 0 && n_mine) base = atomicAdd(&cnt[qi], n_mine);
-                    base = __shfl(base, half * 32, 64);
-                    const int at = base + __popc(mine & ((1u << col) - 1u));
-                    // guarded: a row_pos that repeats positions gives equal keys, of which a
-                    // compaction may keep more than its limit
-                    if (pass && at < kCap) cand[qi * kCap + at] = Cand{acc[r], static_cast<uint32_t>(pos)};
-                    mine_over |= (base + n_mine) > kRoom ? 1 : 0;
-                }
-            }
+            const int mine_over = select_tile(acc, valid, pos, qid, thr, cnt, cand, excl, excl_words);
             acc = f32x16{};
             over = __syncthreads_or(mine_over);
             if (over && more) {
-                for (int qi = wave; qi < nqt; qi += kWaves) {
-                    int n = cnt[qi] < kCap ? cnt[qi] : kCap;
-                    if (n > kRoom) {
-                        float th = thr[qi];
-                        // down to the finish's 128, not to kRoom: a buffer left near kRoom
-                        // passes the check again after the next tile's first appends
-                        compact_keep_ties(cand + qi * kCap, n, k, v4::kFinishCap, hist, th);
-                        if (lane == 0) {
-                            cnt[qi] = n;
-                            thr[qi] = th;
-                        }
-                    }
-                }
+                compact_tile_buffers(nqt, k, cnt, thr, cand, hist);
                 __syncthreads();
             }
         }
@@ -376,14 +206,7 @@ __global__ __launch_bounds__(kThreads, 1) void ivfb_scan(
         cc = ncc;
     }
 
-    // ---- the block's list per query: partials[query][rank][slot x chunks + c] ----
-    const int lists = nprobe * chunks;
-    for (int qi = wave; qi < nqt; qi += kWaves) {
-        if (qid[qi] < 0) continue;  // wave-uniform
-        const int n = cnt[qi] < kCap ? cnt[qi] : kCap;
-        on::write_block_list(cand + qi * kCap, n, k, hist,
-                             partials + static_cast<int64_t>(qid[qi]) * k * lists + qslot[qi] * chunks + c, lists);
-    }
+    write_tile_lists(w, k, nprobe, chunks, qid, qslot, cnt, cand, hist, partials);
 }
 
 }  // namespace ivfb
@@ -398,6 +221,7 @@ static_assert(RT_IVF_MAX_NPROBE == ib::kMaxProbe && RT_IVF_MAX_K == ib::kMaxK, "
 
 // measurements only: which of {grouping, scan, finish} a call issues (0 = all)
 static int g_ivfb_stages = 7;
+int rt::topk::ivfb::stages() { return g_ivfb_stages; }
 
 extern "C" int rt_ivf_topk_batch_tuning(int stages) {
     if (stages < 0 || stages > 7) return RT_ERR_INVALID;
@@ -449,33 +273,12 @@ extern "C" int rt_ivf_topk_batch(const void* queries, int64_t nq, const void* ro
 
     hipStream_t st = as_stream(stream);
     const int64_t pairs = nq * nprobe;
-    const size_t pbytes = ib::partial_bytes(nq, nprobe, k, p);
-    uint64_t* const partials = static_cast<uint64_t*>(workspace);
-    int32_t* const count = reinterpret_cast<int32_t*>(static_cast<char*>(workspace) + pbytes);
-    int32_t* const pair_start = count + nlist;
-    int32_t* const tile_start = pair_start + nlist + 1;
-    int32_t* const rank = tile_start + nlist + 1;
-    int32_t* const pair_of = rank + pairs;
+    const ib::Tables t = ib::carve(workspace, nq, nprobe, nlist, k, p);
+    uint64_t* const partials = t.partials;
     const int stages = g_ivfb_stages;
     int rc = RT_OK;
     if (stages & 1) {
-        // the partial lists and the counts lie side by side: one fill launch
-        const size_t zbytes = pbytes + static_cast<size_t>(nlist) * 4;
-        const size_t zblocks = (zbytes / 8 + 2047) / 2048;  // 8 words per thread, at most
-        hipLaunchKernelGGL(ib::ivfb_zero, dim3(static_cast<unsigned>(zblocks < 1 ? 1 : (zblocks > 4096 ? 4096 : zblocks))),
-                           dim3(256), 0, st, partials, zbytes);
-        rc = check_launch("ivfb_zero");
-        if (rc) return rc;
-        const unsigned pblocks = static_cast<unsigned>((pairs + 255) / 256);
-        hipLaunchKernelGGL(ib::ivfb_count, dim3(pblocks), dim3(256), 0, st, probes, pairs, nlist, count, rank);
-        rc = check_launch("ivfb_count");
-        if (rc) return rc;
-        hipLaunchKernelGGL(ib::ivfb_offsets, dim3(1), dim3(1024), 0, st, count, nlist, pair_start, tile_start);
-        rc = check_launch("ivfb_offsets");
-        if (rc) return rc;
-        hipLaunchKernelGGL(ib::ivfb_scatter, dim3(pblocks), dim3(256), 0, st, probes, pairs, nlist, pair_start, rank,
-                           pair_of);
-        rc = check_launch("ivfb_scatter");
+        rc = ib::launch_grouping(t, probes, pairs, nlist, st);
         if (rc) return rc;
     }
     if (!(stages & 6)) return RT_OK;
@@ -485,7 +288,7 @@ extern "C" int rt_ivf_topk_batch(const void* queries, int64_t nq, const void* ro
 #define RT_IVFB_LAUNCH(T)                                                                                          \
     hipLaunchKernelGGL((ib::ivfb_scan<T>), grid, block, 0, st, static_cast<const T*>(queries), x, nx, d, k,        \
                        list_offsets, nlist, list_len, n_pos, row_pos, nprobe, p.chunks, p.rows_per_chunk,          \
-                       exclude_bits, exclude_words, partials, pair_start, tile_start, pair_of,                     \
+                       exclude_bits, exclude_words, partials, t.pair_start, t.tile_start, t.pair_of,               \
                        static_cast<int>(pairs))
     switch (dtype) {
         case RT_F32: RT_IVFB_LAUNCH(float); break;

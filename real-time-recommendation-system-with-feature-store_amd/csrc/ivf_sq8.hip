@@ -35,6 +35,7 @@
 //    LDS is the online scan's Lds<1> (45,568 B): three blocks per CU.
 // 3. flatip_online_finish (topk_online.h, unchanged).
 #include "ivf_select.h"
+#include "ivf_sq8_fold.h"
 
 namespace rt {
 namespace topk {
@@ -42,13 +43,6 @@ namespace ivfsq8 {
 
 namespace on = rt::topk::online;
 namespace iv = rt::topk::ivf;
-
-constexpr int kMinD = 16, kMaxD = 256;  // whole 16-byte units of codes; the query's LDS
-
-inline bool d_ok(int d) { return d >= kMinD && d <= kMaxD && (d & 15) == 0; }
-inline size_t align256(size_t b) { return (b + 255) & ~static_cast<size_t>(255); }
-// floats of one query's fold: qs[d], then base[nprobe] padded to a float4
-inline int fold_stride(int d, int nprobe) { return d + ((nprobe + 3) & ~3); }
 
 // ---- rt_sq8_encode ----
 constexpr int kEncThreads = 256;
@@ -123,6 +117,13 @@ __global__ __launch_bounds__(kFoldThreads) void sq8_fold(const float* __restrict
     }
     __syncthreads();
     if (t < nprobe) out[d + t] = bias ? bias[static_cast<int64_t>(q) * nprobe + t] + b0 : b0;
+}
+
+int launch_fold(const float* queries, int64_t nq, int d, const float* lo, const float* step, const float* bias,
+                int nprobe, int stride, float* fold, hipStream_t st) {
+    hipLaunchKernelGGL(sq8_fold, dim3(static_cast<unsigned>(nq)), dim3(kFoldThreads), 0, st, queries, d, lo, step,
+                       bias, nprobe, stride, fold);
+    return check_launch("sq8_fold");
 }
 
 // ---- the scan ----
@@ -322,9 +323,7 @@ extern "C" int rt_ivf_sq8_topk(const float* queries, int64_t nq, int d, const ui
     float* fold = reinterpret_cast<float*>(static_cast<char*>(workspace) +
                                            sq::align256(rt_ivf_topk_workspace_bytes(nq, nprobe, max_list_rows, k)));
 
-    hipLaunchKernelGGL(sq::sq8_fold, dim3(static_cast<unsigned>(nq)), dim3(sq::kFoldThreads), 0, st, queries, d, lo,
-                       step, bias, nprobe, stride, fold);
-    int rc = check_launch("sq8_fold");
+    int rc = sq::launch_fold(queries, nq, d, lo, step, bias, nprobe, stride, fold, st);
     if (rc) return rc;
     hipLaunchKernelGGL(sq::ivf_sq8_scan, dim3(static_cast<unsigned>(lists), static_cast<unsigned>(nq)),
                        dim3(sqon::kThreads), 0, st, fold, stride, reinterpret_cast<const char*>(codes), nx, d, k,

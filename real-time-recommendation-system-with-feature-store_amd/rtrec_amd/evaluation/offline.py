@@ -52,8 +52,10 @@ def build_eval_index(item_emb: torch.Tensor, index_config: Dict[str, Any]):
     ``nprobe``, ``storage_dtype`` ...). ``metric`` is forced to
     ``"inner_product"``, so scores stay the towers' dot products, and
     ``batch_min_queries`` defaults to 1: an evaluation searches thousands of
-    users in one call, the shape the list-major scan is for. Positions are the
-    item ids."""
+    users in one call, the shape the list-major scan is for
+    (``sq8_batch_min_queries`` for ``"hip_ivf_sq8"``; neither for
+    ``"hip_ivf_pq"``, which has no list-major scan). Positions are the item
+    ids."""
     from ..serving import retrieval
     cfg = dict(index_config)
     index_type = cfg.pop("index_type", "hip_ivf")
@@ -61,7 +63,10 @@ def build_eval_index(item_emb: torch.Tensor, index_config: Dict[str, Any]):
     if cls is None or not hasattr(cls, "search_tensors"):
         raise ValueError(f"index_type={index_type!r}: not a registered device index "
                          f"(one of {sorted(n for n, c in retrieval._INDEX_TYPES.items() if hasattr(c, 'search_tensors'))})")
-    cfg.setdefault("batch_min_queries", 1)
+    # a registered plugin class without the method keeps the key every class got before
+    key = cls.batch_scan_key() if hasattr(cls, "batch_scan_key") else "batch_min_queries"
+    if key is not None:   # HipIVFSQ8Index: its own key; HipIVFPQIndex: no list-major scan, no key
+        cfg.setdefault(key, 1)
     cfg["metric"] = "inner_product"
     cfg["dimension"] = int(item_emb.shape[1])
     index = cls(cfg)

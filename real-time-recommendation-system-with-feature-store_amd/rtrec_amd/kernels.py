@@ -962,32 +962,22 @@ def sq8_encode(rows: torch.Tensor, lo: torch.Tensor, inv_step: torch.Tensor,
     return out
 
 
-def ivf_sq8_topk(queries: torch.Tensor, codes: torch.Tensor, lo: torch.Tensor, step: torch.Tensor,
-                 list_offsets: torch.Tensor, row_pos: torch.Tensor, probes: torch.Tensor, max_list_rows: int, k: int,
-                 bias: Optional[torch.Tensor] = None, exclude_bits: Optional[torch.Tensor] = None,
-                 out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
-                 workspace_buf: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Top-k over the probed lists of a scalar-quantised corpus (rt_ivf_sq8_topk):
-    the operands and the result contract of :func:`ivf_topk` with the rows
-    replaced by ``codes`` uint8 [nx, d] (list-contiguous) and the quantiser ``lo``,
-    ``step`` (fp32 [d]); ``queries`` fp32 [nq, d]. A row's score is ``bias[q, p]``
-    (fp32 [nq, nprobe], None = 0: for residual codes the coarse search's scores)
-    plus the query's inner product with the decoded row ``lo + (code + 0.5) step``,
-    in the order of include/rtrec_hip.h. Batches above 32,768 queries run in chunks."""
-    native.require_device(queries, codes, lo, step, list_offsets, row_pos, probes, bias, exclude_bits,
-                          what="ivf_sq8_topk")
+def _sq8_scan_shapes(what: str, queries, codes, lo, step, list_offsets, row_pos, probes, k, bias, exclude_bits
+                     ) -> Tuple[int, int, int, int, int]:
+    """The operand checks the two SQ8 scans share -> (nq, d, nx, nprobe, nlist)."""
+    native.require_device(queries, codes, lo, step, list_offsets, row_pos, probes, bias, exclude_bits, what=what)
     if queries.dim() != 2 or queries.dtype != torch.float32:
-        raise ValueError("ivf_sq8_topk expects fp32 [nq, d] queries")
+        raise ValueError(f"{what} expects fp32 [nq, d] queries")
     nq, d = queries.shape
     if codes.dtype != torch.uint8 or codes.dim() != 2 or codes.shape[1] != d:
         raise ValueError(f"codes must be uint8 [nx, {d}]")
     nx = codes.shape[0]
-    _sq8_params(d, "ivf_sq8_topk", lo=lo, step=step)
+    _sq8_params(d, what, lo=lo, step=step)
     if not 1 <= k <= IVF_MAX_K:
-        raise ValueError(f"k={k}: ivf_sq8_topk returns 1..{IVF_MAX_K} results per query")
+        raise ValueError(f"k={k}: {what} returns 1..{IVF_MAX_K} results per query")
     if not (queries.is_contiguous() and codes.is_contiguous() and probes.is_contiguous()
             and list_offsets.is_contiguous() and row_pos.is_contiguous()):
-        raise ValueError("ivf_sq8_topk expects contiguous operands")
+        raise ValueError(f"{what} expects contiguous operands")
     if list_offsets.dtype != torch.int64 or list_offsets.dim() != 1 or list_offsets.numel() < 2:
         raise ValueError("list_offsets must be int64 [nlist + 1]")
     if row_pos.dtype != torch.int32 or row_pos.numel() != nx:
@@ -1000,7 +990,23 @@ def ivf_sq8_topk(queries: torch.Tensor, codes: torch.Tensor, lo: torch.Tensor, s
     if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (nq, nprobe)
                              or not bias.is_contiguous()):
         raise ValueError(f"bias must be contiguous fp32 [{nq}, {nprobe}]")
-    nlist = list_offsets.numel() - 1
+    return nq, d, nx, nprobe, list_offsets.numel() - 1
+
+
+def ivf_sq8_topk(queries: torch.Tensor, codes: torch.Tensor, lo: torch.Tensor, step: torch.Tensor,
+                 list_offsets: torch.Tensor, row_pos: torch.Tensor, probes: torch.Tensor, max_list_rows: int, k: int,
+                 bias: Optional[torch.Tensor] = None, exclude_bits: Optional[torch.Tensor] = None,
+                 out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                 workspace_buf: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Top-k over the probed lists of a scalar-quantised corpus (rt_ivf_sq8_topk):
+    the operands and the result contract of :func:`ivf_topk` with the rows
+    replaced by ``codes`` uint8 [nx, d] (list-contiguous) and the quantiser ``lo``,
+    ``step`` (fp32 [d]); ``queries`` fp32 [nq, d]. A row's score is ``bias[q, p]``
+    (fp32 [nq, nprobe], None = 0: for residual codes the coarse search's scores)
+    plus the query's inner product with the decoded row ``lo + (code + 0.5) step``,
+    in the order of include/rtrec_hip.h. Batches above 32,768 queries run in chunks."""
+    nq, d, nx, nprobe, nlist = _sq8_scan_shapes("ivf_sq8_topk", queries, codes, lo, step, list_offsets, row_pos,
+                                                probes, k, bias, exclude_bits)
     scores, ids = _topk_out(out, nq, k, queries.device)
     words = _exclude_words(exclude_bits, nq, True)
     for a in range(0, nq, IVF_QUERY_CHUNK):
@@ -1041,10 +1047,16 @@ def ivf_topk_batch_tuning(stages: int = 0) -> None:
     call("rt_ivf_topk_batch_tuning", int(stages))
 
 
-def _ivf_batch_query_chunk(nq: int, nprobe: int, nlist: int, max_list_rows: int, k: int) -> int:
+def _ivf_batch_query_chunk(nq: int, nprobe: int, nlist: int, max_list_rows: int, k: int, d: Optional[int] = None
+                           ) -> int:
     """Largest number of queries whose workspace fits IVF_BATCH_WORKSPACE_BUDGET
-    (at least one tile of 32; the workspace is monotone in nq)."""
-    size = native.lib().rt_ivf_topk_batch_workspace_bytes
+    (at least one tile of 32; the workspace is monotone in nq). ``d``: the SQ8
+    batch scan's workspace, which also holds the folded queries."""
+    if d is None:
+        size = native.lib().rt_ivf_topk_batch_workspace_bytes
+    else:
+        def size(*shape):
+            return native.lib().rt_ivf_sq8_topk_batch_workspace_bytes(*shape, d)
     if size(nq, nprobe, nlist, max_list_rows, k) <= IVF_BATCH_WORKSPACE_BUDGET:
         return nq
     lo, hi = 1, max(1, nq // 32)   # in tiles: lo always runs, hi does not fit
@@ -1124,6 +1136,42 @@ def ivf_topk_batch(queries: torch.Tensor, rows: torch.Tensor, list_offsets: torc
              int(n_pos) if list_len is not None else nx, ptr(row_pos) if nx else None, ptr(probes[a:b]), nprobe,
              mlr, k, ptr(exclude_bits[a:b]) if exclude_bits is not None else None, words,
              ptr(scores[a:b]), ptr(ids[a:b]), ptr(ws), ws.numel(), stream_of(queries))
+    return scores, ids
+
+
+def ivf_sq8_topk_batch(queries: torch.Tensor, codes: torch.Tensor, lo: torch.Tensor, step: torch.Tensor,
+                       list_offsets: torch.Tensor, row_pos: torch.Tensor, probes: torch.Tensor, max_list_rows: int,
+                       k: int, bias: Optional[torch.Tensor] = None, exclude_bits: Optional[torch.Tensor] = None,
+                       out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                       workspace_buf: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """:func:`ivf_sq8_topk` for large batches (rt_ivf_sq8_topk_batch): the same
+    operands and, bit for bit, the same result, with the work grouped by LIST as
+    in :func:`ivf_topk_batch` — a block stages a chunk of a list's codes once, as
+    bytes, for a tile of 32 queries that probe it, and scores them on the fp32
+    MFMA. Queries run in chunks whose workspace stays within
+    ``IVF_BATCH_WORKSPACE_BUDGET``; a ``workspace_buf`` must hold one whole
+    call's workspace (``rt_ivf_sq8_topk_batch_workspace_bytes``)."""
+    nq, d, nx, nprobe, nlist = _sq8_scan_shapes("ivf_sq8_topk_batch", queries, codes, lo, step, list_offsets,
+                                                row_pos, probes, k, bias, exclude_bits)
+    scores, ids = _topk_out(out, nq, k, queries.device)
+    words = _exclude_words(exclude_bits, nq, True)
+    mlr = int(max_list_rows)
+    if workspace_buf is not None:
+        chunk = nq
+    else:
+        chunk = _ivf_batch_query_chunk(nq, nprobe, nlist, mlr, k, d) if nq else 0
+    for a in range(0, nq, max(chunk, 1)):
+        b = min(nq, a + chunk)
+        ws = workspace_buf
+        if ws is None:
+            ws = workspace(queries.device,
+                           native.lib().rt_ivf_sq8_topk_batch_workspace_bytes(b - a, nprobe, nlist, mlr, k, d),
+                           "ivf_sq8_topk_batch")
+        call("rt_ivf_sq8_topk_batch", ptr(queries[a:b]), b - a, d, ptr(codes) if nx else None, nx, ptr(lo),
+             ptr(step), ptr(list_offsets), nlist, ptr(row_pos) if nx else None, ptr(probes[a:b]),
+             ptr(bias[a:b]) if bias is not None else None, nprobe, mlr, k,
+             ptr(exclude_bits[a:b]) if exclude_bits is not None else None, words, ptr(scores[a:b]), ptr(ids[a:b]),
+             ptr(ws), ws.numel(), stream_of(queries))
     return scores, ids
 
 

@@ -166,6 +166,9 @@ SIGNATURES = {
     "rt_ivf_sq8_topk_workspace_bytes": (c_size, [c_i64, c_int, c_i64, c_int, c_int]),
     "rt_ivf_sq8_topk": (c_int, [vp, c_i64, c_int, vp, c_i64, vp, vp, vp, c_i64, vp, vp, vp, c_int, c_i64, c_int,
                                 vp, c_i64, vp, vp, vp, c_size, vp]),
+    "rt_ivf_sq8_topk_batch_workspace_bytes": (c_size, [c_i64, c_int, c_i64, c_i64, c_int, c_int]),
+    "rt_ivf_sq8_topk_batch": (c_int, [vp, c_i64, c_int, vp, c_i64, vp, vp, vp, c_i64, vp, vp, vp, c_int, c_i64,
+                                      c_int, vp, c_i64, vp, vp, vp, c_size, vp]),
     "rt_ivf_lists_update_workspace_bytes": (c_size, [c_i64, c_i64]),
     "rt_ivf_lists_update": (c_int, [vp, c_i64, c_int, c_int, vp, c_i64, vp, vp, vp, vp, vp, vp, vp, c_i64, vp, vp,
                                     c_size, vp]),

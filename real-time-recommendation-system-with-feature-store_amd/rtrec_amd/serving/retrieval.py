@@ -100,6 +100,13 @@ class _HbmIndex(IndexBase):
     # scan); otherwise a call with ``exclude_ids`` goes to the bitmap path
     _searcher_takes_exclude = False
 
+    @classmethod
+    def batch_scan_key(cls) -> Optional[str]:
+        """The config key (a smallest query count) an evaluation sets to 1, because it searches
+        thousands of users in one call: the class's list-major batch scan where it has one and
+        an ignored key where it scans exactly; None for a class that refuses every such key."""
+        return "batch_min_queries"
+
     def __init__(self, config: Dict[str, Any]):
         self.config = config
         self.dimension = config.get("dimension", 128)
@@ -2345,15 +2352,34 @@ class _IVFCodesIndex(HipIVFFlatIndex):
 
     _searcher_takes_exclude = False
 
+    @classmethod
+    def batch_scan_key(cls) -> Optional[str]:
+        return None   # no list-major scan over codes, but for HipIVFSQ8Index
+
     def __init__(self, config: Optional[Dict[str, Any]] = None):
         cfg = dict(config or {})
         name = type(self).__name__
         if cfg.get("online_max_batch"):
             raise ValueError(f"{name} has no resident searcher (online_max_batch): HipIVFFlatIndex has")
         if cfg.get("batch_min_queries") is not None:
+            if self.batch_scan_key() is not None:
+                raise ValueError(f"{name}: its list-major scan is keyed sq8_batch_min_queries; batch_min_queries "
+                                 "is HipIVFFlatIndex's")
             raise ValueError(f"{name} has no list-major batch scan (batch_min_queries): HipIVFFlatIndex has")
+        v = cfg.get("sq8_batch_min_queries")
+        if v is not None and self.batch_scan_key() is None:
+            raise ValueError(f"{name} has no list-major batch scan (sq8_batch_min_queries): HipIVFSQ8Index has")
         super().__init__(cfg)
         self.by_residual = bool(self.config.get("by_residual", True))
+        self._init_sq8_batch()
+
+    def _init_sq8_batch(self):
+        """The ``sq8_batch_min_queries`` option: None (off) or the smallest batch that takes
+        the list-major scan over the codes."""
+        v = self.config.get("sq8_batch_min_queries")
+        self.sq8_batch_min_queries = None if v is None else int(v)
+        if self.sq8_batch_min_queries is not None and self.sq8_batch_min_queries < 1:
+            raise ValueError(f"sq8_batch_min_queries={self.sq8_batch_min_queries}: None (off) or >= 1")
 
     @property
     def codes(self) -> Optional[torch.Tensor]:
@@ -2673,11 +2699,18 @@ class HipIVFSQ8Index(_IVFCodesIndex):
     ``device``, ``categories``; ``index_factory`` (``"IVF<nlist>,SQ8"``, default
     ``"IVF1024,SQ8"``); ``by_residual`` (True). ``storage_dtype`` only reaches the
     Flat fallback (below 1,024 items or nlist, as on the parent).
+    ``sq8_batch_min_queries`` (default ``None`` = off; an integer >= 1): calls of
+    that many queries take the list-major scan (``rt_ivf_sq8_topk_batch``: a list's
+    codes are staged once, as bytes, for a tile of 32 queries that probe it, and
+    scored on the fp32 MFMA) — the same results, bit for bit; smaller calls keep
+    ``rt_ivf_sq8_topk``. Saved and loaded with the index; the Flat fallback
+    ignores it. DESIGN.md §5 "IVF-SQ8 batch search" has the measured table.
 
     ``add`` encodes against the existing range — a value outside it clamps to the
     first or last bin, nothing is trained again. Not served here — each raises and
     names the class that has it: the MMR re-rank, ``online_max_batch`` /
-    ``online_searcher`` and ``batch_min_queries`` (:class:`HipIVFFlatIndex`);
+    ``online_searcher`` and ``batch_min_queries`` (:class:`HipIVFFlatIndex`; this
+    class's list-major scan is keyed ``sq8_batch_min_queries``);
     ``update`` / ``remove`` / ``mutable`` (:class:`HipMutableIVFFlatIndex`).
 
     ``vectors()`` returns the RECONSTRUCTION in original order, within half a step
@@ -2686,6 +2719,10 @@ class HipIVFSQ8Index(_IVFCodesIndex):
     ``<path>.pkl``, and a loaded index answers bit-identically."""
 
     _default_factory = _IVF_SQ8_FACTORY
+
+    @classmethod
+    def batch_scan_key(cls) -> Optional[str]:
+        return "sq8_batch_min_queries"
 
     def __init__(self, config: Optional[Dict[str, Any]] = None):
         super().__init__(config)
@@ -2718,8 +2755,12 @@ class HipIVFSQ8Index(_IVFCodesIndex):
         return kernels.sq8_encode(rows, self.lo, self.inv_step)
 
     def _scan_codes(self, q32, probes, k, bias, exclude_bits):
-        return kernels.ivf_sq8_topk(q32, self.index, self.lo, self.step, self.list_offsets, self.row_pos, probes,
-                                    self.max_list_rows, k, bias=bias, exclude_bits=exclude_bits)
+        # a batch of sq8_batch_min_queries or more: one pass over a list's codes for a tile of
+        # queries that probe it (rt_ivf_sq8_topk_batch); the same results, bit for bit
+        batch = self.sq8_batch_min_queries is not None and q32.shape[0] >= self.sq8_batch_min_queries
+        scan = kernels.ivf_sq8_topk_batch if batch else kernels.ivf_sq8_topk
+        return scan(q32, self.index, self.lo, self.step, self.list_offsets, self.row_pos, probes,
+                    self.max_list_rows, k, bias=bias, exclude_bits=exclude_bits)
 
     def build(self, embeddings: Array, ids: List[str], item_categories=None):
         """As :meth:`HipIVFFlatIndex.build`, then the range and the codes."""
@@ -2794,6 +2835,7 @@ class HipIVFSQ8Index(_IVFCodesIndex):
         self._flat = None
         self.config = dict(data.get("config", self.config))
         self.metric = self.config.get("metric", self.metric)
+        self._init_sq8_batch()
         self.dimension = int(centroids.shape[1])
         self.index_factory = f"IVF{self.nlist},SQ8"
         dev = self._dev()

@@ -83,6 +83,16 @@ third side, next to ``hip_ivf`` float16 and ``hip_ivf_pq`` at M = 16: the scalar
 index on the same corpus, nlist and probes; additionally the ratio of its p50 to IVF-Flat
 float16's from the same alternating run. No bar.
 
+``--legs sq8batch`` (not in the default list): the list-major SQ8 scan
+(rt_ivf_sq8_topk_batch, the ``sq8_batch_min_queries`` key) on the same corpus, nlist
+1024, nprobe 20, k in {10, 100}, nq in {256, 1024, 4096}. Arm A is ``hip_ivf_sq8`` with the
+key off, arm B the same index with the key at 1, arm C ``hip_ivf`` float16 with
+``batch_min_queries = 1``; the whole ``search_tensors`` calls alternate call by call, 3
+rounds with each arm first once. A and B must agree bit for bit at every shape. Per shape:
+the p50 per round and arm, and the hipEvent p50 of B's scan call whole and split into fold
++ grouping / scan / finish (rt_ivf_topk_batch_tuning), next to A's scan call. The bar, at
+nq = 4096: B's p50 in every round is below the MINIMUM of A's p50 over its rounds.
+
 Prints one JSON line per case and a closing summary line; run it under a time
 limit, e.g. ``timeout 900 python tools/ivf_latency.py > profiles/ivf_latency.txt``.
 """
@@ -542,6 +552,73 @@ def leg_pq(args, rows, dev, leg="pq"):
     return out
 
 
+def leg_sq8batch(args, rows, dev):
+    """The sq8batch leg: one JSON line per (k, nq). ``rows``: fp32 unit rows on the device."""
+    n, d, nprobe = rows.shape[0], rows.shape[1], 20
+    nqs = [int(x) for x in args.sq8batch_nq.split(",")]
+    queries = torch.from_numpy(corpus(n, d, 4096, max(nqs), dev)[1]).to(dev)   # the same rows, more queries
+    base = {"dimension": d, "metric": "cosine", "nprobe": nprobe, "train_iters": args.train_iters}
+    sq8 = HipIVFSQ8Index({**base, "index_factory": f"IVF{args.nlist},SQ8"})
+    sq8.build(rows, [])
+    f16 = HipIVFFlatIndex({**base, "index_factory": f"IVF{args.nlist},Flat", "storage_dtype": "float16",
+                           "batch_min_queries": 1})
+    f16.build(rows, [])
+    torch.cuda.synchronize()
+    out = []
+    for k, nq in ((k, nq) for k in (10, 100) for nq in nqs):
+        q = queries[:nq].contiguous()
+        calls = max(3, min(args.batch_calls, 20480 // nq))
+
+        def run(ix, key):
+            def f():
+                sq8.sq8_batch_min_queries = key
+                r = ix.search_tensors(q, k)
+                torch.cuda.synchronize()
+                return r
+            return f
+
+        sides = {"A_sq8_per_query": run(sq8, None), "B_sq8_batch": run(sq8, 1), "C_ivf_f16_batch": run(f16, None)}
+        a, b = sides["A_sq8_per_query"](), sides["B_sq8_batch"]()
+        if not (torch.equal(a[1], b[1]) and torch.equal(a[0].view(torch.int32), b[0].view(torch.int32))):
+            raise SystemExit(f"sq8batch leg k={k} nq={nq}: the per-query path and the batch path differ")
+        names, rounds = list(sides), []
+        for r in range(3):
+            order = names[r:] + names[:r]
+            rounds.append({"first": order[0], **timed_alternating({nm: sides[nm] for nm in order}, calls, 2)})
+        floor = min(r["A_sq8_per_query"]["p50_ms"] for r in rounds)
+        # B's launches alone, on prepared device operands: a whole call fills the workspace, then each
+        # stage is issued alone over it (the fold belongs to the grouping bit)
+        q32 = sq8._prepare(q)
+        coarse, probes = sq8.coarse_search(q32, nprobe)
+        ws = torch.empty(kernels.native.lib().rt_ivf_sq8_topk_batch_workspace_bytes(
+            nq, nprobe, sq8.nlist, sq8.max_list_rows, k, d), dtype=torch.uint8, device=dev)
+        res = (torch.empty((nq, k), dtype=torch.float32, device=dev), torch.empty((nq, k), dtype=torch.int64, device=dev))
+        ops = (q32, sq8.index, sq8.lo, sq8.step, sq8.list_offsets, sq8.row_pos, probes, sq8.max_list_rows, k)
+        scan = lambda: kernels.ivf_sq8_topk_batch(*ops, bias=coarse, out=res, workspace_buf=ws)  # noqa: E731
+        scan()
+        ev = {"whole": event_timed({"s": scan}, calls, 2)["s"]}
+        try:
+            for name, stages in (("fold_and_grouping", 1), ("scan", 2), ("finish", 4)):
+                kernels.ivf_topk_batch_tuning(stages)
+                ev[name] = event_timed({"s": scan}, calls, 2)["s"]
+        finally:
+            kernels.ivf_topk_batch_tuning(0)
+        ev["per_query_whole"] = event_timed({"s": lambda: kernels.ivf_sq8_topk(*ops, bias=coarse, out=res)}, calls,
+                                            2)["s"]
+        bar = {"A_min_p50_ms": floor, "A_p50_ms": [r["A_sq8_per_query"]["p50_ms"] for r in rounds],
+               "B_p50_ms": [r["B_sq8_batch"]["p50_ms"] for r in rounds],
+               "C_p50_ms": [r["C_ivf_f16_batch"]["p50_ms"] for r in rounds],
+               "B_below_A_min_in_every_round": all(r["B_sq8_batch"]["p50_ms"] < floor for r in rounds)}
+        case = {"leg": "sq8batch", "nq": nq, "nprobe": nprobe, "k": k, "calls_per_round": calls,
+                "A_equals_B_bit_for_bit": True, "rounds": rounds, "bar": bar, "B_event_p50_ms": ev,
+                "plan": dict(zip(("qt", "rows_per_chunk", "chunks", "items_bound", "blocks"),
+                                 kernels.ivf_topk_batch_plan(nq, nprobe, sq8.nlist, sq8.max_list_rows, k))),
+                "workspace_bytes": int(ws.numel()), "max_list_rows": sq8.max_list_rows}
+        print(json.dumps(case), flush=True)
+        out.append({"nq": nq, "k": k, **bar})
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=1_000_000)
@@ -555,8 +632,9 @@ def main():
     ap.add_argument("--nq", default="1,8")
     ap.add_argument("--chunk-tiles", default="", help="comma list of chunk floors (256-row tiles) for the scan alone")
     ap.add_argument("--train-iters", type=int, default=10)
-    ap.add_argument("--legs", default="search", help="comma list of: search (the default), exclude, mutate, batch, filter, mmr, pq, sq8")
+    ap.add_argument("--legs", default="search", help="comma list of: search (the default), exclude, mutate, batch, filter, mmr, pq, sq8, sq8batch")
     ap.add_argument("--pq-nq", default="1,8,256,4096", help="batch sizes of the pq and sq8 legs")
+    ap.add_argument("--sq8batch-nq", default="256,1024,4096", help="batch sizes of the sq8batch leg")
     ap.add_argument("--mutate-sizes", default="1,64,1024", help="known rows per update call of the mutate leg")
     ap.add_argument("--mutate-calls", type=int, default=12, help="timed update calls per size (fewer for large sizes)")
     ap.add_argument("--exclude-nprobe", type=int, default=20)
@@ -571,13 +649,16 @@ def main():
     ids = []   # positions only: the id maps are not what is measured
     summary = {"rows": n, "dim": d, "k": k, "nlist": args.nlist, "cases": []}
     legs = args.legs.split(",")
-    if set(legs) - {"search", "exclude", "mutate", "batch", "filter", "mmr", "pq", "sq8"}:
+    if set(legs) - {"search", "exclude", "mutate", "batch", "filter", "mmr", "pq", "sq8", "sq8batch"}:
         raise SystemExit(f"unknown leg in {args.legs!r}")
     for leg in ("pq", "sq8"):
         if leg in legs:
             summary[leg] = leg_pq(args, rows, dev, leg)
             torch.cuda.empty_cache()
-    if not set(legs) - {"pq", "sq8"}:
+    if "sq8batch" in legs:
+        summary["sq8batch"] = leg_sq8batch(args, rows, dev)
+        torch.cuda.empty_cache()
+    if not set(legs) - {"pq", "sq8", "sq8batch"}:
         print(json.dumps(summary), flush=True)
         return
     if "batch" in legs:
