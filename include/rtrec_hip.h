@@ -688,6 +688,61 @@ int rt_mmr_rerank(const float* cand_scores, const int64_t* cand_ids, int64_t nq,
                   float* out_scores, int64_t* out_ids, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Exact re-rank of an over-fetch: Faiss's IndexRefine, the third field of the
+ * factory strings "IVF1024,PQ16,RFlat" and "IVF1024,PQ16,Refine(SQ8)" that the
+ * reference hands to faiss.index_factory (src/serving/retrieval.py:96-110).
+ *
+ * rt_refine_topk: per query, score its n_cand <= RT_REFINE_MAX_CAND candidate
+ *   positions against a row store indexed by ORIGINAL position and write the
+ *   best k.
+ *   queries fp32 [nq, d], 16-byte aligned: fp32 whatever the store holds.
+ *   cand_ids int64 [nq, n_cand], contiguous: what rt_ivf_pq_topk (or any search
+ *   here) writes as out_ids — original positions, -1 pads.
+ *   store [n_rows, d], 16-byte aligned, of `kind`:
+ *     RT_REFINE_F32 / _F16 / _BF16 (the rt_dtype codes): rows, with the d /
+ *       dtype limits of rt_flatip_topk_online (f32: d % 4 == 0, 16-bit: d % 8
+ *       == 0, d <= 256); lo and step are not read.
+ *     RT_REFINE_SQ8: uint8 codes of the rows themselves (NON-residual, as
+ *       Faiss's refine index stores them: rt_sq8_encode without centroids),
+ *       with lo and step fp32 [d], 16-byte aligned, and the limits of
+ *       rt_ivf_sq8_topk (d % 16 == 0, RT_SQ8_MIN_D <= d <= RT_SQ8_MAX_D).
+ *   A candidate is ABSENT if its id is < 0 or >= n_rows: it is never read and
+ *   never returned. Duplicate positions are legal, each a candidate of its own.
+ *   Score, fp32, a function of (query, row, kind) only — not of nq, n_cand or
+ *   the candidate's slot:
+ *     rows: acc = 0; acc = fmaf(q_j, (float)x_j, acc), j ascending — with an
+ *       fp32 store the score rt_flatip_topk gives that (query, row), bit for bit;
+ *     SQ8: the arithmetic of rt_ivf_sq8_topk with bias == NULL, restated inside
+ *       the kernel (no fold launch, no workspace): mid_j = fmaf(0.5f, step_j,
+ *       lo_j); b0 = the chain fmaf(q_j, mid_j, .) over j ascending from 0;
+ *       qs_j = q_j * step_j; acc = b0; acc = fmaf(qs_j, (float)code_j, acc),
+ *       j ascending.
+ *   out_scores fp32 / out_ids int64 [nq, k]: the first k present candidates in
+ *   (score desc, position asc, candidate index asc) order with their refined
+ *   scores; (-FLT_MAX, -1) fills the slots past the number of present
+ *   candidates. The order is total on the score's bits (-0 counts as +0, a NaN
+ *   orders by its bits), so no two candidates ever claim one slot. The outputs
+ *   must not overlap the inputs.
+ *   One launch (one workgroup per query, one lane per candidate, rows gathered
+ *   in coalesced 16-byte units through LDS), no workspace, no host read:
+ *   stream-ordered and capturable.
+ *   Status, before any device work: RT_ERR_INVALID for a NULL operand (store
+ *   may be NULL only when n_rows == 0; lo / step are required for SQ8 only),
+ *   k <= 0, n_cand <= 0, d <= 0, a negative size, an unknown kind, queries /
+ *   store (/ lo / step for SQ8) not 16-byte aligned (the other operands: their
+ *   element size); RT_ERR_UNSUPPORTED for n_cand > RT_REFINE_MAX_CAND,
+ *   k > n_cand, a refused d / kind pair, nq > 65,535. nq == 0: RT_OK.
+ * ------------------------------------------------------------------------ */
+#define RT_REFINE_MAX_CAND 128   /* = RT_IVF_MAX_K */
+#define RT_REFINE_F32  0         /* = RT_F32  */
+#define RT_REFINE_F16  1         /* = RT_F16  */
+#define RT_REFINE_BF16 2         /* = RT_BF16 */
+#define RT_REFINE_SQ8  3
+int rt_refine_topk(const float* queries, int64_t nq, int d, const int64_t* cand_ids, int n_cand,
+                   const void* store, int64_t n_rows, int kind, const float* lo, const float* step, int k,
+                   float* out_scores, int64_t* out_ids, void* stream);
+
+/* ------------------------------------------------------------------------
  * In-place mutation of IVF lists stored with slack: the streaming item_update
  * path (RetrievalEngine.update_index, src/serving/retrieval.py:228-246,
  * 629-641) on the reference's default index.

@@ -657,6 +657,63 @@ def mmr_rerank(scores: torch.Tensor, positions: torch.Tensor, rows: torch.Tensor
     return os_, oi
 
 
+REFINE_MAX_CAND = 128        # RT_REFINE_MAX_CAND
+REFINE_QUERY_CHUNK = 65535   # queries per rt_refine_topk call (its grid)
+
+
+def refine_topk(queries: torch.Tensor, cand_ids: torch.Tensor, store: torch.Tensor, k: int,
+                lo: Optional[torch.Tensor] = None, step: Optional[torch.Tensor] = None,
+                out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Exact re-rank of an over-fetch (rt_refine_topk, Faiss's ``IndexRefine``): per
+    query the ``n_cand <= 128`` candidate positions ``cand_ids`` ``[nq, n_cand]``
+    (int64, what a search returned as ids; -1 pads) are scored against ``store``
+    ``[n_rows, d]``, held in ORIGINAL position order, and the best ``k`` come back
+    as (scores fp32, positions int64) ``[nq, k]`` in (score desc, position asc,
+    candidate index asc) order, ``(-FLT_MAX, -1)`` past the number of present
+    candidates. A position outside ``[0, n_rows)`` is absent: never read, never
+    returned.
+
+    ``queries``: fp32 ``[nq, d]`` whatever the store holds. ``store``: fp32 / fp16 /
+    bf16 rows — the score is the sequential fp32 fmaf chain of ``flatip_topk``, bit
+    for bit with an fp32 store — or, with ``lo`` and ``step`` (fp32 ``[d]``), uint8
+    SQ8 codes of the rows themselves (``sq8_encode`` without centroids), scored as
+    ``ivf_sq8_topk`` scores a row without a bias."""
+    native.require_device(queries, cand_ids, store, lo, step, what="refine_topk")
+    if queries.dim() != 2 or cand_ids.dim() != 2 or store.dim() != 2 or cand_ids.shape[0] != queries.shape[0] \
+            or store.shape[1] != queries.shape[1]:
+        raise ValueError(f"shape mismatch: queries {tuple(queries.shape)} cand_ids {tuple(cand_ids.shape)} "
+                         f"store {tuple(store.shape)}")
+    if queries.dtype != torch.float32 or cand_ids.dtype != torch.int64:
+        raise TypeError("refine_topk expects fp32 queries and int64 cand_ids")
+    if not (queries.is_contiguous() and cand_ids.is_contiguous() and store.is_contiguous()):
+        raise ValueError("refine_topk expects contiguous queries, cand_ids and store")
+    nq, d = queries.shape
+    n_cand = cand_ids.shape[1]
+    if not 0 < k <= n_cand:
+        raise ValueError(f"refine_topk: need 0 < k <= n_cand, got k={k}, n_cand={n_cand}")
+    if n_cand > REFINE_MAX_CAND:
+        raise ValueError(f"refine_topk: at most {REFINE_MAX_CAND} candidates per query, got {n_cand}")
+    if store.dtype == torch.uint8:
+        if lo is None or step is None:
+            raise ValueError("refine_topk: a uint8 store holds SQ8 codes and needs lo and step")
+        _sq8_params(d, "refine_topk", lo=lo, step=step)
+        kind = native.RT_REFINE_SQ8
+    else:
+        if lo is not None or step is not None:
+            raise ValueError("refine_topk: lo and step come with a uint8 store of SQ8 codes")
+        kind = native.dtype_code(store.dtype)
+        if d > 256 or d % (4 if kind == native.RT_F32 else 8):
+            raise ValueError(f"refine_topk: d={d} with {store.dtype} rows — served: d <= 256, d % 4 == 0 (fp32) "
+                             "or d % 8 == 0 (fp16 / bf16)")
+    os_, oi = _topk_out(out, nq, k, queries.device)
+    n_rows = store.shape[0]
+    for a in range(0, nq, REFINE_QUERY_CHUNK):
+        b = min(nq, a + REFINE_QUERY_CHUNK)
+        call("rt_refine_topk", ptr(queries[a:b]), b - a, d, ptr(cand_ids[a:b]), n_cand, ptr(store) if n_rows else None,
+             n_rows, kind, ptr(lo), ptr(step), int(k), ptr(os_[a:b]), ptr(oi[a:b]), stream_of(queries))
+    return os_, oi
+
+
 # ---------------------------------------------------------------------------
 # IVF-Flat (faiss "IVF<nlist>,Flat" + nprobe, src/serving/retrieval.py:60-62,101-133)
 # ---------------------------------------------------------------------------

@@ -19,6 +19,7 @@ PKG_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("RTREC_HIP_LIB", os.path.join(PKG_DIR, "lib", "librtrec_hip.so"))
 
 RT_F32, RT_F16, RT_BF16 = 0, 1, 2
+RT_REFINE_SQ8 = 3   # rt_refine_topk's fourth store kind, after the three dtype codes
 ACTS = {"relu": 0, "gelu": 1, "leaky_relu": 2, "tanh": 3, "sigmoid": 4, "none": 5}
 
 c_i64 = ctypes.c_int64
@@ -174,6 +175,7 @@ SIGNATURES = {
                                     c_size, vp]),
     "rt_mmr_rerank": (c_int, [vp, vp, c_i64, c_int, vp, c_i64, c_int, c_int, vp, c_i64, vp, c_int, c_int, vp, vp,
                               vp]),
+    "rt_refine_topk": (c_int, [vp, c_i64, c_int, vp, c_int, vp, c_i64, c_int, vp, vp, c_int, vp, vp, vp]),
     "rt_topk_merge": (c_int, [vp, vp, c_i64, c_int, c_int, c_int, vp, vp, vp]),
     "rt_flatip_topk_tuning": (c_int, [c_int, c_int, c_int]),
     "rt_flatip_topk_shard_workspace_bytes": (c_size, [c_i64, c_i64, c_int, c_int, c_int]),

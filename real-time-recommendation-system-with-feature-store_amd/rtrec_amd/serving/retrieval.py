@@ -2426,6 +2426,11 @@ class _IVFCodesIndex(HipIVFFlatIndex):
             raise ValueError(f"k={k}: the MI355X IVF index returns 1..{kernels.IVF_MAX_K} results per query")
         np_ = self._n_probe(nprobe)
         q32 = self._prepare(query_embeddings)
+        return self._search_prepared(q32, k, exclude_bits, np_, tag_filter)
+
+    def _search_prepared(self, q32: torch.Tensor, k: int, exclude_bits: Optional[torch.Tensor], np_: int,
+                         tag_filter) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``search_tensors`` behind its checks: the filter bitmap, the coarse search, the scan."""
         exclude_bits = self._filter_bits(tag_filter, q32.shape[0], exclude_bits)
         coarse, probes = self.coarse_search(q32, np_)
         return self._scan_codes(q32, probes, k, coarse if self.by_residual else None, exclude_bits)
@@ -2462,10 +2467,19 @@ class _IVFCodesIndex(HipIVFFlatIndex):
 _IVF_PQ_FACTORY = "IVF1024,PQ16"
 
 
-def _parse_ivf_pq_factory(factory: str) -> Tuple[int, int]:
-    """``"IVF<nlist>,PQ<M>"`` or ``"IVF<nlist>,PQ<M>x8"`` -> (nlist, M); anything else raises."""
+_PQ_REFINE_SUFFIXES = {"RFlat": "flat", "Refine(SQ8)": "sq8"}   # Faiss's IndexRefine spellings
+
+
+def _parse_ivf_pq_factory(factory: str) -> Tuple[int, int, Optional[str]]:
+    """``"IVF<nlist>,PQ<M>"`` or ``"IVF<nlist>,PQ<M>x8"``, optionally followed by ``",RFlat"`` or
+    ``",Refine(SQ8)"`` -> (nlist, M, refine: None / "flat" / "sq8"); anything else raises."""
     s = str(factory)
     head, _, tail = s.partition(",")
+    tail, comma, suffix = tail.partition(",")
+    if comma and suffix not in _PQ_REFINE_SUFFIXES:
+        raise ValueError(f"index_factory {factory!r}: after 'IVF<nlist>,PQ<M>' HipIVFPQIndex serves the refine "
+                         "suffixes 'RFlat' (exact rows) and 'Refine(SQ8)' (8-bit codes of the rows), "
+                         f"not {suffix!r}")
     m, x, bits = tail[2:].partition("x")
     ok = head.startswith("IVF") and head[3:].isdigit() and int(head[3:]) >= 1 and tail.startswith("PQ") \
         and m.isdigit() and (not x or bits == "8")
@@ -2473,7 +2487,7 @@ def _parse_ivf_pq_factory(factory: str) -> Tuple[int, int]:
         raise ValueError(f"index_factory {factory!r}: HipIVFPQIndex serves 'IVF<nlist>,PQ<M>' and "
                          "'IVF<nlist>,PQ<M>x8' (8 bits per code, 256 codewords per subspace; "
                          "'IVF<nlist>,Flat': HipIVFFlatIndex)")
-    return int(head[3:]), int(m)
+    return int(head[3:]), int(m), _PQ_REFINE_SUFFIXES.get(suffix)
 
 
 class HipIVFPQIndex(_IVFCodesIndex):
@@ -2511,10 +2525,24 @@ class HipIVFPQIndex(_IVFCodesIndex):
     multiple of 4 up to 32 — the kernels take any even d / M, the training's
     ``rt_segment_mean_f32`` whole 16-byte units); ``by_residual`` (True); ``pq_train_iters`` (25, Faiss's
     ``ClusteringParameters.niter``). ``storage_dtype`` only reaches the Flat
-    fallback (below 1,024 items or nlist, as on the parent).
+    fallback (below 1,024 items or nlist, as on the parent) and ``refine_dtype``.
+
+    Refine (Faiss's ``IndexRefine``; off by default): ``refine`` = ``"flat"`` or
+    ``"sq8"`` — or the factory suffixes ``",RFlat"`` / ``",Refine(SQ8)"`` — keeps a
+    row store ``[n, d]`` in ORIGINAL position order next to the codes: the prepared
+    rows in ``refine_dtype`` (default ``storage_dtype``), or ``rt_sq8_encode`` of the
+    rows themselves against their exact per-dimension range (128 B per item at d =
+    128; d % 16 == 0, d <= 256). ``search_tensors`` with ``k < current_size`` then
+    scans ``R = min(128, refine_k_factor * k, current_size)`` candidates
+    (``refine_k_factor`` default 10, the reference's over-fetch; R never below k) and
+    ``rt_refine_topk`` returns the k best by their scores against the store —
+    for rows the exact sequential fp32 chain of the Flat index. Exclusions and
+    category filters act in the scan, as before; ``add`` appends to the store, ``save``
+    / ``load`` carry it, the Flat fallback ignores it, ``vectors()`` stays the PQ
+    reconstruction. DESIGN.md §5 "IVF-PQ refine" has the measured table.
 
     Not served here — each raises and names the class that has it: the MMR re-rank
-    (it needs stored rows), ``online_max_batch`` / ``online_searcher`` with their
+    (it needs stored rows: served with ``refine="flat"``, over the store), ``online_max_batch`` / ``online_searcher`` with their
     exclusion lists and in-scan tag filter, and ``batch_min_queries``
     (:class:`HipIVFFlatIndex`); ``update`` / ``remove`` / ``mutable``
     (:class:`HipMutableIVFFlatIndex`).
@@ -2533,10 +2561,89 @@ class HipIVFPQIndex(_IVFCodesIndex):
                              f"multiple of 4 elements (rt_segment_mean_f32), d / M = {self.dimension // self.pq_m}")
         self.pq_train_iters = int(self.config.get("pq_train_iters", 25))
         self.codebooks: Optional[torch.Tensor] = None   # [M, 256, d / M] fp32
+        self._init_refine()
+        self._drop_refine()
 
     def _parse_factory(self, factory: str) -> int:
-        nlist, self.pq_m = _parse_ivf_pq_factory(factory)
+        nlist, self.pq_m, self._factory_refine = _parse_ivf_pq_factory(factory)
         return nlist
+
+    # -- refine: exact re-rank of an over-fetch from a resident row store ----
+    def _init_refine(self):
+        """The ``refine`` / ``refine_k_factor`` / ``refine_dtype`` options (the factory suffix
+        sets ``refine`` too), checked against what ``rt_refine_topk`` serves."""
+        r = self.config.get("refine")
+        if self._factory_refine is not None:
+            if r is not None and r != self._factory_refine:
+                raise ValueError(f"refine={r!r} contradicts index_factory {self.index_factory!r}")
+            r = self._factory_refine
+        if r not in (None, "flat", "sq8"):
+            raise ValueError(f"refine={r!r}: None (off), 'flat' (index_factory '...,RFlat') or 'sq8' "
+                             "('...,Refine(SQ8)')")
+        self.refine = r
+        self.refine_k_factor = int(self.config.get("refine_k_factor", 10))
+        if self.refine_k_factor < 1:
+            raise ValueError(f"refine_k_factor={self.refine_k_factor}: >= 1")
+        name = self.config.get("refine_dtype")
+        self.refine_dtype = self.storage_dtype if name is None else _STORAGE[name]
+        if r == "flat" and self.refine_dtype != torch.float32 and self.dimension % 8:
+            raise ValueError(f"refine='flat' with {self.refine_dtype} rows: dimension {self.dimension} is not a "
+                             "multiple of 8")
+        if r == "sq8":
+            kernels._sq8_params(self.dimension, "refine='sq8'")
+
+    def _drop_refine(self):
+        self.refine_store: Optional[torch.Tensor] = None   # [n, d] in ORIGINAL position order
+        self.refine_lo = self.refine_step = self.refine_inv_step = None   # 'sq8': fp32 [d]
+
+    def _refine_rows(self, rows: torch.Tensor) -> torch.Tensor:
+        """Prepared fp32 rows as the store keeps them: cast, or SQ8 codes of the rows themselves."""
+        if self.refine == "flat":
+            return rows.to(self.refine_dtype)
+        return kernels.sq8_encode(rows, self.refine_lo, self.refine_inv_step)
+
+    def _build_refine(self, rows: torch.Tensor):
+        self._drop_refine()
+        if self.refine is None:
+            return
+        if self.refine == "sq8":   # non-residual, as Faiss's refine index: the range of the rows
+            self.refine_lo, self.refine_step, self.refine_inv_step = _sq8_range(rows)
+        self.refine_store = self._refine_rows(rows).contiguous()
+
+    def _check_mmr(self):
+        if self.refine != "flat":
+            raise ValueError(f"mmr_lambda: the MMR re-rank reads stored rows, and {type(self).__name__} keeps codes "
+                             "only unless refine='flat'; HipIVFFlatIndex serves it")
+        _HbmIndex._check_mmr(self)
+
+    def _mmr_operands(self):
+        if self._flat is not None:
+            return self._flat._mmr_operands()
+        return self.refine_store, None, self.current_size
+
+    def search_tensors(self, query_embeddings: Array, k: int, exclude_bits: Optional[torch.Tensor] = None,
+                       nprobe: Optional[int] = None, tag_filter=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """As the parent's; with a refine store and ``k < current_size`` the scan
+        over-fetches ``R = min(128, refine_k_factor * k, current_size)`` (never below
+        k) candidates and ``rt_refine_topk`` returns the k best by their exact (flat)
+        or SQ8 scores against the store: (score desc, position asc), refined scores."""
+        if self.refine_store is None or self._flat is not None or not 1 <= k <= kernels.IVF_MAX_K \
+                or k >= self.current_size:
+            return super().search_tensors(query_embeddings, k, exclude_bits=exclude_bits, nprobe=nprobe,
+                                          tag_filter=tag_filter)
+        r = max(k, min(kernels.REFINE_MAX_CAND, self.refine_k_factor * k, self.current_size))
+        np_ = self._n_probe(nprobe)
+        q32 = self._prepare(query_embeddings)
+        _, cand = self._search_prepared(q32, r, exclude_bits, np_, tag_filter)
+        return kernels.refine_topk(q32, cand, self.refine_store, k, lo=self.refine_lo, step=self.refine_step)
+
+    def add(self, embeddings: Array, ids: List[str], item_categories=None):
+        """As the parent's; the new rows are cast, or encoded against the store's
+        existing range, and appended to the refine store."""
+        flat = self._flat is not None
+        super().add(embeddings, ids, item_categories=item_categories)
+        if self.refine_store is not None and not flat:
+            self.refine_store = torch.cat([self.refine_store, self._refine_rows(self._prepare(embeddings))])
 
     # -- product quantiser -------------------------------------------------
     def _train_pq(self, rows: torch.Tensor, assign: torch.Tensor) -> torch.Tensor:
@@ -2573,6 +2680,7 @@ class HipIVFPQIndex(_IVFCodesIndex):
         n = len(embeddings)
         if n < IVF_MIN_ITEMS or n < self.nlist:
             self.codebooks = None
+            self._drop_refine()
             return super().build(embeddings, ids, item_categories=item_categories)   # the Flat fallback
         start = time.time()
         tags = self._item_tags(item_categories, n)
@@ -2582,6 +2690,7 @@ class HipIVFPQIndex(_IVFCodesIndex):
         assign = self._assign_rows(rows, self.centroids)
         self.codebooks = self._train_pq(rows, assign)
         self._regroup(self._encode(rows, assign), None, assign)
+        self._build_refine(rows)
         self._tags = None
         self._tags_store(0, tags)
         self._reset_ids()
@@ -2624,10 +2733,17 @@ class HipIVFPQIndex(_IVFCodesIndex):
         path.parent.mkdir(parents=True, exist_ok=True)
         self._save_ids(path)
         cfg = {k: v for k, v in self.config.items() if isinstance(v, (str, int, float, bool, type(None)))}
+        refine = {}
+        if self.refine_store is not None:   # the store's bytes (numpy has no bf16) and what they are
+            refine = dict(refine=np.array(self.refine), refine_store=self.refine_store.view(torch.uint8).cpu().numpy(),
+                          refine_dtype=np.array(str(self.refine_store.dtype).replace("torch.", "")))
+            if self.refine == "sq8":
+                refine.update(refine_lo=self.refine_lo.cpu().numpy(), refine_step=self.refine_step.cpu().numpy(),
+                              refine_inv_step=self.refine_inv_step.cpu().numpy())
         np.savez(npz, codes=self._codes_by_position().cpu().numpy(), codebooks=self.codebooks.cpu().numpy(),
                  centroids=self.centroids.cpu().numpy(), assign=self.assign.cpu().numpy(),
                  config=np.array(json.dumps(cfg)), seed=np.int64(self.seed), nlist=np.int64(self.nlist),
-                 by_residual=np.bool_(self.by_residual))
+                 by_residual=np.bool_(self.by_residual), **refine)
         self._save_tags(path)
         logger.info("Saved index to %s", path)
 
@@ -2636,21 +2752,35 @@ class HipIVFPQIndex(_IVFCodesIndex):
         npz = path.with_suffix(".ivfpq.npz")
         if not npz.exists():   # saved by the Flat fallback
             self.codebooks = None
+            self._drop_refine()
             return super().load(str(path))
         self._online = None
         data = self._read_pkl(path)
         with np.load(npz) as z:
             codes, codebooks, centroids, assign = z["codes"], z["codebooks"], z["centroids"], z["assign"]
             self.seed, self.nlist, self.by_residual = int(z["seed"]), int(z["nlist"]), bool(z["by_residual"])
+            refine = {name: z[name] for name in z.files if name.startswith("refine")}   # none: no store
         self._flat = None
         self.config = dict(data.get("config", self.config))
         self.metric = self.config.get("metric", self.metric)
         self.pq_m, self.dimension = int(codebooks.shape[0]), int(centroids.shape[1])
-        self.index_factory = f"IVF{self.nlist},PQ{self.pq_m}"
+        # refine is what the file holds, whatever the saved config asked for
+        self._factory_refine = self.config["refine"] = str(refine["refine"]) if refine else None
+        self._init_refine()
+        self._drop_refine()
+        suffix = {v: "," + s for s, v in _PQ_REFINE_SUFFIXES.items()}.get(self.refine, "")
+        self.index_factory = f"IVF{self.nlist},PQ{self.pq_m}{suffix}"
         dev = self._dev()
         self.centroids = torch.from_numpy(centroids).to(dev)
         self.codebooks = torch.from_numpy(codebooks).to(dev)
         self._regroup(torch.from_numpy(codes).to(dev), None, torch.from_numpy(assign).to(dev))
+        if refine:
+            self.refine_dtype = getattr(torch, str(refine["refine_dtype"]))
+            store = torch.from_numpy(refine["refine_store"]).to(dev)
+            self.refine_store = store if self.refine == "sq8" else store.view(self.refine_dtype)
+            if self.refine == "sq8":
+                self.refine_lo, self.refine_step, self.refine_inv_step = (
+                    torch.from_numpy(refine[name]).to(dev) for name in ("refine_lo", "refine_step", "refine_inv_step"))
         self._load_ids(data, self.current_size)
         self._load_tags(path)
         self._generation += 1
@@ -2659,6 +2789,23 @@ class HipIVFPQIndex(_IVFCodesIndex):
 
 _IVF_SQ8_FACTORY = "IVF1024,SQ8"
 _SQ8_RANGE_CHUNK = 1 << 18   # rows per amin / amax pass of the range
+
+
+def _sq8_range(rows: torch.Tensor, centroids: Optional[torch.Tensor] = None, assign: Optional[torch.Tensor] = None
+               ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(lo, step, inv_step), fp32 [d]: the exact per-dimension range of every row — of its
+    residual ``row - centroids[assign]`` with ``centroids`` — as the SQ8 quantiser."""
+    lo = hi = None
+    for a in range(0, rows.shape[0], _SQ8_RANGE_CHUNK):
+        x = rows[a:a + _SQ8_RANGE_CHUNK]
+        if centroids is not None:
+            x = x - centroids[assign[a:a + _SQ8_RANGE_CHUNK]]   # the encode's fp32 subtraction
+        mn, mx = x.amin(dim=0), x.amax(dim=0)
+        lo = mn if lo is None else torch.minimum(lo, mn)
+        hi = mx if hi is None else torch.maximum(hi, mx)
+    span = hi - lo
+    return (lo.contiguous(), (span / 255.0).contiguous(),
+            torch.where(span > 0, 255.0 / span, torch.zeros_like(span)).contiguous())
 
 
 def _parse_ivf_sq8_factory(factory: str) -> int:
@@ -2736,18 +2883,7 @@ class HipIVFSQ8Index(_IVFCodesIndex):
 
     def _train_range(self, rows: torch.Tensor, assign: torch.Tensor):
         """lo, step, inv_step from the exact per-dimension range of every (residual) row."""
-        lo = hi = None
-        for a in range(0, rows.shape[0], _SQ8_RANGE_CHUNK):
-            x = rows[a:a + _SQ8_RANGE_CHUNK]
-            if self.by_residual:
-                x = x - self.centroids[assign[a:a + _SQ8_RANGE_CHUNK]]   # the encode's fp32 subtraction
-            mn, mx = x.amin(dim=0), x.amax(dim=0)
-            lo = mn if lo is None else torch.minimum(lo, mn)
-            hi = mx if hi is None else torch.maximum(hi, mx)
-        span = hi - lo
-        self.lo = lo.contiguous()
-        self.step = (span / 255.0).contiguous()
-        self.inv_step = torch.where(span > 0, 255.0 / span, torch.zeros_like(span)).contiguous()
+        self.lo, self.step, self.inv_step = _sq8_range(rows, self.centroids if self.by_residual else None, assign)
 
     def _encode(self, rows: torch.Tensor, assign: torch.Tensor) -> torch.Tensor:
         if self.by_residual:

@@ -93,6 +93,14 @@ the p50 per round and arm, and the hipEvent p50 of B's scan call whole and split
 + grouping / scan / finish (rt_ivf_topk_batch_tuning), next to A's scan call. The bar, at
 nq = 4096: B's p50 in every round is below the MINIMUM of A's p50 over its rounds.
 
+``--legs refine`` (not in the default list): the pq leg's protocol over ``hip_ivf`` float16 and,
+for M = 16 and M = 32, ``hip_ivf_pq`` plain, with ``,RFlat`` (float16 rows) and with
+``,Refine(SQ8)``, plus the plain index at k = R = 100 (what a refined call scans before its
+refine launch): nprobe = 20, k = 10, refine_k_factor 10. Per nq the median p50 of 3 rounds,
+recall@10 against the exact Flat lists, the refine launch's share of the call (refined p50 minus
+the plain index's p50 at k = R, same run), the ratio to IVF-Flat float16 and the resident bytes
+per item, store included. No bar.
+
 Prints one JSON line per case and a closing summary line; run it under a time
 limit, e.g. ``timeout 900 python tools/ivf_latency.py > profiles/ivf_latency.txt``.
 """
@@ -552,6 +560,69 @@ def leg_pq(args, rows, dev, leg="pq"):
     return out
 
 
+def leg_refine(args, rows, dev):
+    """The refine leg: one JSON line per nq. ``rows``: fp32 unit rows on the device."""
+    n, d, k, nprobe = rows.shape[0], rows.shape[1], 10, 20
+    nqs = [int(x) for x in args.pq_nq.split(",")]
+    queries = torch.from_numpy(corpus(n, d, 4096, max(nqs), dev)[1]).to(dev)   # the same rows, more queries
+    base = {"dimension": d, "metric": "cosine", "nprobe": nprobe, "train_iters": args.train_iters}
+    sides, build_s = {}, {}
+    arms = [("ivf_f16", HipIVFFlatIndex, {"index_factory": f"IVF{args.nlist},Flat", "storage_dtype": "float16"}),
+            ("sq8", HipIVFSQ8Index, {"index_factory": f"IVF{args.nlist},SQ8"})]   # the index a store competes with
+    for m in (16, 32):
+        pq = f"IVF{args.nlist},PQ{m}"
+        arms += [(f"pq{m}", HipIVFPQIndex, {"index_factory": pq}),
+                 (f"pq{m}_rflat", HipIVFPQIndex, {"index_factory": pq + ",RFlat", "refine_dtype": "float16"}),
+                 (f"pq{m}_rsq8", HipIVFPQIndex, {"index_factory": pq + ",Refine(SQ8)"})]
+    for name, cls, cfg in arms:
+        t0 = time.perf_counter()
+        sides[name] = cls({**base, **cfg})
+        sides[name].build(rows, [])
+        torch.cuda.synchronize()
+        build_s[name] = round(time.perf_counter() - t0, 3)
+    flat = HipFlatIPIndex({"dimension": d, "metric": "cosine", "storage_dtype": "float32"})
+    flat.build(rows, [])
+    r_cand = max(k, min(kernels.REFINE_MAX_CAND, sides["pq16_rflat"].refine_k_factor * k, n))
+    # codes or rows, the refine store, and what stays resident next to them (row_pos int32, assign int64)
+    bytes_per_item = {name: ix.index.shape[1] * ix.index.element_size() + 12
+                      + (0 if getattr(ix, "refine_store", None) is None
+                         else ix.refine_store.shape[1] * ix.refine_store.element_size())
+                      for name, ix in sides.items()}
+    out = []
+    for nq in nqs:
+        q = queries[:nq].contiguous()
+        calls = max(5, min(args.calls, 20480 // nq))
+
+        def run(ix, kk=k):
+            def f():
+                r = ix.search_tensors(q, kk)
+                torch.cuda.synchronize()
+                return r
+            return f
+
+        fns = {name: run(ix) for name, ix in sides.items()}
+        exact = flat.search_tensors(q, k)[1].cpu().numpy()
+        got = {name: f()[1].cpu().numpy() for name, f in fns.items()}
+        # the unrefined scan at k = R: what a refined call runs before its refine launch
+        fns.update({f"pq{m}_k{r_cand}": run(sides[f"pq{m}"], r_cand) for m in (16, 32)})
+        names, rounds = list(fns), []
+        for r in range(3):
+            order = names[r:] + names[:r]
+            rounds.append({"first": order[0], **timed_alternating({nm: fns[nm] for nm in order}, calls, 3)})
+        p50 = {nm: sorted(r[nm]["p50_ms"] for r in rounds)[1] for nm in names}
+        case = {"leg": "refine", "nq": nq, "nprobe": nprobe, "k": k, "refine_candidates": r_cand,
+                "calls_per_round": calls, "rounds": rounds, "p50_ms": p50,
+                "recall_at_10_vs_flat": {nm: round(recall(got[nm], exact), 4) for nm in got},
+                "refine_share_ms": {f"pq{m}_{s}": round(p50[f"pq{m}_{s}"] - p50[f"pq{m}_k{r_cand}"], 5)
+                                    for m in (16, 32) for s in ("rflat", "rsq8")},
+                "over_ivf_f16": {nm: round(p50[nm] / p50["ivf_f16"], 3) for nm in got},
+                "bytes_per_item": bytes_per_item, "build_s": build_s}
+        print(json.dumps(case), flush=True)
+        out.append({key: case[key] for key in ("nq", "p50_ms", "recall_at_10_vs_flat", "refine_share_ms",
+                                               "over_ivf_f16", "bytes_per_item")})
+    return out
+
+
 def leg_sq8batch(args, rows, dev):
     """The sq8batch leg: one JSON line per (k, nq). ``rows``: fp32 unit rows on the device."""
     n, d, nprobe = rows.shape[0], rows.shape[1], 20
@@ -632,8 +703,8 @@ def main():
     ap.add_argument("--nq", default="1,8")
     ap.add_argument("--chunk-tiles", default="", help="comma list of chunk floors (256-row tiles) for the scan alone")
     ap.add_argument("--train-iters", type=int, default=10)
-    ap.add_argument("--legs", default="search", help="comma list of: search (the default), exclude, mutate, batch, filter, mmr, pq, sq8, sq8batch")
-    ap.add_argument("--pq-nq", default="1,8,256,4096", help="batch sizes of the pq and sq8 legs")
+    ap.add_argument("--legs", default="search", help="comma list of: search (the default), exclude, mutate, batch, filter, mmr, pq, sq8, sq8batch, refine")
+    ap.add_argument("--pq-nq", default="1,8,256,4096", help="batch sizes of the pq, sq8 and refine legs")
     ap.add_argument("--sq8batch-nq", default="256,1024,4096", help="batch sizes of the sq8batch leg")
     ap.add_argument("--mutate-sizes", default="1,64,1024", help="known rows per update call of the mutate leg")
     ap.add_argument("--mutate-calls", type=int, default=12, help="timed update calls per size (fewer for large sizes)")
@@ -649,7 +720,7 @@ def main():
     ids = []   # positions only: the id maps are not what is measured
     summary = {"rows": n, "dim": d, "k": k, "nlist": args.nlist, "cases": []}
     legs = args.legs.split(",")
-    if set(legs) - {"search", "exclude", "mutate", "batch", "filter", "mmr", "pq", "sq8", "sq8batch"}:
+    if set(legs) - {"search", "exclude", "mutate", "batch", "filter", "mmr", "pq", "sq8", "sq8batch", "refine"}:
         raise SystemExit(f"unknown leg in {args.legs!r}")
     for leg in ("pq", "sq8"):
         if leg in legs:
@@ -658,7 +729,10 @@ def main():
     if "sq8batch" in legs:
         summary["sq8batch"] = leg_sq8batch(args, rows, dev)
         torch.cuda.empty_cache()
-    if not set(legs) - {"pq", "sq8", "sq8batch"}:
+    if "refine" in legs:
+        summary["refine"] = leg_refine(args, rows, dev)
+        torch.cuda.empty_cache()
+    if not set(legs) - {"pq", "sq8", "sq8batch", "refine"}:
         print(json.dumps(summary), flush=True)
         return
     if "batch" in legs:
