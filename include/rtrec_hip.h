@@ -324,6 +324,34 @@ int rt_segment_mean_f32(const void* rows, int64_t n, int d, int dtype, const int
                         const float* prev, int normalize, float* out, void* stream);
 
 /* ------------------------------------------------------------------------
+ * IVF-Flat, wide top-K: rt_ivf_topk's contract for 1 <= k <= RT_IVF_WIDE_MAX_K
+ * (the reference retrieves k = num_recommendations * 10 <= 1,000 candidates,
+ * src/serving/service.py:206). Operands, result order ((score desc, original
+ * position asc), (-FLT_MAX, -1) pads), score bits (rt_ivf_topk's, all three
+ * dtypes), probes (-1 or outside [0, nlist): no list), the optional bitmap
+ * (indexed by original position) and the plan (rt_ivf_topk_plan, honouring
+ * rt_ivf_topk_tuning) are rt_ivf_topk's. list_len and n_pos are operands of
+ * this one entry point and mean what they mean for rt_ivf_topk_lens: list_len
+ * may be NULL (lists without slack; pass n_pos = nx), positions outside
+ * [0, n_pos) are dropped, exclude_words >= ceil(n_pos / 32). No CSR exclusion
+ * lists and no tag filter: fold them into the bitmap. A row_pos that repeats
+ * positions may return a position more than once, never more than k entries.
+ * Two launches on `stream`, no host read, the grid from host arguments only:
+ * capturable. Status, before any device work: rt_ivf_topk_lens's refusals with
+ * RT_ERR_UNSUPPORTED for k > RT_IVF_WIDE_MAX_K (list_len == NULL is accepted).
+ * rt_ivf_topk_wide_workspace_bytes: per scan block (rt_ivf_topk_plan's out[2])
+ *   a count and min(k, rows per chunk) 8-byte composite keys (256 for a
+ *   refused shape). Workspace alignment: 8 bytes.
+ * ------------------------------------------------------------------------ */
+#define RT_IVF_WIDE_MAX_K 1024
+size_t rt_ivf_topk_wide_workspace_bytes(int64_t nq, int nprobe, int64_t max_list_rows, int k);
+int rt_ivf_topk_wide(const void* queries, int64_t nq, const void* rows, int64_t nx, int d, int dtype,
+                     const int64_t* list_offsets, int64_t nlist, const int64_t* list_len, int64_t n_pos,
+                     const int32_t* row_pos, const int64_t* probes, int nprobe, int64_t max_list_rows, int k,
+                     const uint32_t* exclude_bits, int64_t exclude_words, float* out_scores, int64_t* out_ids,
+                     void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * IVF-PQ (faiss.index_factory(d, "IVF1024,PQ16"): the factory string of
  * src/serving/retrieval.py:96-110 with product-quantised lists). A stored row
  * is M bytes: code m names one of the 256 codewords of subspace m, the

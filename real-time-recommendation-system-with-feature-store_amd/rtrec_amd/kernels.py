@@ -852,6 +852,74 @@ def ivf_topk(queries: torch.Tensor, rows: torch.Tensor, list_offsets: torch.Tens
     return scores, ids
 
 
+IVF_WIDE_MAX_K = 1024   # RT_IVF_WIDE_MAX_K
+# Workspace one rt_ivf_topk_wide call may ask for: a query's slices are nprobe x
+# chunks x (min(k, rows per chunk) + 1) keys of 8 bytes (164 KB at nprobe 20, 4
+# chunks, k = 1000), so larger batches run in chunks. The batch scan's policy
+# default (IVF_BATCH_WORKSPACE_BUDGET), not a measured one.
+IVF_WIDE_WORKSPACE_BUDGET = 256 << 20
+
+
+def ivf_topk_wide(queries: torch.Tensor, rows: torch.Tensor, list_offsets: torch.Tensor, row_pos: torch.Tensor,
+                  probes: torch.Tensor, max_list_rows: int, k: int, exclude_bits: Optional[torch.Tensor] = None,
+                  out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                  workspace_buf: Optional[torch.Tensor] = None, list_len: Optional[torch.Tensor] = None,
+                  n_pos: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """:func:`ivf_topk` for ``1 <= k <= 1024`` (rt_ivf_topk_wide): the same operands,
+    result order, pads and score bits; a selection of its own (unsorted per-block
+    key sets, an exact radix select of the k-th composite key and one sort of the
+    survivors). Exclusions come as the bitmap only — fold CSR lists and tag
+    filters into it (``tag_filter_bitmap``). ``list_len`` with ``n_pos``: lists
+    stored with slack, as for :func:`ivf_topk`. Batches run in chunks whose
+    workspace stays within ``IVF_WIDE_WORKSPACE_BUDGET``."""
+    native.require_device(queries, rows, list_offsets, row_pos, probes, exclude_bits, list_len, what="ivf_topk_wide")
+    if queries.dim() != 2 or rows.dim() != 2 or queries.shape[1] != rows.shape[1]:
+        raise ValueError(f"shape mismatch: queries {tuple(queries.shape)} rows {tuple(rows.shape)}")
+    if queries.dtype != rows.dtype:
+        raise TypeError("queries and rows must share a dtype")
+    if not 1 <= k <= IVF_WIDE_MAX_K:
+        raise ValueError(f"k={k}: ivf_topk_wide returns 1..{IVF_WIDE_MAX_K} results per query")
+    if not (queries.is_contiguous() and rows.is_contiguous() and probes.is_contiguous()
+            and list_offsets.is_contiguous() and row_pos.is_contiguous()):
+        raise ValueError("ivf_topk_wide expects contiguous operands")
+    nq, d = queries.shape
+    nx = rows.shape[0]
+    if list_offsets.dtype != torch.int64 or list_offsets.dim() != 1 or list_offsets.numel() < 2:
+        raise ValueError("list_offsets must be int64 [nlist + 1]")
+    if row_pos.dtype != torch.int32 or row_pos.numel() != nx:
+        raise ValueError("row_pos must be int32 [nx]")
+    if probes.dtype != torch.int64 or probes.dim() != 2 or probes.shape[0] != nq:
+        raise ValueError("probes must be int64 [nq, nprobe]")
+    nprobe = probes.shape[1]
+    if not 1 <= nprobe <= IVF_MAX_NPROBE:
+        raise ValueError(f"nprobe={nprobe}: 1..{IVF_MAX_NPROBE}")
+    nlist = list_offsets.numel() - 1
+    if list_len is not None:
+        if list_len.dtype != torch.int64 or list_len.numel() != nlist or not list_len.is_contiguous():
+            raise ValueError("list_len must be contiguous int64 [nlist]")
+        if n_pos is None or not 0 <= int(n_pos):
+            raise ValueError("list_len comes with n_pos >= 0, the number of valid positions")
+    elif n_pos is not None:
+        raise ValueError("n_pos comes with list_len")
+    npos = int(n_pos) if list_len is not None else nx
+    dt = native.dtype_code(queries.dtype)
+    scores, ids = _topk_out(out, nq, k, queries.device)
+    words = _exclude_words(exclude_bits, nq, True)
+    ws_bytes = native.lib().rt_ivf_topk_wide_workspace_bytes
+    per_query = max(1, ws_bytes(1, nprobe, int(max_list_rows), k))
+    step = max(1, min(IVF_QUERY_CHUNK, IVF_WIDE_WORKSPACE_BUDGET // per_query))
+    for a in range(0, nq, step):
+        b = min(nq, a + step)
+        ws = workspace_buf
+        if ws is None:
+            ws = workspace(queries.device, ws_bytes(b - a, nprobe, int(max_list_rows), k), "ivf_topk_wide")
+        call("rt_ivf_topk_wide", ptr(queries[a:b]), b - a, ptr(rows) if nx else None, nx, d, dt,
+             ptr(list_offsets), nlist, ptr(list_len), npos, ptr(row_pos) if nx else None, ptr(probes[a:b]), nprobe,
+             int(max_list_rows), k, ptr(exclude_bits[a:b]) if exclude_bits is not None else None, words,
+             ptr(scores[a:b]), ptr(ids[a:b]), ptr(ws), ws.numel(), stream_of(queries))
+    return scores, ids
+
+
 # ---------------------------------------------------------------------------
 # IVF-PQ (faiss "IVF<nlist>,PQ<M>": product-quantised lists, include/rtrec_hip.h)
 # ---------------------------------------------------------------------------

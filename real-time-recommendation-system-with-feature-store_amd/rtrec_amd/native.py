@@ -153,6 +153,9 @@ SIGNATURES = {
                                  c_int, vp, c_i64, vp, vp, vp, c_size, vp]),
     "rt_ivf_topk_lists_lens": (c_int, [vp, c_i64, vp, c_i64, c_int, c_int, vp, c_i64, vp, c_i64, vp, vp, c_int,
                                        c_i64, c_int, ctypes.POINTER(ExclusionLists), c_int, vp, vp, vp, c_size, vp]),
+    "rt_ivf_topk_wide_workspace_bytes": (c_size, [c_i64, c_int, c_i64, c_int]),
+    "rt_ivf_topk_wide": (c_int, [vp, c_i64, vp, c_i64, c_int, c_int, vp, c_i64, vp, c_i64, vp, vp, c_int, c_i64,
+                                 c_int, vp, c_i64, vp, vp, vp, c_size, vp]),
     "rt_ivf_topk_batch_tuning": (c_int, [c_int]),
     "rt_ivf_topk_batch_plan": (c_int, [c_i64, c_int, c_i64, c_i64, c_int, vp]),
     "rt_ivf_topk_batch_workspace_bytes": (c_size, [c_i64, c_int, c_i64, c_i64, c_int]),

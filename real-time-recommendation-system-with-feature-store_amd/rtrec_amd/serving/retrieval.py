@@ -1643,10 +1643,18 @@ class HipIVFFlatIndex(_HbmIndex):
     queries per call — 0.90x (float16) and 0.79x (float32) the per-query path's
     time there, slower below it (1.03-1.05x at 1,024, about 2x at 16-256) — so
     4096 is the recommended value.
+    ``wide_k`` (default ``False``; saved and loaded with the config): ``True`` lets
+    ``search_tensors`` — and ``search`` (2k <= 1024 with ``filter_ids``) and
+    ``RetrievalEngine.retrieve`` above it — return up to 1,024 results per query,
+    the reference's ``retrieve(k = num_recommendations * 10)``. k <= 128 takes the
+    scans it takes without the key; 128 < k <= 1024 takes ``rt_ivf_topk_wide``, with
+    ``exclude_ids`` and category filters folded into its bitmap. The MMR candidates,
+    the resident searcher and the PQ / SQ8 indexes keep their 128.
+    Measured: DESIGN.md §5, "IVF wide top-K".
     ``mutable: True`` raises and names :class:`HipMutableIVFFlatIndex` (index
     type ``hip_ivf_mutable``), whose lists change in place; on this class
     ``update`` and ``remove`` only warn, as the reference's do. k <= 128 per
-    search (2k <= 128 with ``filter_ids``).
+    search (2k <= 128 with ``filter_ids``) without ``wide_k``.
 
     Below 1,024 items, or below nlist, ``build`` logs the reference's message
     and everything is delegated to an inner :class:`HipFlatIPIndex`.
@@ -1716,6 +1724,9 @@ class HipIVFFlatIndex(_HbmIndex):
         self.batch_min_queries = None if v is None else int(v)
         if self.batch_min_queries is not None and self.batch_min_queries < 1:
             raise ValueError(f"batch_min_queries={self.batch_min_queries}: None (off) or >= 1")
+        # ``wide_k``: searches of up to kernels.IVF_WIDE_MAX_K results (rt_ivf_topk_wide above 128)
+        self.wide_k = bool(self.config.get("wide_k", False))
+        self.max_k = kernels.IVF_WIDE_MAX_K if self.wide_k else kernels.IVF_MAX_K
 
     def _flat_config(self) -> Dict[str, Any]:
         cfg = {k: v for k, v in self.config.items()
@@ -1847,8 +1858,8 @@ class HipIVFFlatIndex(_HbmIndex):
             raise ValueError("Index not built yet")
         if self._flat is not None:
             return self._flat.search_tensors(query_embeddings, k, exclude_bits=exclude_bits, tag_filter=tag_filter)
-        if not 1 <= k <= kernels.IVF_MAX_K:
-            raise ValueError(f"k={k}: the MI355X IVF index returns 1..{kernels.IVF_MAX_K} results per query")
+        if not 1 <= k <= self.max_k:
+            raise ValueError(f"k={k}: the MI355X IVF index returns 1..{self.max_k} results per query")
         np_ = self._n_probe(nprobe)
         q32 = self._prepare(query_embeddings)
         exclude_bits = self._filter_bits(tag_filter, q32.shape[0], exclude_bits)
@@ -1860,6 +1871,8 @@ class HipIVFFlatIndex(_HbmIndex):
         # probe it (rt_ivf_topk_batch); the same results, bit for bit
         batch = self.batch_min_queries is not None and q32.shape[0] >= self.batch_min_queries
         scan = kernels.ivf_topk_batch if batch else kernels.ivf_topk
+        if k > kernels.IVF_MAX_K:   # wide_k: the wide selection; at or below 128 the scans above stay
+            scan = kernels.ivf_topk_wide
         return scan(q32.to(self.storage_dtype), self.index, self.list_offsets, self.row_pos, probes,
                     self.max_list_rows, k, exclude_bits=exclude_bits, **self._scan_operands())
 
@@ -2361,6 +2374,8 @@ class _IVFCodesIndex(HipIVFFlatIndex):
         name = type(self).__name__
         if cfg.get("online_max_batch"):
             raise ValueError(f"{name} has no resident searcher (online_max_batch): HipIVFFlatIndex has")
+        if cfg.get("wide_k"):
+            raise ValueError(f"{name} has no wide top-K scan (wide_k): HipIVFFlatIndex has")
         if cfg.get("batch_min_queries") is not None:
             if self.batch_scan_key() is not None:
                 raise ValueError(f"{name}: its list-major scan is keyed sq8_batch_min_queries; batch_min_queries "

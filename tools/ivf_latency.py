@@ -93,6 +93,13 @@ the p50 per round and arm, and the hipEvent p50 of B's scan call whole and split
 + grouping / scan / finish (rt_ivf_topk_batch_tuning), next to A's scan call. The bar, at
 nq = 4096: B's p50 in every round is below the MINIMUM of A's p50 over its rounds.
 
+``--legs wide`` (not in the default list): the wide top-K scan (rt_ivf_topk_wide, config key
+``wide_k``) at nprobe = 20, nq in ``--pq-nq``, arms alternating call by call, 3 rounds, p50 per
+round. (a) k = 128, the only shape both serve: rt_ivf_topk against rt_ivf_topk_wide over the same
+probes (scan and finish alone; the results must agree bit for bit) — the price of the wide
+selection. (b) k in {200, 1000}: whole ``search_tensors`` calls of the wide_k index against
+HipFlatIPIndex, the only thing that serves those k otherwise, with recall@k against its lists.
+
 ``--legs refine`` (not in the default list): the pq leg's protocol over ``hip_ivf`` float16 and,
 for M = 16 and M = 32, ``hip_ivf_pq`` plain, with ``,RFlat`` (float16 rows) and with
 ``,Refine(SQ8)``, plus the plain index at k = R = 100 (what a refined call scans before its
@@ -507,6 +514,68 @@ def leg_batch(args, storage, rows, queries, dev):
     return out
 
 
+def leg_wide(args, rows, dev):
+    """The wide leg: one JSON line per (storage, nq). ``rows``: fp32 unit rows on the device. nprobe = 20.
+    (a) k = 128, the scan and finish alone over the same probes: rt_ivf_topk against rt_ivf_topk_wide.
+    (b) k in {200, 1000}, whole ``search_tensors`` calls: the wide_k IVF index against HipFlatIPIndex."""
+    n, d, nprobe = rows.shape[0], rows.shape[1], 20
+    sizes = [int(x) for x in args.pq_nq.split(",")]
+    queries = torch.from_numpy(corpus(n, d, 4096, max(sizes), dev)[1]).to(dev)
+    out = []
+    for storage in args.storage.split(","):
+        ivf = HipIVFFlatIndex({"dimension": d, "metric": "cosine", "storage_dtype": storage, "nprobe": nprobe,
+                               "index_factory": f"IVF{args.nlist},Flat", "train_iters": args.train_iters,
+                               "wide_k": True})
+        ivf.build(rows, [])
+        flat = HipFlatIPIndex({"dimension": d, "metric": "cosine", "storage_dtype": storage})
+        flat.build(rows, [])
+        torch.cuda.synchronize()
+        for nq in sizes:
+            q = queries[:nq].contiguous()
+            q32 = ivf._prepare(q)
+            qs = q32.to(ivf.storage_dtype)
+            _, probes = (kernels.flatip_topk_online if nq <= kernels.ONLINE_MAX_NQ else kernels.flatip_topk)(
+                q32, ivf.centroids, nprobe)
+            calls = max(3, min(args.batch_calls, 20480 // nq))
+            lists = (qs, ivf.index, ivf.list_offsets, ivf.row_pos, probes, ivf.max_list_rows)
+
+            def synced(fn, *a):
+                def run():
+                    r = fn(*a)
+                    torch.cuda.synchronize()
+                    return r
+                return run
+
+            def rounds_of(sides):
+                names, rounds = list(sides), []
+                for r in range(3):
+                    order = names[r % len(names):] + names[:r % len(names)]
+                    rounds.append({"first": order[0],
+                                   **timed_alternating({name: sides[name] for name in order}, calls, 2)})
+                return {name: [r[name]["p50_ms"] for r in rounds] for name in names}
+
+            sides = {"A_ivf_topk": synced(kernels.ivf_topk, *lists, 128),
+                     "B_ivf_topk_wide": synced(kernels.ivf_topk_wide, *lists, 128)}
+            a, b = sides["A_ivf_topk"](), sides["B_ivf_topk_wide"]()
+            if not (torch.equal(a[1], b[1]) and torch.equal(a[0].view(torch.int32), b[0].view(torch.int32))):
+                raise SystemExit(f"wide leg {storage} nq={nq}: rt_ivf_topk and rt_ivf_topk_wide differ at k = 128")
+            case = {"leg": "wide", "storage": storage, "nq": nq, "nprobe": nprobe, "calls_per_round": calls,
+                    "plan": kernels.ivf_topk_plan(min(nq, 32768), nprobe, ivf.max_list_rows),
+                    "k128_equal_bit_for_bit": True, "k128_p50_ms": rounds_of(sides)}
+            for k in (200, 1000):
+                sides = {"B_ivf_wide": synced(ivf.search_tensors, q, k), "C_flat": synced(flat.search_tensors, q, k)}
+                got, want = sides["B_ivf_wide"](), sides["C_flat"]()
+                case[f"k{k}_p50_ms"] = rounds_of(sides)
+                case[f"k{k}_recall_vs_flat"] = round(recall(got[1].cpu().numpy(), want[1].cpu().numpy()), 4)
+                case[f"k{k}_workspace_bytes"] = int(kernels.native.lib().rt_ivf_topk_wide_workspace_bytes(
+                    nq, nprobe, ivf.max_list_rows, k))
+            print(json.dumps(case), flush=True)
+            out.append(case)
+        del ivf, flat
+        torch.cuda.empty_cache()
+    return out
+
+
 def leg_pq(args, rows, dev, leg="pq"):
     """The pq and sq8 legs: one JSON line per nq. ``rows``: fp32 unit rows on the device."""
     n, d, k, nprobe = rows.shape[0], rows.shape[1], 10, 20
@@ -703,8 +772,8 @@ def main():
     ap.add_argument("--nq", default="1,8")
     ap.add_argument("--chunk-tiles", default="", help="comma list of chunk floors (256-row tiles) for the scan alone")
     ap.add_argument("--train-iters", type=int, default=10)
-    ap.add_argument("--legs", default="search", help="comma list of: search (the default), exclude, mutate, batch, filter, mmr, pq, sq8, sq8batch, refine")
-    ap.add_argument("--pq-nq", default="1,8,256,4096", help="batch sizes of the pq, sq8 and refine legs")
+    ap.add_argument("--legs", default="search", help="comma list of: search (the default), exclude, mutate, batch, filter, mmr, pq, sq8, sq8batch, refine, wide")
+    ap.add_argument("--pq-nq", default="1,8,256,4096", help="batch sizes of the pq, sq8, refine and wide legs")
     ap.add_argument("--sq8batch-nq", default="256,1024,4096", help="batch sizes of the sq8batch leg")
     ap.add_argument("--mutate-sizes", default="1,64,1024", help="known rows per update call of the mutate leg")
     ap.add_argument("--mutate-calls", type=int, default=12, help="timed update calls per size (fewer for large sizes)")
@@ -720,7 +789,7 @@ def main():
     ids = []   # positions only: the id maps are not what is measured
     summary = {"rows": n, "dim": d, "k": k, "nlist": args.nlist, "cases": []}
     legs = args.legs.split(",")
-    if set(legs) - {"search", "exclude", "mutate", "batch", "filter", "mmr", "pq", "sq8", "sq8batch", "refine"}:
+    if set(legs) - {"search", "exclude", "mutate", "batch", "filter", "mmr", "pq", "sq8", "sq8batch", "refine", "wide"}:
         raise SystemExit(f"unknown leg in {args.legs!r}")
     for leg in ("pq", "sq8"):
         if leg in legs:
@@ -732,7 +801,10 @@ def main():
     if "refine" in legs:
         summary["refine"] = leg_refine(args, rows, dev)
         torch.cuda.empty_cache()
-    if not set(legs) - {"pq", "sq8", "sq8batch", "refine"}:
+    if "wide" in legs:
+        summary["wide"] = leg_wide(args, rows, dev)
+        torch.cuda.empty_cache()
+    if not set(legs) - {"pq", "sq8", "sq8batch", "refine", "wide"}:
         print(json.dumps(summary), flush=True)
         return
     if "batch" in legs:
